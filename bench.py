@@ -9,9 +9,13 @@ MSE + KL, backward, global-norm clip, AdamW, LR schedule — all through libluna
 sprites already resident in HBM (fp32 NCHW, normalised like train_hybrid.py:181-182).  Per-GPU batch is fixed
 (weak scaling); with N>1 the flat gradient buffer is averaged with one RCCL all-reduce per step.
 
-Prints ONE JSON line (rank 0) with the throughput, a `roofline` object for the dominant kernel (HIP events on the
-launch stream, collected by the library's per-launch profiler in extra steps after the timed region) and a
-`cpu_baseline` object (the CPU oracle timed on the host cores on a bounded sample).
+Prints ONE JSON line (rank 0) with the throughput (`value`, `ms_per_step` of the K timed steps).  A plain run does only
+that: set-up, warm-up, the K timed steps, the line.  `--full` adds everything else, after the timed region: a `roofline`
+object for the dominant kernel (HIP events on the launch stream, collected by the library's per-launch profiler in extra
+steps), the other BASELINE configurations (fp8 operands, batch 32 / latent 256, the full hybrid step and its variants)
+and `cpu_baseline` objects (the CPU oracle timed on the host cores on a bounded sample).
+
+`--dump-outputs DIR` writes what the last timed step computed (rank 0), see `dump_outputs`.
 """
 from __future__ import annotations
 
@@ -117,6 +121,32 @@ def cpu_baseline(batch: int, latent: int, steps: int, warm: int = 3):
                       f"{warm} warm-up + {steps} timed full training steps, median"}
 
 
+DUMP_MAX_IMAGES = 64         # per-image outputs are dumped for the first 64 images of the batch (recon: 12.6 MB)
+DUMP_PARAM_SAMPLE = 1 << 20  # fixed, seeded sample of the flat fp32 parameter buffer (4 MB)
+
+
+def dump_outputs(st, dirname: str) -> dict:
+    """What a caller of `VAEStepper.step` holds after the last timed step, as float32 / float64 .npy files in `dirname`:
+    recon, mu, logvar (the step's return values, first DUMP_MAX_IMAGES images), metrics (float64: recon_loss, kl_loss,
+    vae_loss, grad_norm of that step) and params_sample (the updated parameters at DUMP_PARAM_SAMPLE sorted indices drawn
+    with seed 0).  Returns {name: shape}."""
+    os.makedirs(dirname, exist_ok=True)
+    torch.cuda.synchronize()
+    recon, mu, logvar = st.last
+    met = st.metrics()
+    flat = st.vae._flat
+    idx = np.unique(np.random.default_rng(0).integers(0, flat.numel(), DUMP_PARAM_SAMPLE))
+    arrays = {"recon": recon[:DUMP_MAX_IMAGES], "mu": mu[:DUMP_MAX_IMAGES], "logvar": logvar[:DUMP_MAX_IMAGES],
+              "params_sample": flat[torch.from_numpy(idx).to(flat.device)],
+              "metrics": np.array([met[k] for k in ("recon_loss", "kl_loss", "vae_loss", "grad_norm")], dtype=np.float64)}
+    shapes = {}
+    for name, a in arrays.items():
+        a = a.detach().float().cpu().numpy() if torch.is_tensor(a) else a
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 MIN_WARMUP_STEPS = 300
 
 
@@ -127,6 +157,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=64, help="per-GPU batch")
     ap.add_argument("--latent", type=int, default=512)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the roofline leg (--prof-steps, --breakdown), the extra legs (--*-steps) and the CPU "
+                         "baselines (--cpu-*); without --full those options have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy (bench_outputs/ is git-ignored)")
     ap.add_argument("--prof-steps", type=int, default=3)
     ap.add_argument("--cpu-batch", type=int, default=0, help="batch of the main CPU-baseline leg (0 = the GPU leg's batch)")
     ap.add_argument("--cpu-steps", type=int, default=10, help="timed steps of each CPU-baseline leg (after --cpu-warmup warm-up steps; median)")
@@ -150,6 +185,10 @@ def main():
                     help="N > 1: gradient exchange = the direct all-to-all reduce-scatter + all-gather over all xGMI links (default; fp16 wire) "
                          "or one RCCL all-reduce per hand-over range (fp32 wire); every range is exchanged on a communication stream behind the backward")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.breakdown and not args.full:
+        ap.error("--breakdown prints the roofline leg's tables: it needs --full")
     args.dp_fp16 = (args.dp_fp16 or args.dp_exchange == "direct") and not args.dp_fp32
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -212,11 +251,13 @@ def main():
         elapsed = t.item()
     met = st.metrics()
     assert met["grads_finite"] == 1.0 and np.isfinite(met["recon_loss"]), met
-    # the host's own cost of enqueuing a step: a burst of 5 steps into an EMPTY queue, outside the timed region (host_enqueue_ms
-    # above is taken with ~20 steps already queued, where the runtime's back-pressure, not the host, sets the pace)
-    torch.cuda.synchronize()
-    host_idle_s = run(5) / 5
-    torch.cuda.synchronize()
+    dumped = dump_outputs(st, args.dump_outputs) if args.dump_outputs and rank == 0 else None
+    if args.full:
+        # the host's own cost of enqueuing a step: a burst of 5 steps into an EMPTY queue, outside the timed region (host_enqueue_ms
+        # above is taken with ~20 steps already queued, where the runtime's back-pressure, not the host, sets the pace)
+        torch.cuda.synchronize()
+        host_idle_s = run(5) / 5
+        torch.cuda.synchronize()
     dp_info = None
     if dist is not None:
         # what actually ran: ranks of the process group and the device each one drove, bytes handed to the exchange per backward
@@ -231,6 +272,40 @@ def main():
 
     out = None
     if rank == 0:
+        out = {
+            "metric": "128x128 sprites/sec, VAE training step (train_hybrid.py _process_batch), latent_dim=512",
+            "value": world * B * args.steps / elapsed,
+            "unit": "sprites/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "warmup_steps_run": warmup_run,
+            "ms_per_step": 1e3 * elapsed / args.steps,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f16" if args.precision == "fp16" else "fp8 (e4m3 forward operands) / f16 backward",
+            "data": "synthetic",
+            "config": {"workload": f"VAE-only training step (fwd+MSE/KL+bwd+clip+AdamW), per-GPU batch {B}, latent_dim {args.latent}, "
+                                   "teacher scalar 0 (--reward_scale 0 --quality_weight 0; the full hybrid step of BASELINE config 3 is the config3_full_hybrid object of a --full run at N=1), "
+                                   "gradient_accumulation_steps 1, " + ("fp16 MFMA operands" if args.precision == "fp16" else
+                                   "e4m3 MFMA operands in the forward convs with Cin % 128 == 0, fp16 elsewhere") + " / fp32 accumulate, fp32 master weights",
+                       "global_batch": world * B, "latent_dim": args.latent,
+                       "parallelism": f"dp{world}" if world > 1 else "single",
+                       # how the three Linear layers' weight gradients (82 % of the parameters) exist in this run: never written
+                       # (Gram-matrix norm + AdamW forming the tiles, csrc/lo_lowrank.hip), exchanged as factors, or written out
+                       "linear_weight_gradients": ("factored (never materialised)" if getattr(st, "linear_factored", False) and world == 1
+                                                   else ("factors all-gathered, averaged matrices formed per rank" if getattr(st, "dp_factored", False) and world > 1
+                                                         else "materialised"))},
+            "host_enqueue_ms": 1e3 * host_enqueue_s / args.steps,     # host time per step inside the timed region (includes queue back-pressure)
+            "final_metrics": {k: met[k] for k in ("recon_loss", "kl_loss", "grad_norm")},
+        }
+        if world > 1:
+            out["data_parallel"] = dp_info
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+    if rank == 0 and args.full:
+        out["host_enqueue_ms_idle_queue"] = 1e3 * host_idle_s         # the host's own cost: 5 steps enqueued into an empty queue (launch-bound only when THIS nears ms_per_step)
         # ---- roofline leg: per-launch HIP events on the launch stream, extra steps after the timed region
         rows = {}
         if args.prof_steps > 0:
@@ -350,38 +425,7 @@ def main():
                                  f"{(r[3] / (r[0] * 1e-3) / 1e9 if r[0] > 0 else 0):8.1f} GB/s  "
                                  f"floor {floor_ms / max(args.prof_steps, 1):7.4f} ms ({(floor_ms / r[0] if r[0] > 0 else 0):4.2f} of floor)\n")
             sys.stderr.write(f"sum of kernel time {total_ms / max(args.prof_steps, 1):.4f} ms/step\n")
-        out = {
-            "metric": "128x128 sprites/sec, VAE training step (train_hybrid.py _process_batch), latent_dim=512",
-            "value": world * B * args.steps / elapsed,
-            "unit": "sprites/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "warmup_steps_run": warmup_run,
-            "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f16" if args.precision == "fp16" else "fp8 (e4m3 forward operands) / f16 backward",
-            "data": "synthetic",
-            "config": {"workload": f"VAE-only training step (fwd+MSE/KL+bwd+clip+AdamW), per-GPU batch {B}, latent_dim {args.latent}, "
-                                   "teacher scalar 0 (--reward_scale 0 --quality_weight 0; the full hybrid step of BASELINE config 3 is the config3_full_hybrid object at N=1), "
-                                   "gradient_accumulation_steps 1, " + ("fp16 MFMA operands" if args.precision == "fp16" else
-                                   "e4m3 MFMA operands in the forward convs with Cin % 128 == 0, fp16 elsewhere") + " / fp32 accumulate, fp32 master weights",
-                       "global_batch": world * B, "latent_dim": args.latent,
-                       "parallelism": f"dp{world}" if world > 1 else "single",
-                       # how the three Linear layers' weight gradients (82 % of the parameters) exist in this run: never written
-                       # (Gram-matrix norm + AdamW forming the tiles, csrc/lo_lowrank.hip), exchanged as factors, or written out
-                       "linear_weight_gradients": ("factored (never materialised)" if getattr(st, "linear_factored", False) and world == 1
-                                                   else ("factors all-gathered, averaged matrices formed per rank" if getattr(st, "dp_factored", False) and world > 1
-                                                         else "materialised"))},
-            "roofline": roof,
-            "host_enqueue_ms": 1e3 * host_enqueue_s / args.steps,     # host time per step inside the timed region (includes queue back-pressure)
-            "host_enqueue_ms_idle_queue": 1e3 * host_idle_s,          # the host's own cost: 5 steps enqueued into an empty queue (launch-bound only when THIS nears ms_per_step)
-            "final_metrics": {k: met[k] for k in ("recon_loss", "kl_loss", "grad_norm")},
-        }
-        if world > 1:
-            out["data_parallel"] = dp_info
+        out["roofline"] = roof
         if world == 1 and args.fp8_steps > 0 and args.precision == "fp16":
             # BASELINE config 5: the same VAE-only step with e4m3 operands in the forward convs; loss parity against the fp16 mode
             # from identical weights, inputs and noise (first step), then throughput

@@ -170,9 +170,9 @@ def test_cli_teacher_full_backward_flag_on_gpu(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_line_contract(tmp_path):
-    """bench.py prints ONE JSON line with the driver's keys plus `roofline` and (when asked) `cpu_baseline`."""
+    """bench.py --full prints ONE JSON line with the driver's keys plus `roofline` and (when asked) `cpu_baseline`."""
     import json
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--min-warmup", "0", "--batch", "8", "--latent", "256",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--min-warmup", "0", "--batch", "8", "--latent", "256",
                         "--hybrid-steps", "1", "--cpu-batch", "2", "--cpu-steps", "1", "--cpu-warmup", "1", "--cpu-hybrid-steps", "0",
                         "--fp8-steps", "0", "--config2-steps", "0", "--highend-steps", "0", "--fullbwd-steps", "0"], capture_output=True, text=True, timeout=900)      # the legs this test does not look at: off
     assert r.returncode == 0, r.stderr[-2000:]
@@ -193,13 +193,44 @@ def test_bench_line_contract(tmp_path):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain bench.py run prints the headline alone (no roofline, extra legs or CPU baselines); --dump-outputs writes the last
+    timed step's outputs as float32 / float64 .npy files, and two runs with the same arguments compute the same outputs."""
+    import json
+    dumps = []
+    for run in ("a", "b"):
+        d_out = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--min-warmup", "0", "--batch", "8",
+                            "--latent", "256", "--dump-outputs", str(d_out)], capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 4 and d["unit"] == "sprites/s" and d["higher_is_better"] is True and d["dtype"] == "f16"
+        assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 8) < 1e-6          # value and ms_per_step describe the same 4 timed steps
+        for k in ("roofline", "cpu_baseline", "config3_full_hybrid", "config2_b32_l256", "config5_fp8_forward", "host_enqueue_ms_idle_queue"):
+            assert k not in d, k
+        files = {f.stem: np.load(f) for f in d_out.glob("*.npy")}
+        assert set(files) == set(d["dumped_outputs"]) == {"recon", "mu", "logvar", "metrics", "params_sample"}
+        assert files["recon"].shape == (8, 3, 128, 128) and files["mu"].shape == (8, 256) and files["logvar"].shape == (8, 256)
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in files.values())
+        assert sum(a.nbytes for a in files.values()) <= 64 << 20
+        assert abs(files["metrics"][0] - d["final_metrics"]["recon_loss"]) <= 1e-6 * max(1.0, abs(d["final_metrics"]["recon_loss"]))
+        dumps.append(files)
+    for k in dumps[0]:
+        np.testing.assert_allclose(dumps[1][k], dumps[0][k], rtol=1e-3, atol=1e-4, err_msg=k)
+
+
+@pytest.mark.gpu
 def test_bench_two_rank_control_flow_on_one_gpu():
     """The driver's N > 1 launch (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`) rehearsed with two
     ranks sharing the one GPU of the test box (gloo carries the collectives; RCCL refuses two ranks on one device): barriers,
     max-over-ranks timing, the rank-0-only roofline leg (which must not issue collectives) and the single JSON line."""
     import json
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--min-warmup", "0",
+                        "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--min-warmup", "0",
                         "--batch", "4", "--latent", "256", "--dist-backend", "gloo"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]

@@ -6,8 +6,8 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 O=gpurun_out/prof_refresh
 rm -rf $O && mkdir -p $O
-python3 bench.py --steps 50 --warmup 10 --breakdown > $O/bench.json 2> $O/bench_breakdown.txt
-LO_PROF_LAYERS=1 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --hybrid-steps 0 --fp8-steps 0 --config2-steps 0 --highend-steps 0 --breakdown > /dev/null 2> $O/bench_per_layer.txt
+python3 bench.py --full --steps 50 --warmup 10 --breakdown > $O/bench.json 2> $O/bench_breakdown.txt
+LO_PROF_LAYERS=1 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --hybrid-steps 0 --fp8-steps 0 --config2-steps 0 --highend-steps 0 --breakdown > /dev/null 2> $O/bench_per_layer.txt
 python3 tools/vendor_ceiling.py --mine $O/bench_per_layer.txt > $O/vendor_ceiling.txt 2> $O/vendor_ceiling.err
 python3 tools/vendor_teacher_conv.py > $O/vendor_teacher_conv.txt 2> $O/vendor_teacher_conv.err
 python3 tools/fp8_layer_table.py > $O/fp8_per_layer.txt 2> $O/fp8_per_layer.err
@@ -20,7 +20,7 @@ echo "bench + probes done" >&2
 # kernel durations are compared with the side stream switched off in BOTH measurements (the library's HIP-event leg always runs
 # that way): under concurrency - and under the tracer's kernel serialisation of a two-stream schedule - a kernel's duration is not a
 # property of the kernel.  The default schedule is traced as well (..._overlap_on).
-FAST="--no-cpu-baseline --hybrid-steps 0 --fp8-steps 0 --config2-steps 0 --highend-steps 0"
+FAST="--full --no-cpu-baseline --hybrid-steps 0 --fp8-steps 0 --config2-steps 0 --highend-steps 0"
 export LO_NO_OVERLAP=1
 rocprofv3 --kernel-trace --stats -d $O/rp_bench -o bench -- python3 bench.py --steps 20 --warmup 5 $FAST > $O/bench_under_rocprof.json 2> $O/rp_bench.err
 unset LO_NO_OVERLAP
