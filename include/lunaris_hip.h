@@ -90,6 +90,10 @@ int lo_gn_mish_backward(const void* dy, const void* v, const void* other, const 
 /* first conv Conv2d(3,64,k3,s2,p1) on fp32 NCHW images (lunar_generate.py:95) and its weight gradient */
 int lo_first_conv_forward(const float* x, const float* w, const float* bias, void* v, float* gn_partial, int B, void* stream);
 int lo_first_conv_wgrad_op(const float* x, const void* dv, float* partial /*B*16*1728*/, float* dw, int B, float scale, void* stream);
+/* data gradient of a 3x3 / padding 1 conv with 3 input channels onto the images: dx fp32 NCHW [B,3,128,128] = scale * conv2d_input(dy, w),
+ * dy fp16 NHWC [B][128/stride][128/stride][cout], w fp32 [cout][3][3][3].  Built for (stride 2, cout 64: the VAE's encoder.down1.0) and
+ * (stride 1, cout 32: the teacher's feature_extractor.conv1.0).  Deterministic (no atomics). */
+int lo_image_dgrad_op(const void* dy, int cout, int stride, const float* w, int B, float scale, float* dx, void* stream);
 /* final conv Conv2d(32,3,k3,p1)+tanh (+MSE partial sums, B*64 floats) (lunar_generate.py:192,227-228; train_hybrid.py:859) */
 int lo_final_conv_forward(const void* a4, const float* w, const float* bias, const float* target, float* recon,
                           float* mse_partial, int B, void* stream);
@@ -223,6 +227,10 @@ int lo_vae_decoder_backward(LoVae* h, const float* flat_params, void* ws, const 
 int lo_vae_encoder_backward(LoVae* h, const float* x, const float* flat_params, void* ws, const float* gmu, const float* glv,
                             const float* gskip0, const float* gskip1, const float* gskip2, float loss_scale, float* flat_grads,
                             void* stream);
+/* the same, and the gradient wrt the images x: dx fp32 NCHW [B,3,128,128] (NULL = not wanted; lo_vae_encoder_backward is this with NULL) */
+int lo_vae_encoder_backward_dx(LoVae* h, const float* x, const float* flat_params, void* ws, const float* gmu, const float* glv,
+                               const float* gskip0, const float* gskip1, const float* gskip2, float loss_scale, float* flat_grads,
+                               float* dx, void* stream);
 /* reduce the loss partial sums of the last forward; losses_dev[4] = recon_loss, kl_loss, vae_loss, pg_loss.
  * vae_loss = (recon_weight*recon + kl_weight*kl - mean_advantage*recon)/accum  (train_hybrid.py:886-889,895).
  * adv_dev (device scalar) overrides mean_advantage when not NULL.  Also prepares the gradient seeds for
@@ -235,6 +243,11 @@ int lo_vae_loss(LoVae* h, void* ws, float recon_weight, float kl_weight, float m
 int lo_vae_backward(LoVae* h, const float* x, const float* flat_params, void* ws, const float* recon, const float* target,
                     int fused, const float* drecon, const float* gmu, const float* glv, float loss_scale,
                     float* flat_grads, void* stream);
+/* the same, and the gradient wrt the images x: dx fp32 NCHW [B,3,128,128] (NULL = not wanted; lo_vae_backward is this with NULL).  Meant for
+ * fused = 0 (the module's autograd node); the steppers do not ask for it. */
+int lo_vae_backward_dx(LoVae* h, const float* x, const float* flat_params, void* ws, const float* recon, const float* target,
+                       int fused, const float* drecon, const float* gmu, const float* glv, float loss_scale,
+                       float* flat_grads, float* dx, void* stream);
 
 /* GroupNorm + Mish run inside the producing convolution's epilogue wherever the kernel that owns the layer supports it (the
  * workgroups holding one sample's tiles exchange their partial sums through the workspace and wait for each other; csrc/lo_common.h,
@@ -351,6 +364,12 @@ int lo_teacher_full_backward_ex(LoTeacher* h, const float* images_nchw, float* f
                                 const float* pooled_e, const float* raw_q, const float* expert_weights, const float* d_quality,
                                 const float* d_weights, float dropout_p, uint64_t drop_seed, float gscale, float* rows, float* flat_grads,
                                 void* stream);
+/* the same, and the gradient wrt the images: dx fp32 NCHW [B,3,128,128] (NULL = not wanted; lo_teacher_full_backward_ex is this with NULL).
+ * The autograd node of a train-mode LunarMoETeacher whose input requires grad calls it. */
+int lo_teacher_full_backward_dx(LoTeacher* h, const float* images_nchw, float* flat_state, void* ws, void* bws, const float* pooled_f,
+                                const float* pooled_e, const float* raw_q, const float* expert_weights, const float* d_quality,
+                                const float* d_weights, float dropout_p, uint64_t drop_seed, float gscale, float* rows, float* flat_grads,
+                                float* dx, void* stream);
 /* clip_grad_norm_(teacher.parameters()) + AdamW (train_hybrid.py:914, 922) with every teacher parameter live: the norm over the whole
  * flat gradient of lo_teacher_full_backward, the update over exactly the tensors that have a .grad in the reference (not the
  * BatchNorm buffers, not the style / prompt / semantic heads, whose .grad is None there).  m, v: lo_teacher_flat_elems floats each,

@@ -109,6 +109,9 @@ extern "C" int lo_first_conv_forward(const float* x, const float* w, const float
 extern "C" int lo_first_conv_wgrad_op(const float* x, const void* dv, float* partial, float* dw, int B, float scale, void* stream) {
   return lo_first_conv_wgrad(x, (const f16*)dv, partial, dw, B, scale, S(stream));
 }
+extern "C" int lo_image_dgrad_op(const void* dy, int cout, int stride, const float* w, int B, float scale, float* dx, void* stream) {
+  return lo_image_dgrad((const f16*)dy, cout, stride, w, B, scale, dx, S(stream));
+}
 extern "C" int lo_final_conv_forward(const void* a4, const float* w, const float* bias, const float* target, float* recon,
                                      float* mse_partial, int B, void* stream) {
   return lo_final_conv_fwd((const f16*)a4, w, bias, target, recon, mse_partial, B, S(stream));
@@ -1332,16 +1335,24 @@ static int conv_gn_bwd(LoVae* h, ConvLayer& c, const f16* dy, const f16* other, 
 }
 
 // phase 5 / 6 = Decoder / Encoder backward on their own (the module boundary: lo_vae_decoder_backward / lo_vae_encoder_backward);
-// the feature-map gradients cross as fp32 NCHW tensors
-struct LoSplitBwd { float* dz; float* dskip[3]; const float* gskip[3]; };
+// the feature-map gradients cross as fp32 NCHW tensors.  dx (any phase that runs encoder stage 1; NULL = not wanted): the gradient wrt
+// the images, fp32 NCHW [B,3,128,128]
+struct LoSplitBwd { float* dz; float* dskip[3]; const float* gskip[3]; float* dx; };
 static int vae_backward_impl(LoVae* h, int phase, const float* x, const float* P, void* ws, const float* recon, const float* target,
                              int fused, const float* drecon, const float* gmu, const float* glv, float loss_scale,
                              float* G, void* stream, const LoSplitBwd* sp = nullptr);
 
+extern "C" int lo_vae_backward_dx(LoVae* h, const float* x, const float* P, void* ws, const float* recon, const float* target,
+                                  int fused, const float* drecon, const float* gmu, const float* glv, float loss_scale,
+                                  float* G, float* dx, void* stream) {
+  if (!dx) return vae_backward_impl(h, 0, x, P, ws, recon, target, fused, drecon, gmu, glv, loss_scale, G, stream);
+  LoSplitBwd sp{nullptr, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, dx};
+  return vae_backward_impl(h, 0, x, P, ws, recon, target, fused, drecon, gmu, glv, loss_scale, G, stream, &sp);
+}
 extern "C" int lo_vae_backward(LoVae* h, const float* x, const float* P, void* ws, const float* recon, const float* target,
                                int fused, const float* drecon, const float* gmu, const float* glv, float loss_scale,
                                float* G, void* stream) {
-  return vae_backward_impl(h, 0, x, P, ws, recon, target, fused, drecon, gmu, glv, loss_scale, G, stream);
+  return lo_vae_backward_dx(h, x, P, ws, recon, target, fused, drecon, gmu, glv, loss_scale, G, nullptr, stream);
 }
 extern "C" int lo_vae_backward_phase(LoVae* h, int phase, const float* x, const float* P, void* ws, const float* recon,
                                      const float* target, int fused, const float* drecon, const float* gmu, const float* glv,
@@ -1637,6 +1648,8 @@ static int vae_backward_impl(LoVae* h, int phase, const float* x, const float* P
         LO_TRY(lo_gn_bwd_nofinal(Gc, WSP(f16, c0.o_v), nullptr, WSP(float, c0.o_stats), PRM(c0.p_gw), PRM(c0.p_gb), nullptr, Gd,
                                  WSP(float, c0.o_P1), WSP(float, c0.o_P2), B, 64 * 64, 64, 0, st, c0.np1));
       LO_TRY(lo_first_conv_wgrad(x, dv0, WSP(float, h->o_fcw_part), GRD(c0.p_w), B, inv, st));
+      // the images' gradient (lo_vae_backward_dx / lo_vae_encoder_backward_dx): the same dv0 through the transposed first conv
+      if (sp && sp->dx) LO_TRY(lo_image_dgrad(dv0, 64, 2, PRM(c0.p_w), B, inv, sp->dx, st));
     }
   }
   // ---- GroupNorm affine + conv bias gradients: all 16 layers in one launch (single call), or those of the stages this call ran.
@@ -1664,16 +1677,22 @@ static int vae_backward_impl(LoVae* h, int phase, const float* x, const float* P
 extern "C" int lo_vae_decoder_backward(LoVae* h, const float* P, void* ws, const float* recon, const float* drecon, float loss_scale,
                                        float* dz, float* dskip0, float* dskip1, float* dskip2, float* G, void* stream) {
   LO_REQUIRE(h && drecon && dz, "lo_vae_decoder_backward: null argument");
-  LoSplitBwd sp{dz, {dskip0, dskip1, dskip2}, {nullptr, nullptr, nullptr}};
+  LoSplitBwd sp{dz, {dskip0, dskip1, dskip2}, {nullptr, nullptr, nullptr}, nullptr};
   return vae_backward_impl(h, 5, nullptr, P, ws, recon, nullptr, 0, drecon, nullptr, nullptr, loss_scale, G, stream, &sp);
 }
 // Backward of lo_vae_encode (Encoder.forward, lunar_generate.py:127-153): upstream gradients of mu, logvar [B,L] and of the skip
 // maps (fp32 NCHW; any of them may be NULL = zero) -> the encoder's parameter gradients ([0, decoder.fc.weight) of flat_grads).
+// lo_vae_encoder_backward_dx also writes the gradient wrt x (fp32 NCHW [B,3,128,128]; NULL = not wanted).
+extern "C" int lo_vae_encoder_backward_dx(LoVae* h, const float* x, const float* P, void* ws, const float* gmu, const float* glv,
+                                          const float* gskip0, const float* gskip1, const float* gskip2, float loss_scale, float* G,
+                                          float* dx, void* stream) {
+  LoSplitBwd sp{nullptr, {nullptr, nullptr, nullptr}, {gskip0, gskip1, gskip2}, dx};
+  return vae_backward_impl(h, 6, x, P, ws, nullptr, nullptr, 0, nullptr, gmu, glv, loss_scale, G, stream, &sp);
+}
 extern "C" int lo_vae_encoder_backward(LoVae* h, const float* x, const float* P, void* ws, const float* gmu, const float* glv,
                                        const float* gskip0, const float* gskip1, const float* gskip2, float loss_scale, float* G,
                                        void* stream) {
-  LoSplitBwd sp{nullptr, {nullptr, nullptr, nullptr}, {gskip0, gskip1, gskip2}};
-  return vae_backward_impl(h, 6, x, P, ws, nullptr, nullptr, 0, nullptr, gmu, glv, loss_scale, G, stream, &sp);
+  return lo_vae_encoder_backward_dx(h, x, P, ws, gmu, glv, gskip0, gskip1, gskip2, loss_scale, G, nullptr, stream);
 }
 
 // The Linear-layer weight gradients of the last fused backward written out after all (tests, tools, anybody who reads

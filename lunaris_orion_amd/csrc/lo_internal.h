@@ -105,6 +105,10 @@ int lo_nchw_f32_to_nhwc_f16(const float* src, f16* dst, int B, int HW, int C, fl
 int lo_first_conv_fwd(const float* x, const float* w, const float* bias, f16* v, float* gn_partial, int B, hipStream_t st);
 int lo_first_conv_wgrad(const float* x, const f16* dv, float* partial, float* dw, int B, float scale, hipStream_t st);
 int lo_colsum(const float* partial, float* out, int nrow, int ncol, int stride, float scale, hipStream_t st);
+
+// lo_imgdgrad.hip: data gradient of a 3x3 / padding 1 conv with 3 input channels onto fp32 NCHW [B,3,128,128] images
+// (stride 1 with 32 channels: the teacher's conv1; stride 2 with 64 channels: the VAE's first conv).  dy fp16 NHWC, w fp32 [cout][3][3][3]
+int lo_image_dgrad(const f16* dy, int cout, int stride, const float* w, int B, float scale, float* dx, hipStream_t st);
 int lo_final_conv_fwd(const f16* a4, const float* w, const float* bias, const float* target, float* recon,
                       float* mse_partial, int B, hipStream_t st);
 int lo_final_conv_bwd(const f16* a4, const float* w, const float* recon, const float* target, const float* drecon,

@@ -817,8 +817,8 @@ static int tb_fe_forward(TbCtx& c, const float* x, int train, float* pool_partia
   LO_TRYT(t_bn_apply(h, TB(f16, c.pl.o_rawF), nullptr, nullptr, TB(f16, c.pl.o_feat), 128, 128, 0, 0, pool_partial, ws, st));
   return LO_OK;
 }
-// ... and backward, from dfeat (gradient wrt the features, scaled)
-static int tb_fe_backward(TbCtx& c, const float* x) {
+// ... and backward, from dfeat (gradient wrt the features, scaled); dx (NULL = not wanted): the gradient wrt the images
+static int tb_fe_backward(TbCtx& c, const float* x, float* dx) {
   LoTeacher* h = c.h; float* P = c.P; float* G = c.G; void* bws = c.bws; hipStream_t st = c.st;
   const int B = h->B;
   const size_t px = (size_t)B * T_HW;
@@ -872,12 +872,13 @@ static int tb_fe_backward(TbCtx& c, const float* x) {
     LO_TRYT(lo_colsum(TB(float, c.pl.o_part), TG(q + ".0.weight"), B * 128, 32 * K * K, 32 * K * K, c.inv_g, st));
     LO_TRYT(lo_colsum(TB(float, c.pl.o_bpart), TG(q + ".0.bias"), B * 128, 32, 32, c.inv_g, st));
   }
-  // BatchNorm + LeakyReLU of conv1, then its weight gradient (the images need no gradient: the teacher sees recon.detach())
+  // BatchNorm + LeakyReLU of conv1, then its weight gradient and -- for a caller whose images require grad -- its data gradient
   LO_TRYT(tb_bn_backward(c, dn0, 32, 0, TB(f16, c.pl.o_raw32), 32, 0, TB(float, c.pl.o_mr[3]), fe + ".conv1.2", nullptr, nullptr, ddw, 32, 0, 32, 1, 0, 0, 0, 0));
   hipLaunchKernelGGL(lo_tb_conv1_wgrad_kernel, dim3(128, B), dim3(256), 0, st, x, ddw, TB(float, c.pl.o_part), TB(float, c.pl.o_bpart));
   LO_LAUNCH_CHECK("tb_conv1_wgrad");
   LO_TRYT(lo_colsum(TB(float, c.pl.o_part), TG(fe + ".conv1.0.weight"), B * 128, 864, 864, c.inv_g, st));
   LO_TRYT(lo_colsum(TB(float, c.pl.o_bpart), TG(fe + ".conv1.0.bias"), B * 128, 32, 32, c.inv_g, st));
+  if (dx) LO_TRYT(lo_image_dgrad(ddw, 32, 1, TP(fe + ".conv1.0.weight"), B, c.inv_g, dx, st));
   return LO_OK;
 }
 
@@ -953,7 +954,7 @@ extern "C" int lo_teacher_forward_keep(LoTeacher* h, const float* x, float* P, v
 // written, everything else is zeroed.
 static int tb_full_backward_impl(LoTeacher* h, const float* x, float* P, void* ws, void* bws, const float* pooled_f, const float* pooled_e,
                                  const float* raw_q, const float* expert_weights, const float* dq_up, const float* dw_up, float coef,
-                                 float drop_p, uint64_t drop_seed, float gscale, float* rows, float* grads, void* stream) {
+                                 float drop_p, uint64_t drop_seed, float gscale, float* rows, float* grads, float* dx, void* stream) {
   LO_REQUIRE(h && x && P && ws && bws && expert_weights && rows && grads, "lo_teacher_full_backward: null argument");
   LO_REQUIRE(gscale > 0.f, "lo_teacher_full_backward: gscale must be positive");
   LO_REQUIRE(h->last_path >= 0, "lo_teacher_full_backward: no forward has run on this engine");
@@ -995,7 +996,7 @@ static int tb_full_backward_impl(LoTeacher* h, const float* x, float* P, void* w
     }
   }
   // pass 3: feature extractor
-  return tb_fe_backward(c, x);
+  return tb_fe_backward(c, x, dx);
 }
 
 // clip_grad_norm_ + AdamW over the teacher's parameters in the full-backward mode (train_hybrid.py:914, 922 with every parameter
@@ -1046,16 +1047,23 @@ extern "C" int lo_teacher_full_backward(LoTeacher* h, const float* x, float* P, 
                                         float gscale, float* rows, float* grads, void* stream) {
   LO_REQUIRE(h && ws, "lo_teacher_full_backward: null argument");
   return tb_full_backward_impl(h, x, P, ws, bws, TW(float, h->o_pool_f), TW(float, h->o_pool_e), TW(float, h->o_rawq), expert_weights, nullptr, nullptr,
-                               coef, h->last_p, h->last_seed, gscale, rows, grads, stream);
+                               coef, h->last_p, h->last_seed, gscale, rows, grads, nullptr, stream);
 }
 // The same backward for arbitrary upstream gradients of quality_scores [B][4] / expert_weights [B][E] (either may be NULL), with the
 // head inputs, dropout_p and call seed of the forward being differentiated passed explicitly (lo_teacher_heads_saved: a caller may
 // have run other forwards since) -- what the module's autograd node calls (LunarMoETeacher(full_backward=True)).  The images must be
 // the ones of that forward.  Upstream gradients should be of order 1 (the caller normalises a foreign loss scale: lo_grad_scale_pick).
+// lo_teacher_full_backward_dx also writes the gradient wrt the images, fp32 NCHW [B,3,128,128] (NULL = not wanted), from the same pass.
+extern "C" int lo_teacher_full_backward_dx(LoTeacher* h, const float* x, float* P, void* ws, void* bws, const float* pooled_f, const float* pooled_e,
+                                           const float* raw_q, const float* expert_weights, const float* d_quality, const float* d_weights,
+                                           float dropout_p, uint64_t drop_seed, float gscale, float* rows, float* grads, float* dx, void* stream) {
+  LO_REQUIRE(pooled_f && pooled_e && raw_q && (d_quality || d_weights), "lo_teacher_full_backward_ex: null argument");
+  return tb_full_backward_impl(h, x, P, ws, bws, pooled_f, pooled_e, raw_q, expert_weights, d_quality, d_weights, 0.f, dropout_p, drop_seed, gscale,
+                               rows, grads, dx, stream);
+}
 extern "C" int lo_teacher_full_backward_ex(LoTeacher* h, const float* x, float* P, void* ws, void* bws, const float* pooled_f, const float* pooled_e,
                                            const float* raw_q, const float* expert_weights, const float* d_quality, const float* d_weights,
                                            float dropout_p, uint64_t drop_seed, float gscale, float* rows, float* grads, void* stream) {
-  LO_REQUIRE(pooled_f && pooled_e && raw_q && (d_quality || d_weights), "lo_teacher_full_backward_ex: null argument");
-  return tb_full_backward_impl(h, x, P, ws, bws, pooled_f, pooled_e, raw_q, expert_weights, d_quality, d_weights, 0.f, dropout_p, drop_seed, gscale,
-                               rows, grads, stream);
+  return lo_teacher_full_backward_dx(h, x, P, ws, bws, pooled_f, pooled_e, raw_q, expert_weights, d_quality, d_weights, dropout_p, drop_seed,
+                                     gscale, rows, grads, nullptr, stream);
 }

@@ -28,6 +28,7 @@ README's High-End recipe, /root/reference/README.md:102-118: a generic path with
 from __future__ import annotations
 
 import ctypes as C
+import warnings
 from typing import Dict, Optional
 
 import torch
@@ -107,13 +108,15 @@ class _TeacherFunction(torch.autograd.Function):
     """LunarMoETeacher.forward as an autograd node over the gate / quality-head parameters (lunar_evaluator.py:353-373, 417,
     431-432): differentiable outputs quality_scores [B,4] and expert_weights [B,E]; the embeddings and the semantic score are
     returned without a graph (nothing in the reference step differentiates them).  The head inputs of THIS call (pooled
-    features, pre-weighting logits, dropout stream) are copied out of the workspace, so later forward calls do not disturb it."""
+    features, pre-weighting logits, dropout stream) are copied out of the workspace, so later forward calls do not disturb it.
+    want_dx (train mode, input requires grad): the full backward with the images' gradient (lo_teacher_full_backward_dx)."""
 
     @staticmethod
-    def forward(ctx, model, x, *live):
-        full = model.all_parameters_live and model.training
-        out, eng, p, seed = model._native_forward(x, keep=full)
-        ctx.full, ctx.x = full, (x if full else None)
+    def forward(ctx, model, want_dx, x, *live):
+        full = (model.all_parameters_live or want_dx) and model.training
+        xd = x.detach().contiguous().float()
+        out, eng, p, seed = model._native_forward(xd, keep=full)
+        ctx.full, ctx.x, ctx.want_dx, ctx.x_dtype = full, (xd if full else None), bool(want_dx and full), x.dtype
         offs, elems = (C.c_size_t * 3)(), (C.c_size_t * 3)()
         _lib.check(_lib.lib.lo_teacher_heads_saved(eng.handle, offs, elems), "lo_teacher_heads_saved")
         saved = [eng.ws[offs[i]:offs[i] + 4 * elems[i]].view(torch.float32).clone() for i in range(3)]
@@ -134,20 +137,24 @@ class _TeacherFunction(torch.autograd.Function):
         _lib.check(_lib.lib.lo_teacher_grad_range(eng.handle, C.byref(b), C.byref(e)), "lo_teacher_grad_range")
         rows = torch.empty(w.shape[0] * (e.value - b.value), dtype=torch.float32, device=w.device)
         grads = torch.zeros_like(model._flat)
+        dx = None
         if ctx.full and (gq is not None or gw is not None):
-            # every parameter on the path (lo_teacher_full_backward_ex).  A foreign loss scale (GradScaler: 65 536) is divided out on the
+            # every parameter on the path (lo_teacher_full_backward_dx; dx = NULL unless the images require grad).  A foreign loss scale (GradScaler: 65 536) is divided out on the
             # device first, like at the VAE's boundary, so that the fp16 activation gradients see upstream values of order 1
             from .vae import _normalise_upstream
             scr, (gq, gw) = _normalise_upstream([gq, gw])
             B = w.shape[0]
             if getattr(eng, "bws", None) is None:
                 eng.bws = torch.empty(_lib.lib.lo_teacher_full_backward_bytes(eng.handle), dtype=torch.uint8, device=w.device)
-            _lib.check(_lib.lib.lo_teacher_full_backward_ex(eng.handle, ctx.x.data_ptr(), model._flat.data_ptr(), eng.ws.data_ptr(), eng.bws.data_ptr(),
+            dx = torch.empty_like(ctx.x) if ctx.want_dx and ctx.needs_input_grad[2] else None
+            _lib.check(_lib.lib.lo_teacher_full_backward_dx(eng.handle, ctx.x.data_ptr(), model._flat.data_ptr(), eng.ws.data_ptr(), eng.bws.data_ptr(),
                                                             pooled_f.data_ptr(), pooled_e.data_ptr(), raw_q.data_ptr(), w.data_ptr(), _lib.ptr(gq),
                                                             _lib.ptr(gw), float(ctx.drop[0]), int(ctx.drop[1]), float(2 ** 20), rows.data_ptr(),
-                                                            grads.data_ptr(), _lib.stream_ptr()), "lo_teacher_full_backward_ex")
-            _lib.check(_lib.lib.lo_grad_unscale_dev(grads.data_ptr(), grads.numel(), scr.data_ptr() + 4, None, _lib.stream_ptr()),
-                       "lo_grad_unscale_dev")
+                                                            grads.data_ptr(), _lib.ptr(dx), _lib.stream_ptr()), "lo_teacher_full_backward_dx")
+            for t in (grads, dx):
+                if t is not None:
+                    _lib.check(_lib.lib.lo_grad_unscale_dev(t.data_ptr(), t.numel(), scr.data_ptr() + 4, None, _lib.stream_ptr()),
+                               "lo_grad_unscale_dev")
         elif gq is not None or gw is not None:
             _lib.check(_lib.lib.lo_teacher_heads_backward_ex(eng.handle, model._flat.data_ptr(), pooled_f.data_ptr(), pooled_e.data_ptr(),
                                                              raw_q.data_ptr(), w.data_ptr(), _lib.ptr(gq), _lib.ptr(gw), float(ctx.drop[0]),
@@ -159,7 +166,9 @@ class _TeacherFunction(torch.autograd.Function):
             for d in shape:
                 n *= int(d)
             out.append(grads[o:o + n].view(shape))
-        return (None, None) + tuple(out)
+        if dx is not None and ctx.x_dtype != torch.float32:
+            dx = dx.to(ctx.x_dtype)
+        return (None, None, dx) + tuple(out)
 
 
 class LunarMoETeacher(nn.Module):
@@ -298,7 +307,10 @@ class LunarMoETeacher(nn.Module):
     def live_parameters(self):
         """The parameters that receive gradients in the reference step (gate.*, quality_heads.*: SURVEY §3.2), state_dict order; with
         ``LunarMoETeacher(full_backward=True)`` every parameter on the path of quality_scores / expert_weights (all but the style / prompt / semantic heads)."""
-        if self.all_parameters_live:
+        return self._live_parameters(False)
+
+    def _live_parameters(self, full: bool):
+        if self.all_parameters_live or full:
             return [p for k, p in self.named_parameters() if k.split(".")[0] not in ("semantic_head", "style_net", "prompt_net")]
         return [p for k, p in self.named_parameters() if k.startswith("gate.") or k.startswith("quality_heads.")]
 
@@ -410,12 +422,24 @@ class LunarMoETeacher(nn.Module):
     def forward(self, x: torch.Tensor, prompt_embedding=None):
         """lunar_evaluator.py:408-462.  ``prompt_embedding`` is accepted and ignored exactly like the reference does
         (it is overwritten at :438 before any use).  With gradients enabled, ``quality_scores`` / ``expert_weights`` carry a
-        graph over the gate / quality-head parameters (see `_TeacherFunction`)."""
+        graph over the gate / quality-head parameters (see `_TeacherFunction`).
+
+        An input that requires grad (the teacher as a differentiable reward: ``teacher(recon)`` with ``recon`` not detached) gets
+        ``x.grad`` in train mode.  There the reference's reentrant checkpoints see an input that requires grad and differentiate the
+        whole trunk, so this call takes the full backward whatever ``full_backward`` says: every parameter on the path of
+        ``quality_scores`` / ``expert_weights`` receives its gradient (the ones ``full_backward=True`` gives), through the kept forward
+        (its scratch is 26 GB at batch 64, feature_dim 128).  The BatchNorm running statistics move once per forward, as in the full
+        backward (nothing is recomputed); the reference's reentrant recompute would advance them a second time.  In eval mode an input
+        that requires grad gets no gradient (a UserWarning says so) and the outputs are those of the eval forward."""
         self._ensure_flat()
         if torch.is_grad_enabled():
-            live = [p for p in self.live_parameters() if p.requires_grad]
-            if live:
-                q, w, st, pr, sem = _TeacherFunction.apply(self, x.detach(), *live)
+            want_dx = bool(x.requires_grad) and self.training
+            if x.requires_grad and not self.training:
+                warnings.warn("LunarMoETeacher in eval mode: the input requires grad but gets no gradient (its input gradient is built "
+                              "for train mode only); outputs are the eval-mode forward's", UserWarning, stacklevel=2)
+            live = [p for p in self._live_parameters(want_dx) if p.requires_grad]
+            if live or want_dx:
+                q, w, st, pr, sem = _TeacherFunction.apply(self, want_dx, x if want_dx else x.detach(), *live)
                 return {"quality_scores": q, "expert_weights": w, "style_embedding": st, "prompt_embedding": pr,
                         "semantic_score": sem, "feature_maps": None}
         return self._native_forward(x)[0]

@@ -165,11 +165,11 @@ class Encoder(_OwnedByVAE, nn.Module):
     def forward(self, x: torch.Tensor):
         vae = _owner_of(self)
         vae._ensure_flat()
-        x = x.detach().contiguous().float()
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            # an input that requires grad gets x.grad (lo_vae_encoder_backward_dx), also with the parameters frozen
             mu, logvar, s0, s1, s2 = _EncoderFunction.apply(vae, x, *self.parameters())
         else:
-            mu, logvar, s0, s1, s2, _ = vae._native_encode(x)
+            mu, logvar, s0, s1, s2, _ = vae._native_encode(x.detach().contiguous().float())
         return mu, logvar, [s0, s1, s2]
 
 
@@ -248,9 +248,10 @@ class _EncoderFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, vae, x, *params):
-        mu, logvar, s0, s1, s2, eng = vae._native_encode(x)
-        ctx.vae, ctx.eng, ctx.nparam, ctx.gen = vae, eng, len(params), (eng.gen_enc, None)
-        ctx.save_for_backward(x)
+        xd = x.detach().contiguous().float()
+        mu, logvar, s0, s1, s2, eng = vae._native_encode(xd)
+        ctx.vae, ctx.eng, ctx.nparam, ctx.gen, ctx.x_dtype = vae, eng, len(params), (eng.gen_enc, None), x.dtype
+        ctx.save_for_backward(xd)
         return mu, logvar, s0, s1, s2
 
     @staticmethod
@@ -264,12 +265,19 @@ class _EncoderFunction(torch.autograd.Function):
         if all(t is None for t in ups):
             return (None, None) + tuple(flat_g[o:o + n].view(shape) for (o, n, shape) in vae._layout[:ctx.nparam])
         scr, (g_mu, g_lv, g0, g1, g2) = _normalise_upstream(ups)
-        _lib.check(_lib.lib.lo_vae_encoder_backward(eng.handle, x.data_ptr(), vae._flat.data_ptr(), eng.ws.data_ptr(), _lib.ptr(g_mu),
-                                                    _lib.ptr(g_lv), _lib.ptr(g0), _lib.ptr(g1), _lib.ptr(g2), 1.0,
-                                                    flat_g.data_ptr(), _lib.stream_ptr()), "lo_vae_encoder_backward")
+        dx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
+        _lib.check(_lib.lib.lo_vae_encoder_backward_dx(eng.handle, x.data_ptr(), vae._flat.data_ptr(), eng.ws.data_ptr(), _lib.ptr(g_mu),
+                                                       _lib.ptr(g_lv), _lib.ptr(g0), _lib.ptr(g1), _lib.ptr(g2), 1.0,
+                                                       flat_g.data_ptr(), _lib.ptr(dx), _lib.stream_ptr()), "lo_vae_encoder_backward_dx")
         _denormalise(flat_g, scr, eng)
+        _denormalise(dx, scr, eng)
         grads = tuple(flat_g[o:o + n].view(shape) for (o, n, shape) in vae._layout[:ctx.nparam])
-        return (None, None) + grads
+        return (None, _as_input_grad(dx, ctx.x_dtype)) + grads
+
+
+def _as_input_grad(dx: Optional[torch.Tensor], dtype: torch.dtype) -> Optional[torch.Tensor]:
+    """The images' gradient (fp32 from the kernel) in the dtype of the tensor the caller passed in."""
+    return dx if dx is None or dtype == torch.float32 else dx.to(dtype)
 
 
 class _DecoderFunction(torch.autograd.Function):
@@ -335,9 +343,10 @@ class _VAEFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, x, eps, *params):
-        recon, mu, logvar, eng = model._native_forward(x, eps, target=None)
-        ctx.model, ctx.eng, ctx.gen = model, eng, (eng.gen_enc, eng.gen_dec)
-        ctx.save_for_backward(x, recon)
+        xd = x.detach().contiguous().float()
+        recon, mu, logvar, eng = model._native_forward(xd, eps, target=None)
+        ctx.model, ctx.eng, ctx.gen, ctx.x_dtype = model, eng, (eng.gen_enc, eng.gen_dec), x.dtype
+        ctx.save_for_backward(xd, recon)
         return recon, mu, logvar
 
     @staticmethod
@@ -353,12 +362,14 @@ class _VAEFunction(torch.autograd.Function):
             return (None, None, None) + tuple(flat_g[o:o + n].view(shape) for (o, n, shape) in model._layout)
         # the upstream gradients may carry a foreign loss scale (torch.amp.GradScaler): normalised on the device, see _normalise_upstream
         scr, (g_recon, g_mu, g_logvar) = _normalise_upstream(ups)
-        _lib.check(_lib.lib.lo_vae_backward(eng.handle, x.data_ptr(), model._flat.data_ptr(), eng.ws.data_ptr(), recon.data_ptr(),
-                                            None, 0, _lib.ptr(g_recon), _lib.ptr(g_mu), _lib.ptr(g_logvar),
-                                            1.0, flat_g.data_ptr(), _lib.stream_ptr()), "lo_vae_backward")
+        dx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
+        _lib.check(_lib.lib.lo_vae_backward_dx(eng.handle, x.data_ptr(), model._flat.data_ptr(), eng.ws.data_ptr(), recon.data_ptr(),
+                                               None, 0, _lib.ptr(g_recon), _lib.ptr(g_mu), _lib.ptr(g_logvar),
+                                               1.0, flat_g.data_ptr(), _lib.ptr(dx), _lib.stream_ptr()), "lo_vae_backward_dx")
         _denormalise(flat_g, scr, eng)
+        _denormalise(dx, scr, eng)
         grads = tuple(flat_g[o:o + n].view(shape) for (o, n, shape) in model._layout)
-        return (None, None, None) + grads
+        return (None, _as_input_grad(dx, ctx.x_dtype), None) + grads
 
 
 class LunarisCoreVAE(nn.Module):
@@ -558,11 +569,13 @@ class LunarisCoreVAE(nn.Module):
         """(reconstruction, mu, logvar), lunar_generate.py:263-276.  ``eps`` optionally injects the N(0,1) noise of
         ``reparameterize`` (parity runs); by default it is drawn on the device."""
         self._ensure_flat()
-        x = x.detach().contiguous().float()
         if eps is None and self.next_eps is not None:
             eps, self.next_eps = self.next_eps, None
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            # an input that requires grad (train_hybrid.py:845) gets x.grad through the encoder (lo_vae_backward_dx), also with the
+            # parameters frozen
             return _VAEFunction.apply(self, x, eps, *self.parameters())
+        x = x.detach().contiguous().float()
         recon, mu, logvar, _ = self._native_forward(x, eps, None)
         return recon, mu, logvar
 
@@ -572,7 +585,12 @@ class LunarisCoreVAE(nn.Module):
         return mu + torch.randn_like(std) * std
 
     def decode(self, z: torch.Tensor) -> torch.Tensor:
-        """Decoder without skip connections (`self.decoder(z, skips=[])`, lunar_generate.py:290) on the native path."""
+        """Decoder without skip connections (`self.decoder(z, skips=[])`, lunar_generate.py:290) on the native path.  With ``z``
+        requiring grad (latent optimisation, ``teacher(vae.decode(z))``) it is the Decoder's autograd node without skips, so ``z.grad``
+        (and the decoder's parameter gradients) are filled."""
+        if torch.is_grad_enabled() and z.requires_grad:
+            self._ensure_flat()
+            return _DecoderFunction.apply(self, 0, z, *self.decoder.parameters())
         z = z.detach().contiguous().float()
         if z.dim() != 2 or z.shape[1] != self.latent_dim:
             raise ValueError("z must have shape [B, latent_dim]")

@@ -3,6 +3,7 @@
 
   python tools/op_bench.py --op conv|wgrad --kind 0 --B 64 --H 32 --Cin 128 --Cout 128 --iters 20
   python tools/op_bench.py --op attn --B 64 --H 8 --Cin 512        (SelfAttention2d forward on a [B, Cin, H, H] map)
+  python tools/op_bench.py --op imgdgrad --stride 2|1 --B 64       (images' data gradient: VAE encoder.down1.0 | teacher conv1)
 """
 import argparse
 import ctypes as C
@@ -25,6 +26,7 @@ def main():
     ap.add_argument("--Cout", type=int, default=128)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--stats", type=int, default=1)
+    ap.add_argument("--stride", type=int, default=2, help="--op imgdgrad: 2 = the VAE's first conv (64 channels), 1 = the teacher's conv1 (32)")
     a = ap.parse_args()
     lib = _lib.lib
     B, H, Cin, Cout, kind = a.B, a.H, a.Cin, a.Cout, a.kind
@@ -57,6 +59,36 @@ def main():
         byts = 4.0 * B * N * (2.0 * D + 3.0 * Cc)
         print(f"attn B={B} C={Cc} N={N}: {ms * 1e3:.1f} us/call (one q|k|v projection launch + fused attention)  {(fl_core + fl_proj) / ms / 1e9:.2f} TFLOP/s "
               f"= {(fl_core + fl_proj) / ms / 1e9 / 2500.0:.4f} of the dense fp16 MFMA peak;  {byts / ms / 1e6:.1f} GB/s of q/k/v/x/out traffic = {byts / ms / 1e6 / 8000.0:.4f} of HBM peak")
+        return
+    if a.op == "imgdgrad":
+        # lo_image_dgrad_op: dy fp16 NHWC -> dx fp32 NCHW [B,3,128,128].  Bytes = dy read once + dx written once; the calls rotate over
+        # buffer sets larger than the 256 MB last-level cache together, so every call reads dy from HBM
+        s_, co = a.stride, (64 if a.stride == 2 else 32)
+        ho = 128 // s_
+        byts = B * (ho * ho * co * 2 + 3 * 16384 * 4)
+        nset = max(2, -(-320 * 2 ** 20 // byts))
+        dys = [(torch.randn(B, ho, ho, co, device="cuda") * 0.1).half() for _ in range(nset)]
+        dxs = [torch.empty(B, 3, 128, 128, device="cuda") for _ in range(nset)]
+        w = torch.randn(co, 3, 3, 3, device="cuda") * 0.2
+        fl = 2.0 * B * ho * ho * co * 27
+        it = [0]
+
+        def run():
+            i = it[0] % nset
+            it[0] += 1
+            _lib.check(lib.lo_image_dgrad_op(dys[i].data_ptr(), co, s_, w.data_ptr(), B, 1.0, dxs[i].data_ptr(), st))
+        for _ in range(3):
+            run()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.iters):
+            run()
+        e1.record()
+        torch.cuda.synchronize()
+        ms = e0.elapsed_time(e1) / a.iters
+        print(f"imgdgrad stride={s_} Cout={co} B={B}: {ms * 1e3:.1f} us/call  {byts / ms / 1e9:.2f} TB/s over {byts / 1e6:.1f} MB "
+              f"(dy read + dx write) = {byts / ms / 1e9 / 8.0:.3f} of the 8 TB/s HBM peak;  {fl / ms / 1e9:.2f} TFLOP/s")
         return
     x = (torch.randn(B, H, H, Cin, device="cuda") * 0.5).half()
     if a.op == "conv":
