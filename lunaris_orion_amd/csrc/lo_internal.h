@@ -2,6 +2,14 @@
 #pragma once
 #include "lo_common.h"
 
+// the C ABI units (lo_api.hip, lo_vae_*.hip): the stream behind the void* of an entry point, and early return of an error code
+static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
+#define LO_TRY(call)            \
+  do {                          \
+    int _r = (call);            \
+    if (_r != LO_OK) return _r; \
+  } while (0)
+
 const char* lo_get_error();
 
 // lo_conv.hip

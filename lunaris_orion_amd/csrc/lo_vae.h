@@ -1,0 +1,181 @@
+// Private header of the native VAE step executor: one C call enqueues every kernel of LunarisCoreVAE.forward
+// (lunar_generate.py:263-276) or of its backward on the given HIP stream.
+//   lo_vae_plan.hip  workspace plan, create / destroy, queries
+//   lo_vae_opt.hip   operand refresh (packs, casts) and the pipelined optimizer step
+//   lo_vae_step.hip  forward, loss, backward
+#pragma once
+#include "lo_internal.h"
+#include "../../include/lunaris_hip.h"
+#include <stdio.h>
+#include <string.h>
+#include <stdlib.h>
+#include <vector>
+
+// workspace / flat parameter / flat gradient addressing: expect `ws`, `P`, `G` and `h` in scope
+#define WSP(T, off) reinterpret_cast<T*>(reinterpret_cast<unsigned char*>(ws) + (off))
+#define PRM(i) (P + h->p_off[(i)])
+#define GRD(i) (G + h->p_off[(i)])
+
+struct ConvLayer {           // conv + GroupNorm + Mish
+  int kind = 0;              // forward kind
+  int H = 0, W = 0, Cin = 0, Cout = 0;   // input spatial dims / channels
+  int Ho = 0, Wo = 0;        // output spatial dims
+  LoGeom gf{}, gd{};         // forward / data-gradient geometry
+  int p_w = 0, p_b = 0, p_gw = 0, p_gb = 0;   // parameter indices (state_dict order)
+  size_t o_wp_f = 0, o_wp_d = 0;   // workspace offsets: packed fp16 weights (fwd, dgrad)
+  size_t o_v = 0, o_a = 0;   // raw conv output, activation after GN+Mish(+...)
+  size_t o_part = 0, o_stats = 0;   // GN partial sums, saved stats
+  size_t o_P1 = 0, o_P2 = 0; // GN backward partial sums (kept until the fused finalize at the end of backward)
+  int np1 = 0;               // >0: P1 rows per sample written by the consumer's fused data-gradient epilogue
+  int MT = 0;
+  size_t o_dv = 0;           // gradient wrt the raw conv output (GroupNorm backward -> data / weight gradient); one per layer, so the
+                             // side-stream weight gradient of layer k never shares a buffer with what the main stream writes next
+  // fp8 operand mode (LO_VAE_FP8_FWD): e4m3 weights + per-row scales of the forward op, e4m3 copy of the activation o_a
+  bool f8 = false;           // this layer's forward conv runs on e4m3 operands
+  size_t o_wp8 = 0, o_wscale = 0, o_a8 = 0;   // o_a8 = 0: no consumer needs the copy
+  // GroupNorm + Mish fused into the forward conv's epilogue (LoGnFuse, lo_common.h): exchange lines, arrival counters, and how many
+  // launches have used them (the counters are monotonic: launch k leaves them at k * tiles per sample)
+  bool gnf = false; int gnf_mts = 0, gnf_nt = 0;
+  size_t o_xbuf = 0, o_xcnt = 0;
+  unsigned gnf_epoch = 0;
+  // GroupNorm-backward APPLY fused into the data-gradient epilogue of the layer that CONSUMES this layer's activation (LoGnBwdFuse):
+  // arrival counters [B][8], launches so far, and -- per backward -- whether o_dv / P2 were already produced that way
+  size_t o_bcnt = 0;
+  unsigned gba_epoch = 0;
+  bool dv_done = false; int np2 = 0;
+  hipEvent_t ev_ready = nullptr;   // dv_done: the event bound to the launch that wrote this layer's dv (null: none was bound)
+  // few-rows layers (the 8 x 8 stage): forward / data gradient as a K-split 128 x 128-tile GEMM into fp32 slabs + ONE fused
+  // (sample, group)-local pass (slab sum + bias + GroupNorm [+ Mish | backward]); 0 = the one-launch kernel
+  int sk_fwd = 0, sk_dgrad = 0;
+};
+
+struct LoVae {
+  int B = 0, L = 0;
+  // parameters
+  int nparam = 0;
+  std::vector<size_t> p_off, p_numel;
+  size_t flat_elems = 0;
+  // layers: encoder stage s: enc[s][0] = strided conv, enc[s][1] = res.conv1, enc[s][2] = res.conv2
+  ConvLayer enc[4][3];
+  ConvLayer dec[4];
+  size_t o_eout[4] = {};     // ResBlock outputs (stage outputs)
+  size_t o_skipin[3] = {};   // skip feature maps handed to Decoder.forward from outside (lo_vae_decode_skips), fp16 NHWC
+  // latent
+  LoGeom g_head{}, g_head_d{}, g_dfc{}, g_dfc_d{};
+  int head_split = 32, dfcd_split = 32;    // K splits of the two K = 32768 Linear GEMMs (8 / 16 / 32 / 64 measured in round 2: 32)
+  size_t o_wp_head = 0, o_wp_head_t = 0, o_wp_dfc = 0, o_wp_dfc_t = 0;
+  size_t o_xflat = 0, o_slab_head = 0, o_eps = 0, o_z = 0, o_klp = 0, o_mu = 0, o_lv = 0, o_yfc = 0, o_h0 = 0;
+  size_t o_msep = 0, o_losses = 0, o_coefs = 0;
+  // backward scratch
+  size_t o_G[6] = {}, o_skipg[3] = {}, o_P1 = 0, o_P2 = 0, o_wslab = 0, o_wslab_lin = 0, o_fcw_part = 0, o_lc_part = 0, o_dz = 0, o_dml = 0,
+         o_slab_dz = 0, o_gfc = 0;
+  size_t o_packjobs = 0;
+  std::vector<LoPackJob> packjobs_host;   // kept alive: source of the asynchronous table upload
+  int n_packjobs = 0, pack_blocks = 0;
+  int n_packjobs_enc = 0, pack_blocks_enc = 0;   // the early share of the table: encoder stages 1..3 (their jobs come first)
+  const void* packjobs_for_ws = nullptr;         // workspace / parameter pointers the uploaded job table was built for
+  const void* packjobs_for_params = nullptr;
+  size_t ws_bytes = 0;
+  int idx_fc_mu_w = 0, idx_fc_mu_b = 0, idx_fc_lv_w = 0, idx_fc_lv_b = 0, idx_dfc_w = 0, idx_dfc_b = 0, idx_final_w = 0, idx_final_b = 0;
+  bool forward_done = false, loss_done = false;
+  bool enc_done = false, dec_done = false;   // activations of an encoder / decoder forward are in the workspace (split module calls)
+  int dec_skips = 0;         // how many skip maps the last decoder forward added (3 inside lo_vae_forward)
+  // weight-gradient GEMMs run on a side stream, concurrently with the data-gradient / GroupNorm chain
+  hipStream_t side = nullptr;
+  hipEvent_t ev_dv[4] = {}, ev_join = nullptr, ev_pre = nullptr, ev_range = nullptr;
+  bool async_handover = false, range_pending = false;   // lo_vae_set_async_handover: phase 1 / 3 leave their range's completion as an event on the side stream
+  // Operand refresh on the side stream in five levels, one event each, recorded in this order (waiting for a level implies the
+  // lower ones): 1 packed convs of encoder stages 1..3; 2 encoder stage 4 (parameters + packs); 3 the encoder heads (fc_mu /
+  // fc_logvar: parameters + fp16 copy); 4 decoder.fc + decoder convs; 5 the transposed Linear copies only the backward reads
+  hipEvent_t ev_lvl[6] = {};
+  bool lvl_pending[6] = {};
+  // pipelined optimizer step: levels 2..5 (AdamW of 97 % of the parameters + their operand refresh) are ENQUEUED by the next
+  // forward once its first stage has run -- see lo_vae_optimizer_step
+  struct { bool pending = false; float* P; const float* G; float* M; float* V; void* ws; const float* norm; float lr, beta1, beta2, eps, wd; int step; } defer;
+  int n_packjobs_s4 = 0, pack_blocks_s4 = 0, n_packjobs8_s4 = 0, pack_blocks8_s4 = 0;   // job-table prefix up to and including encoder stage 4
+  int bwd_layer = 0;         // conv layers processed so far in the current backward (selects the dv buffer / events)
+  size_t o_skslab = 0;       // slabs of the split-K convolutions (one launch at a time on the caller's stream)
+  bool gn_local = true;      // LO_GN_LOCAL=0: never use the one-pass (sample, group)-local GroupNorm backward
+  int nevent = 0;            // hand-over events handed out so far (ev_dv[nevent & 3])
+  bool overlap = false;
+  float* norm_scratch = nullptr;   // lo_vae_set_gradnorm_scratch: where a single-call backward leaves the early part of the gradient norm
+  bool fuse_gnb = true;      // fuse the GroupNorm-backward reduction into the producing data-gradient epilogue
+  bool fuse_gnf = false;     // fuse GroupNorm + Mish of a conv output into that conv's epilogue (sample rendezvous between its workgroups)
+  bool fuse_gna = true;      // fuse the GroupNorm-backward APPLY pass into the data-gradient epilogue that already carries its reduction
+  size_t o_sync_fail = 0;    // one word: set by a workgroup whose rendezvous poll ran out (never, unless a launch was lost)
+  // rank-B Linear-layer weight gradients kept as their factors (lo_lowrank.hip): transposed, batch-padded factor copies
+  // dml^T [2L][Bp], xflat^T [32768][Bp], Gfc^T [32768][Bp], z^T [L][Bp] (one contiguous block), Gram scratch; fac_ready: a fused
+  // backward has left this step's factors and the Gram part of the gradient norm; fac_scale: 1 / loss scale of that backward
+  bool lin_factored = false, fac_ready = false;
+  bool lin_factored_dp = false;   // data parallel: phase 1 leaves the factors (no Linear weight gradients); the ranks all-gather them
+  int Bp = 0;
+  size_t o_fac_dmlT = 0, o_fac_xT = 0, o_fac_gfcT = 0, o_fac_zT = 0, o_gram = 0;
+  float fac_scale = 1.f;
+  int n_cu = 0;              // compute units of the device (partition) this plan was made on; 0 = no device: nothing that waits across workgroups is planned
+  const void* sync_for_ws = nullptr;
+  // fp8 operand mode of the forward convs (lo_vae_create_ex flag LO_VAE_FP8_FWD)
+  bool fp8_fwd = false;
+  size_t o_eout8[4] = {}, o_h08 = 0, o_packjobs8 = 0;
+  std::vector<LoPackF8Job> packjobs8_host;
+  int n_packjobs8 = 0, pack_blocks8 = 0;
+  int n_packjobs8_enc = 0, pack_blocks8_enc = 0;
+};
+
+// the 16 conv + GroupNorm + Mish layers in forward order: encoder stage 1 (strided conv, res.conv1, res.conv2) .. stage 4, then up1 .. up4
+template <typename H, typename F>
+static inline void for_each_layer(H* h, F&& fn) {   // H: LoVae or const LoVae
+  for (int s = 0; s < 4; ++s)
+    for (int k = 0; k < 3; ++k) fn(h->enc[s][k]);
+  for (int s = 0; s < 4; ++s) fn(h->dec[s]);
+}
+
+// ---- stream plumbing -------------------------------------------------------------------------------------------------------------
+// work with slack (weight gradients, optimizer tail, operand refresh) goes to the side stream, if there is one; per-launch profiling
+// keeps everything on one stream
+static inline bool vae_side_on(const LoVae* h) { return h->overlap && !g_lo_prof_on; }
+// what `behind` gets from here on runs after everything `ahead` holds now
+static inline int vae_order(hipStream_t behind, hipStream_t ahead, hipEvent_t e) {
+  LO_HIP(hipEventRecord(e, ahead));
+  LO_HIP(hipStreamWaitEvent(behind, e, 0));
+  return LO_OK;
+}
+static inline bool lo_event_marker() {   // LO_EVENT_MARKER=1: hipEventRecord behind the launch, as before round 3 (A/B: -0.5 %)
+  static const bool on = getenv("LO_EVENT_MARKER") != nullptr;
+  return on;
+}
+// Hand-over of a buffer to the side stream.  The event rides on the launch that writes the buffer (LO_LAUNCH_STOP, lo_common.h): a
+// hipEventRecord behind that launch costs the caller's stream 3.5-4.7 us per hand-over (a marker packet the next kernel waits
+// for), the kernel's own completion signal 0.9-1.3 us (tools/probe/ev_probe.hip).  Construct it right before the launcher whose LAST
+// launch writes the buffer and call finish() right after it; the armed event never outlives the object (error returns included).
+// Never two of them alive at once.
+struct LoHandover {
+  hipEvent_t ev = nullptr;                                                             // null: no side stream, nothing handed over
+  LoHandover(hipEvent_t e, bool on) { if (on) { ev = e; if (!lo_event_marker()) g_lo_stop_event = e; } }
+  LoHandover(LoVae* h, bool on) : LoHandover(on ? h->ev_dv[h->nevent & 3] : nullptr, on) { if (on) ++h->nevent; }   // next of the ring
+  ~LoHandover() { g_lo_stop_event = nullptr; }
+  int finish(hipStream_t st) {   // nobody consumed it (a launcher path without LO_LAUNCH_STOP, or LO_EVENT_MARKER): fall back to a marker
+    if (ev && (g_lo_stop_event || lo_event_marker())) {
+      g_lo_stop_event = nullptr;
+      LO_HIP(hipEventRecord(ev, st));
+    }
+    return LO_OK;
+  }
+};
+
+// Names the profiler records opened while it lives (per-call-site breakdowns of a LO_PROF_LAYERS run).  The records keep the
+// pointer: the text is interned.  Never two of them alive at once (the end of any one clears the tag).
+struct LoProfTag {
+  template <typename... A>
+  explicit LoProfTag(const char* fmt, A... a) {
+    if (!(g_lo_prof_on && g_lo_prof_layers)) return;
+    char text[64];
+    snprintf(text, sizeof(text), fmt, a...);
+    g_lo_prof_tag = lo_prof_intern(text);
+  }
+  void end() { g_lo_prof_tag = nullptr; }     // ahead of the scope's end: what is launched next keeps its own name
+  ~LoProfTag() { end(); }
+};
+
+// ---- across the units ------------------------------------------------------------------------------------------------------------
+int vae_flush_deferred(LoVae* h, hipStream_t after_main);    // lo_vae_opt.hip: enqueue a pipelined optimizer step's tail
+int vae_wait_level(LoVae* h, hipStream_t st, int lvl);       // lo_vae_opt.hip: `st` waits for operand-refresh level lvl
