@@ -1,5 +1,6 @@
 // C ABI (include/lunaris_hip.h): the single-op entry points.  The native VAE step executor is in lo_vae_*.hip.
 #include "lo_internal.h"
+#include "lo_conv.h"
 #include "../../include/lunaris_hip.h"
 #include <stdio.h>
 #include <string.h>
@@ -28,8 +29,9 @@ extern "C" int lo_conv_forward(int kind, int B, int H, int W, int Cin, int Cout,
                                void* stream) {
   LoGeom g;
   LO_TRY(lo_make_geom(&g, kind, B, H, W, Cin, Cout));
-  if (mt_out) *mt_out = lo_conv_mt(g);
-  return lo_conv_run(g, (const f16*)in, (const f16*)wp, bias, (const f16*)add_src, (f16*)out, gn_partial, nullptr, 1, S(stream));
+  const LoConvOp op{.in = (const f16*)in, .w = (const f16*)wp, .bias = bias, .add_src = (const f16*)add_src, .out = (f16*)out, .gn_partial = gn_partial};
+  if (mt_out) *mt_out = lo_conv_choose(g, lo_conv_use(op)).mts;
+  return lo_conv_run(g, op, S(stream));
 }
 // fp8 (e4m3) operand forms of the same op: see LO_VAE_FP8_FWD in the header
 extern "C" int lo_quantize_act_f8(const void* x16, void* x8, size_t n, void* stream) {
@@ -49,8 +51,11 @@ extern "C" int lo_conv_forward_f8(int kind, int B, int H, int W, int Cin, int Co
   LO_REQUIRE(in8 && wp8 && wscale && out, "lo_conv_forward_f8: null argument");
   LoGeom g;
   LO_TRY(lo_make_geom(&g, kind, B, H, W, Cin, Cout));
-  if (mt_out) *mt_out = lo_conv_mt_f8(g);
-  return lo_conv_run_f8(g, (const uint8_t*)in8, (const uint8_t*)wp8, wscale, bias, (const f16*)add_src, (f16*)out, gn_partial, S(stream));
+  const LoConvOp op{.bias = bias, .add_src = (const f16*)add_src, .out = (f16*)out, .gn_partial = gn_partial};
+  LoConvUse use = lo_conv_use(op);
+  use.f8 = true;
+  if (mt_out) *mt_out = lo_conv_choose(g, use).mts;
+  return lo_conv_run_f8(g, (const uint8_t*)in8, (const uint8_t*)wp8, wscale, op, S(stream));
 }
 // the teacher's 3x3 stride-1 convolution kernel (lo_conv3x3_pp) with its epilogue: bias, optional LeakyReLU(0.2), optional
 // BatchNorm partial sums [B * (H/16) * (W/16)][Cout][2]; operands fp16 (fp8 == 0: in / wp as for lo_conv_forward) or e4m3
@@ -68,7 +73,7 @@ extern "C" int lo_linear_splitk(int M, int K, int N, const void* x, const void* 
                                 int nsplit, float* out32, void* out16, void* stream) {
   LoGeom g;
   LO_TRY(lo_make_geom(&g, LO_LINEAR, M, 1, 1, K, N));
-  LO_TRY(lo_conv_run(g, (const f16*)x, (const f16*)wp, nullptr, nullptr, nullptr, nullptr, slab, nsplit, S(stream)));
+  LO_TRY(lo_conv_run(g, {.in = (const f16*)x, .w = (const f16*)wp, .slab = slab, .nsplit = nsplit}, S(stream)));
   return lo_splitk_reduce(slab, bias, out32, (f16*)out16, M, N, nsplit, S(stream));
 }
 extern "C" size_t lo_wgrad_slab_bytes_for(int kind, int B, int H, int W, int Cin, int Cout) {

@@ -11,7 +11,7 @@
 // Same unpadded XOR-swizzled LDS image as lo_igemm_nt (chunk ^= (row >> 1) & 7), same LDS-staged epilogue (bias,
 // residual add, GroupNorm partial sums).  Tap offsets come from LoGeom, so the data gradient (mirrored taps) is the
 // same kernel.
-#include "lo_internal.h"
+#include "lo_conv.h"
 #include <stdlib.h>
 
 __device__ __attribute__((aligned(256))) unsigned int lo_zero_page3[64];
@@ -43,7 +43,7 @@ struct Conv3Args {
 #ifdef LO_STAMPS
   unsigned long long* stamps;   // diagnostic build only (tools/conv3_stamp.cpp): [workgroup][wave][16] shader-clock stamps
 #endif
-  // fused GroupNorm-backward reduction (lo_conv3x3_pp only; same contract as IgemmArgs::gb_* in lo_conv.hip): the output is the
+  // fused GroupNorm-backward reduction (lo_conv3x3_pp only; same contract as IgemmArgs::gb_* in lo_igemm.hip): the output is the
   // gradient wrt the activation of a conv+GN+Mish layer whose raw conv output is gb_v; P1[n][tile][c] = (sum du, sum du*xhat)
   const f16* gb_v = nullptr;
   const float* gb_stats = nullptr;
@@ -603,84 +603,32 @@ __global__ __launch_bounds__(512) void lo_conv3x3_pp(Conv3Args a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// launcher
+// launcher (whether this kernel runs an op, and with which tile, is lo_conv_choose's decision: lo_conv_select.hip)
 // ---------------------------------------------------------------------------------------------
-// LO_HALO: 0 = never, 2 = default (the shapes where it measured faster than lo_igemm_nt), 3 = every shape it can tile (what the
-// forced parity test uses: small batches run on it too)
-static inline int conv3_mode() {
-  static const int m = getenv("LO_HALO") ? atoi(getenv("LO_HALO")) : 2;
-  return m;
-}
-// tile of the 8-wave ping-pong kernel that gives >= 256 workgroups at batch 64: 16x16 pixels x 128 channels, 8x16 x 128 when that
-// would leave CUs idle, 16x16 x 64 for 64 output channels
-static inline bool conv3_tile(const LoGeom& g, int* th, int* tw, int* bn) {
-  if (g.n_phase != 1 || g.T[0] != 9 || g.in_stride != 1 || g.out_stride != 1) return false;
-  if (g.Cin % 64 || g.Cout % 64 || g.Win % 16 || g.Hin % 16) return false;
-  const long t16 = (long)g.B * (g.Hin / 16) * (g.Win / 16);
-  if (g.Cout % 128 == 0 && t16 * (g.Cout / 128) >= 256) { *th = 16; *tw = 16; *bn = 128; }
-  else if (g.Cout % 128 == 0) { *th = 8; *tw = 16; *bn = 128; }
-  else if (g.Cout == 64) { *th = 16; *tw = 16; *bn = 64; }
-  else return false;
-  return (g.Cout >> 3) <= *bn;   // a GroupNorm group must fit inside the N tile
-}
-
-// tiles per image of the fused-tap kernel for this geometry, or 0 when the kernel does not apply / is not selected
-int lo_conv3_tiles_per_image(const LoGeom& g, bool need_bn) {
-  int th, tw, bn;
-  const int mode = conv3_mode();
-  if (mode == 0 || !conv3_tile(g, &th, &tw, &bn)) return 0;
-  if (mode == 2) {
-    // default: where it measured faster than lo_igemm_nt -- the 16x16-pixel x 128-channel workgroup on
-    // long grids (>= 4 tiles per CU: the teacher), and, for launches without the BatchNorm epilogue, any tile choice above that
-    // puts a workgroup on every CU (the VAE's 64 / 128 / 256-channel ResBlock convolutions at batch 64: 44 -> 36, 34 -> 28,
-    // 36 -> 33 us; +1.0 % on the step over three interleaved pairs)
-    const long tiles = (long)g.B * (g.Hin / th) * (g.Win / tw) * (g.Cout / bn);
-    const bool long_grid = th == 16 && bn == 128 && tiles >= 1024;
-    if (!(long_grid || (!need_bn && tiles >= 256))) return 0;
-  }
-  return (g.Hin / th) * (g.Win / tw);
-}
-
-// does the kernel lo_conv3_run would launch for g carry the fused GroupNorm-backward epilogue?  (it always does)
-bool lo_conv3_fuses_gnb(const LoGeom& g) { return lo_conv3_tiles_per_image(g, false) > 0; }
-
-// fused GroupNorm epilogue (LoGnFuse / LoGnBwdFuse::dv): tile rows per sample and n tiles per row of the launch
-bool lo_conv3_gn_fuse_tiles(const LoGeom& g, int* mts, int* nt) {
-  int th, tw, bn;
-  if (lo_conv3_tiles_per_image(g, false) <= 0 || !conv3_tile(g, &th, &tw, &bn)) return false;
-  *mts = (g.Hin / th) * (g.Win / tw);
-  *nt = g.Cout / bn;
-  return *mts * *nt <= LO_GNF_MAX_TILES;
-}
-
-int lo_conv3_run(const LoGeom& g, const f16* in, const f16* wp, const float* bias, const f16* add_src, f16* out,
-                 float* gn_partial, hipStream_t st, const LoConvExtra* ex, const LoGnBwdFuse* gb, const LoGnFuse* gf) {
-  int th, tw, bn;
-  LO_REQUIRE(conv3_tile(g, &th, &tw, &bn), "lo_conv3_run: geometry not supported by the fused-tap kernel");
-  if (gf) {
-    int mts = 0, nt = 0;
-    LO_REQUIRE(!add_src && !gb && !ex && lo_conv3_gn_fuse_tiles(g, &mts, &nt) && mts == gf->MTs && nt == gf->NT,
-               "lo_conv3_run: fused GroupNorm asked for a geometry / tile grid the kernel does not have");
-  }
-  Conv3Args a{in, wp, bias, add_src, out, gn_partial, ex ? ex->bn_partial : nullptr, ex ? ex->act : 0, nullptr, nullptr, 0, nullptr, g};
+int lo_conv3_run(const LoGeom& g, const LoConvOp& op, const LoConvChoice& c, hipStream_t st) {
+  const LoConvExtra* ex = op.ex;
+  const LoGnBwdFuse* gb = op.gb;
+  const int th = c.th, tw = c.tw, bn = c.bn;
+  LO_REQUIRE(c.kernel == LO_CK_CONV3_PP, "lo_conv3_run: geometry not supported by the fused-tap kernel");
+  Conv3Args a{op.in, op.w, op.bias, op.add_src, op.out, op.gn_partial, ex ? ex->bn_partial : nullptr, ex ? ex->act : 0, nullptr, nullptr, 0, nullptr, g};
   if (gb) {
     a.gb_v = gb->v; a.gb_stats = gb->stats; a.gb_gamma = gb->gamma; a.gb_beta = gb->beta; a.gb_P1 = gb->P1;
     a.gb_dv = gb->dv; a.gb_P2 = gb->P2; a.gb_counter = gb->counter; a.gb_target = gb->target; a.gb_fail = gb->fail;
     a.gb_keep_out = gb->keep_out ? 1 : 0;
     LO_REQUIRE(!gb->dv || (g.Cout >> 3) >= 8, "lo_conv3_run: fused GroupNorm-backward apply needs groups of at least 8 channels");
   }
-  if (gf) a.gf = *gf;
+  if (op.gf) a.gf = *op.gf;
 #ifdef LO_STAMPS
   a.stamps = g_lo_conv3_stamps;
 #endif
-  const int tiles = g.B * (g.Hin / th) * (g.Win / tw) * (g.Cout / bn);
+  const int tiles = c.grid;
   double flops = 2.0 * g.B * g.Hin * g.Win * (double)g.Cout * 9 * g.Cin;
   double bytes = 2.0 * ((double)g.B * g.Hin * g.Win * (g.Cin + g.Cout) + 9.0 * g.Cin * g.Cout);
   static char name[64];
   snprintf(name, sizeof(name), "lo_conv3x3_pp<%d,%dx%d>", bn, th, tw);
   // algorithmic bytes of the FUSED op, as in launch_igemm: the residual gradient it adds and the producing layer's raw conv output
   // that the fused GroupNorm-backward reduction reads, each the size of the output
-  if (add_src) bytes += 2.0 * g.B * g.Hin * g.Win * g.Cout;
+  if (op.add_src) bytes += 2.0 * g.B * g.Hin * g.Win * g.Cout;
   if (gb) bytes += 2.0 * g.B * g.Hin * g.Win * g.Cout;
   LoProfScope _p(lo_prof_intern(name), flops, bytes, st);
   if (th == 8) LO_LAUNCH_STOP((lo_conv3x3_pp<128, 8, LO_PP_PLAIN>), dim3(tiles), dim3(512), 0, st, a);
@@ -697,6 +645,7 @@ bool lo_conv3_pp_applies(const LoGeom& g) {
   return g.n_phase == 1 && g.T[0] == 9 && g.in_stride == 1 && g.out_stride == 1 && g.Cin % 64 == 0 && g.Cout % 128 == 0 &&
          g.Hin % 16 == 0 && g.Win % 16 == 0 && g.Hin >= 16 && g.Cin <= 128;
 }
+int lo_conv3_pp_rows(const LoGeom& g) { return g.B * (g.Hin / 16) * (g.Win / 16); }
 int lo_conv3_run_pp_xf(const LoGeom& g, const f16* in, const f16* xc, const f16* kx, int nlev, const f16* wp, const float* bias,
                        f16* out, hipStream_t st, const LoConvExtra* ex) {
   LO_REQUIRE(lo_conv3_pp_applies(g), "lo_conv3_run_pp_xf: geometry not supported");
@@ -705,7 +654,7 @@ int lo_conv3_run_pp_xf(const LoGeom& g, const f16* in, const f16* xc, const f16*
 #ifdef LO_STAMPS
   a.stamps = nullptr;
 #endif
-  const int tiles = g.B * (g.Hin / 16) * (g.Win / 16) * (g.Cout / 128);
+  const int tiles = lo_conv3_pp_rows(g) * (g.Cout / 128);
   double flops = 2.0 * g.B * g.Hin * g.Win * (double)g.Cout * 9 * g.Cin;
   double bytes = 2.0 * ((double)g.B * g.Hin * g.Win * (g.Cin + g.Cout) + 9.0 * g.Cin * g.Cout);
   LoProfScope _p(nlev ? "lo_conv3x3_pp (transform on load)" : "lo_conv3x3_pp", flops, bytes, st);
@@ -729,7 +678,7 @@ int lo_conv3_run_pp_f8(const LoGeom& g, const uint8_t* in8, const uint8_t* w8, c
 #ifdef LO_STAMPS
   a.stamps = nullptr;
 #endif
-  const int tiles = g.B * (g.Hin / 16) * (g.Win / 16) * (g.Cout / 128);
+  const int tiles = lo_conv3_pp_rows(g) * (g.Cout / 128);
   double flops = 2.0 * g.B * g.Hin * g.Win * (double)g.Cout * 9 * g.Cin;
   double bytes = (double)g.B * g.Hin * g.Win * (g.Cin + 2.0 * g.Cout) + 9.0 * g.Cin * g.Cout;
   LoProfScope _p("lo_conv3x3_pp<f8>", flops, bytes, st);
@@ -944,27 +893,11 @@ __global__ __launch_bounds__(512) void lo_convt4_patch_fwd_kernel(ConvT4PatchArg
   }
 }
 
-// ConvTranspose2d k4 s2 p1 forward geometry with 64 -> 32 or 128 -> 64 channels on a map of whole 16 x 16 tiles
-bool lo_convt4_patch_applies(const LoGeom& g) {
-  if (g.n_phase != 4 || g.in_stride != 1 || g.out_stride != 2) return false;
-  if (!((g.Cin == 64 && g.Cout == 32) || (g.Cin == 128 && g.Cout == 64))) return false;
-  for (int p = 0; p < 4; ++p) if (g.T[p] != 4) return false;
-  return g.Hin % 16 == 0 && g.Win % 16 == 0 && g.Hout == 2 * g.Hin && g.Wout == 2 * g.Win;
-}
-int lo_convt4_patch_tiles_per_image(const LoGeom& g) { return lo_convt4_patch_applies(g) ? (g.Hin / 16) * (g.Win / 16) : 0; }
-
-// Data gradient of the stride-2 3x3 convolution 64 -> 128 (lunar_generate.py:102): dy [B][32][32][128] -> dx [B][64][64][64] (+ add_src)
-bool lo_convs2d_patch_applies(const LoGeom& g) {
-  if (g.n_phase != 4 || g.in_stride != 1 || g.out_stride != 2 || g.Cin != 128 || g.Cout != 64) return false;
-  if (g.T[0] != 1 || g.T[1] != 2 || g.T[2] != 2 || g.T[3] != 4) return false;
-  for (int p = 0; p < 4; ++p)
-    for (int t = 0; t < g.T[p]; ++t) if (g.dy[p][t] < 0 || g.dy[p][t] > 1 || g.dx[p][t] < 0 || g.dx[p][t] > 1) return false;
-  return g.Hin % 16 == 0 && g.Win % 16 == 0 && g.Hout == 2 * g.Hin && g.Wout == 2 * g.Win;
-}
-int lo_convs2d_patch_run(const LoGeom& g, const f16* dy, const f16* wp, const f16* add_src, f16* dx, hipStream_t st) {
-  LO_REQUIRE(lo_convs2d_patch_applies(g), "lo_convs2d_patch_run: geometry not supported");
-  ConvT4PatchArgs a{dy, wp, nullptr, dx, nullptr, g, add_src};
-  const int tiles = g.B * (g.Hin / 16) * (g.Win / 16);
+int lo_convs2d_patch_run(const LoGeom& g, const LoConvOp& op, const LoConvChoice& c, hipStream_t st) {
+  LO_REQUIRE(c.kernel == LO_CK_CONVS2D_PATCH, "lo_convs2d_patch_run: geometry not supported");
+  const f16* add_src = op.add_src;
+  ConvT4PatchArgs a{op.in, op.w, nullptr, op.out, nullptr, g, add_src};
+  const int tiles = c.grid;
   double flops = 0;
   for (int p = 0; p < 4; ++p) flops += 2.0 * g.B * g.GH * g.GW * (double)g.Cout * g.T[p] * g.Cin;
   const double bytes = 2.0 * ((double)g.B * g.Hin * g.Win * g.Cin + (add_src ? 2.0 : 1.0) * (double)g.B * g.Hout * g.Wout * g.Cout + 9.0 * g.Cin * g.Cout);
@@ -974,10 +907,10 @@ int lo_convs2d_patch_run(const LoGeom& g, const f16* dy, const f16* wp, const f1
   return LO_OK;
 }
 
-int lo_convt4_patch_run(const LoGeom& g, const f16* in, const f16* wp, const float* bias, f16* out, float* gn_partial, hipStream_t st) {
-  LO_REQUIRE(lo_convt4_patch_applies(g), "lo_convt4_patch_run: geometry not supported");
-  ConvT4PatchArgs a{in, wp, bias, out, gn_partial, g, nullptr};
-  const int tiles = g.B * (g.Hin / 16) * (g.Win / 16);
+int lo_convt4_patch_run(const LoGeom& g, const LoConvOp& op, const LoConvChoice& c, hipStream_t st) {
+  LO_REQUIRE(c.kernel == LO_CK_CONVT4_PATCH, "lo_convt4_patch_run: geometry not supported");
+  ConvT4PatchArgs a{op.in, op.w, op.bias, op.out, op.gn_partial, g, nullptr};
+  const int tiles = c.grid;
   double flops = 0;
   for (int p = 0; p < 4; ++p) flops += 2.0 * g.B * g.GH * g.GW * (double)g.Cout * g.T[p] * g.Cin;
   const double bytes = 2.0 * ((double)g.B * g.Hin * g.Win * g.Cin + (double)g.B * g.Hout * g.Wout * g.Cout + 16.0 * g.Cin * g.Cout);

@@ -1,0 +1,18 @@
+// Device-side pieces shared by the LDS-DMA GEMM kernels (lo_igemm_nt, lo_wgrad_tn); each unit gets its own zero page.
+#pragma once
+#include "lo_common.h"
+
+// 16 zero bytes x 16: source of every LDS-DMA lane whose row is padding / out of range
+static __device__ __attribute__((aligned(256))) unsigned int lo_zero_page[64];
+
+#define LO_VMCNT(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
+
+// Workgroups are dealt round-robin over the 8 XCDs (each with a private 4 MiB L2).  Map the linear block id so that
+// every XCD works on ONE contiguous range of logical tile ids: tiles that re-read the same activations (the taps of a
+// pixel tile, the N tiles of an M tile) then hit in that XCD's L2 instead of the Infinity Cache.  Bijective for any
+// total (speed only, never correctness).
+__device__ __forceinline__ int lo_xcd_remap(int bid, int total) {
+  const int q = total >> 3, r = total & 7;
+  const int xcd = bid & 7, loc = bid >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+}

@@ -12,72 +12,6 @@ static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); 
 
 const char* lo_get_error();
 
-// lo_conv.hip
-int lo_pack_weight(const float* w, f16* wp, const LoGeom& g, hipStream_t st);
-int lo_pack_all(const LoPackJob* jobs_dev, int njobs, int nblocks, hipStream_t st, int block_base = 0);   // block_base: a sub-range of the table
-int lo_pack_blocks(const LoGeom& g);   // blocks of one job in the fused pack launch
-// Data-gradient epilogue that also runs the GroupNorm backward of the layer whose activation gradient it produces.  P1: the
-// reduction (per-tile, per-channel sum du / sum du*xhat).  dv != null: the APPLY pass too -- the workgroups of a sample exchange
-// their P1 rows (sc1 stores, arrival counter per (sample, n tile): lo_common.h lo_arrive_and_wait), form the group sums in the
-// order lo_gn_bwd_apply uses and write dv (+ P2 = per-tile sums of dv for the conv bias gradient) instead of the activation
-// gradient, which is then never stored.  lo_conv_gnb_apply_tiles: whether the kernel lo_conv_run picks supports it.
-struct LoGnBwdFuse {
-  const f16* v; const float* stats; const float* gamma; const float* beta; float* P1;
-  f16* dv = nullptr; float* P2 = nullptr; unsigned int* counter = nullptr; unsigned int target = 0; unsigned int* fail = nullptr;
-  bool keep_out = false;    // with dv: store the activation gradient too (somebody else reads it: the decoder's skip gradients)
-};
-bool lo_conv_gnb_apply_tiles(const LoGeom& gd, int* mts, int* nt);
-int lo_conv_splitk_plan(const LoGeom& g);     // K splits for the few-rows convolutions (128 x 128 split-K tiles + a fused slab pass), 0 = no
-// teacher epilogue: LeakyReLU(0.2), per-channel BN partial sums; out_pitch > 0: the output tensor has out_pitch channels per pixel
-// and this op writes its Cout channels starting at channel out_choff (writing straight into a concatenated tensor)
-struct LoConvExtra { int act; float* bn_partial; int out_pitch = 0; int out_choff = 0; };
-int lo_conv_run(const LoGeom& g, const f16* in, const f16* wp, const float* bias, const f16* add_src, f16* out,
-                float* gn_partial, float* slab, int nsplit, hipStream_t st, const LoGnBwdFuse* gb = nullptr,
-                const LoConvExtra* ex = nullptr, const LoGnFuse* gf = nullptr);
-// gf: GroupNorm + Mish of the output inside the epilogue (LoGnFuse, lo_common.h).  lo_conv_gn_fuse_tiles: whether the kernel
-// lo_conv_run picks for g supports it, and the tile grid per sample the caller must put into gf->MTs / gf->NT
-bool lo_conv_gn_fuse_tiles(const LoGeom& g, int* mts, int* nt);
-bool lo_conv3_gn_fuse_tiles(const LoGeom& g, int* mts, int* nt);
-// fp8 (e4m3) operand path of the forward convs
-struct LoPackF8Job { const f16* src; uint8_t* dst; float* scale; int K[LO_MAX_PHASE]; int wofs[LO_MAX_PHASE]; int Cout, n_phase, block0; };
-bool lo_conv_f8_applies(const LoGeom& g);
-int lo_conv_run_f8(const LoGeom& g, const uint8_t* in8, const uint8_t* w8, const float* wscale, const float* bias, const f16* add_src,
-                   f16* out, float* gn_partial, hipStream_t st);
-void lo_pack_f8_job(LoPackF8Job* j, const LoGeom& g, const f16* src, uint8_t* dst, float* scale, int block0);   // blocks: n_phase * Cout
-int lo_pack_f8_all(const LoPackF8Job* jobs_dev, int njobs, int nblocks, hipStream_t st, int block_base = 0);
-int lo_pack_f8_one(const LoGeom& g, const f16* wp, uint8_t* w8, float* wscale, hipStream_t st);
-int lo_quantize_f8(const f16* x, uint8_t* x8, size_t n, hipStream_t st);
-int lo_conv_tile_m(const LoGeom& g);
-int lo_conv_mt_f8(const LoGeom& g);   // the same for lo_conv_run_f8
-int lo_conv_mt(const LoGeom& g);   // GroupNorm partial rows per sample the conv epilogue writes for this geometry
-int lo_conv3_tiles_per_image(const LoGeom& g, bool need_bn = false);
-int lo_conv_bn_rows(const LoGeom& g);
-bool lo_conv3_pp_applies(const LoGeom& g);
-int lo_conv3_run_pp_xf(const LoGeom& g, const f16* in, const f16* xc, const f16* kx, int nlev, const f16* wp, const float* bias,
-                       f16* out, hipStream_t st, const LoConvExtra* ex);   // BatchNorm partial rows written by lo_conv_run(..., ex) for this geometry
-bool lo_conv3_pp_f8_applies(const LoGeom& g);
-int lo_conv3_run_pp_f8(const LoGeom& g, const uint8_t* in8, const uint8_t* w8, const float* wscale, const float* bias, f16* out,
-                       hipStream_t st, const LoConvExtra* ex);
-int lo_conv3_run(const LoGeom& g, const f16* in, const f16* wp, const float* bias, const f16* add_src, f16* out,
-                 float* gn_partial, hipStream_t st, const LoConvExtra* ex = nullptr, const LoGnBwdFuse* gb = nullptr,
-                 const LoGnFuse* gf = nullptr);
-bool lo_conv3_fuses_gnb(const LoGeom& g);
-bool lo_convt4_patch_applies(const LoGeom& g);   // patch-resident forward of the 64 -> 32 transposed convolution
-int lo_convt4_patch_tiles_per_image(const LoGeom& g);
-int lo_convt4_patch_run(const LoGeom& g, const f16* in, const f16* wp, const float* bias, f16* out, float* gn_partial, hipStream_t st);
-bool lo_convs2d_patch_applies(const LoGeom& g);   // the same kernel as the data gradient of the stride-2 conv 64 -> 128 (all four phases from one dy patch)
-int lo_convs2d_patch_run(const LoGeom& g, const f16* dy, const f16* wp, const f16* add_src, f16* dx, hipStream_t st);
-int lo_conv_gnb_rows(const LoGeom& g);   // P1 rows per sample written by lo_conv_run(g, ..., gb) (fused GroupNorm-backward epilogue)
-int lo_splitk_reduce(const float* slab, const float* bias, float* out32, f16* out16, int M, int N, int nsplit, hipStream_t st);
-int lo_wgrad_nsplit(const LoGeom& g);
-int lo_wgrad3_nsplit(const LoGeom& g);   // multi-tap 3x3 stride-1 weight-gradient kernel: pixel splits, 0 = does not apply
-int lo_wgrad3_run(const LoGeom& g, const f16* x, const f16* dy, float* slab, hipStream_t st, int* nsplit_out);
-int lo_wgrad2_nsplit(const LoGeom& g);   // multi-tap weight-gradient kernel of the stride-2 layers: position splits, 0 = does not apply
-int lo_wgrad2_run(const LoGeom& g, const f16* x, const f16* dy, float* slab, hipStream_t st, int* nsplit_out);
-int lo_wgrad_run(const LoGeom& g, const f16* x, const f16* dy, float* slab, float* grad, float scale, hipStream_t st);
-size_t lo_wgrad_slab_bytes(const LoGeom& g);
-size_t lo_packed_weight_elems(const LoGeom& g);
-
 // lo_norm.hip
 int lo_gn_nchunk(int HW, int C);
 int lo_gn_fwd(const f16* v, const float* partial, int MT, const float* gamma, const float* beta, const f16* other, f16* y,

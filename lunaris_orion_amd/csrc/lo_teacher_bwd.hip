@@ -15,6 +15,7 @@
 // positions of a loss of order 1/B underflows fp16 otherwise); parameter gradients are fp32, unscaled, written to their slots of
 // the teacher's flat gradient buffer (layout = the state table, like lo_teacher_heads_backward).
 #include "lo_teacher.h"
+#include "lo_conv.h"
 
 // out = a + b (+ dpool broadcast): fp16 tensors of n8 8-element chunks
 __global__ __launch_bounds__(256) void lo_tb_add_kernel(const f16* __restrict__ a, const f16* __restrict__ b, const float* __restrict__ dpool,
@@ -333,7 +334,7 @@ static int tb_fe_backward(TbCtx& c, const float* x, float* dx) {
     hipLaunchKernelGGL(lo_tb_wt_kernel, dim3((64 * 128 + 255) / 256), dim3(256), 0, st, TP(fe.fus_w), TB(f16, c.pl.o_wt), 64, 128, 192, 64 * b);
     LO_LAUNCH_CHECK("tb_wt");
     LoConvExtra exd{0, nullptr, 192, 64 * b};
-    LO_TAGGED("tb fusion dgrad", lo_conv_run(d64, dcf, TB(f16, c.pl.o_wt), nullptr, nullptr, TB(f16, c.pl.o_dcat), nullptr, nullptr, 1, st, nullptr, &exd));
+    LO_TAGGED("tb fusion dgrad", lo_conv_run(d64, {.in = dcf, .w = TB(f16, c.pl.o_wt), .out = TB(f16, c.pl.o_dcat), .ex = &exd}, st));
   }
   f16* dpw = TB(f16, c.pl.o_cat64);               // gradient wrt a pointwise conv's output [pix][64]
   f16* ddw = TB(f16, c.pl.o_d32a);                // gradient wrt a depthwise conv's output [pix][32]

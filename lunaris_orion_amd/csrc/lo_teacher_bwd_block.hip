@@ -4,6 +4,7 @@
 // Heavy contractions reuse the VAE path's kernels: lo_conv_run (3x3 data gradients as LO_CONV3_S1_DGRAD, 1x1 data gradients as
 // LO_LINEAR on transposed weights) and lo_wgrad_run (weight gradients).  Everything else is below: simple, HBM-bound passes.
 #include "lo_teacher.h"
+#include "lo_conv.h"
 
 // ---------------------------------------------------------------------------------------------
 // BatchNorm(train) backward, per channel over (N, H, W):   y = (r - mean) * rstd * gamma + beta,  r = LeakyReLU(conv) (or conv)
@@ -414,7 +415,7 @@ int tb_block_backward(TbCtx& c, int e, int l, const f16* xin, const f16* y, cons
                          dT, F, 0, F, 1, 1, LO_DS_BLOCK(e, l, 3), 0, 0, TG(k.conv2_b)));
   LO_TAGGED("tb conv2 wgrad", lo_wgrad_run(h->g3b, TB(f16, b.a2), dT, TB(float, c.pl.o_wslab), TG(k.conv2_w), c.inv_g, st));
   LO_TRYT(lo_pack_weight(TP(k.conv2_w), TB(f16, c.pl.o_wd), c.d1b, st));
-  LO_TAGGED("tb conv2 dgrad", lo_conv_run(c.d1b, dT, TB(f16, c.pl.o_wd), nullptr, nullptr, dU, nullptr, nullptr, 1, st));     // dU = d a2
+  LO_TAGGED("tb conv2 dgrad", lo_conv_run(c.d1b, {.in = dT, .w = TB(f16, c.pl.o_wd), .out = dU}, st));     // dU = d a2
   // proj_drop, proj (compact rows)
   hipLaunchKernelGGL(lo_tb_projdrop_bwd_kernel, dim3(64, B), dim3(256), 0, st, dU, TB(f16, c.pl.o_dprojc), TB(float, c.pl.o_part), F,
                      c.d.site(LO_DS_BLOCK(e, l, 2)), c.d.thr, c.d.inv_keep);
@@ -422,13 +423,13 @@ int tb_block_backward(TbCtx& c, int e, int l, const f16* xin, const f16* y, cons
   LO_TRYT(lo_colsum(TB(float, c.pl.o_part), TG(k.proj_b), B * 64, F, F, c.inv_g, st));
   LO_TAGGED("tb proj wgrad", lo_wgrad_run(h->gpc, TB(f16, b.attc), TB(f16, c.pl.o_dprojc), TB(float, c.pl.o_wslab), TG(k.proj_w), c.inv_g, st));
   LO_TRYT(lo_transpose_cast(TP(k.proj_w), TB(f16, c.pl.o_wt), F, F, st));
-  LO_TAGGED("tb proj dgrad", lo_conv_run(c.dpc, TB(f16, c.pl.o_dprojc), TB(f16, c.pl.o_wt), nullptr, nullptr, TB(f16, c.pl.o_dattc), nullptr, nullptr, 1, st));
+  LO_TAGGED("tb proj dgrad", lo_conv_run(c.dpc, {.in = TB(f16, c.pl.o_dprojc), .w = TB(f16, c.pl.o_wt), .out = TB(f16, c.pl.o_dattc)}, st));
   LO_TRYT(tb_attn_backward(c, e, l, TB(f16, b.qkv)));
   // qkv conv
   LO_TRYT(tb_colsum16(c, TB(f16, c.pl.o_dqkv), TG(k.qkv_b), px, 3 * F));
   LO_TAGGED("tb qkv wgrad", lo_wgrad_run(h->gqF, TB(f16, b.bnA), TB(f16, c.pl.o_dqkv), TB(float, c.pl.o_wslab), TG(k.qkv_w), c.inv_g, st));
   LO_TRYT(lo_transpose_cast(TP(k.qkv_w), TB(f16, c.pl.o_wt), 3 * F, F, st));
-  LO_TAGGED("tb qkv dgrad", lo_conv_run(c.dq, TB(f16, c.pl.o_dqkv), TB(f16, c.pl.o_wt), nullptr, nullptr, dU, nullptr, nullptr, 1, st));      // dU = d a1
+  LO_TAGGED("tb qkv dgrad", lo_conv_run(c.dq, {.in = TB(f16, c.pl.o_dqkv), .w = TB(f16, c.pl.o_wt), .out = dU}, st));      // dU = d a1
   // Dropout2d, BatchNorm1: dU -> dT = gradient wrt conv1's output
   LO_TRYT(tb_bn_backward(c, dU, F, 0, TB(f16, b.rawA), F, 0, TB(float, b.mrA), k.bn1, nullptr, nullptr, dT, F, 0, F, 1, 1,
                          LO_DS_BLOCK(e, l, 0), 0, 0, TG(k.conv1_b)));
@@ -437,15 +438,15 @@ int tb_block_backward(TbCtx& c, int e, int l, const f16* xin, const f16* y, cons
   LO_TAGGED("tb conv1 wgrad", lo_wgrad_run(g1, xin, dT, TB(float, c.pl.o_wslab), TG(k.conv1_w), c.inv_g, st));
   LO_TRYT(lo_pack_weight(TP(k.conv1_w), TB(f16, c.pl.o_wd), d1, st));
   if (!sc) {
-    LO_TAGGED("tb conv1 dgrad", lo_conv_run(d1, dT, TB(f16, c.pl.o_wd), nullptr, dS, dx_out, nullptr, nullptr, 1, st));    // + the identity branch
+    LO_TAGGED("tb conv1 dgrad", lo_conv_run(d1, {.in = dT, .w = TB(f16, c.pl.o_wd), .add_src = dS, .out = dx_out}, st));    // + the identity branch
   } else {
     // shortcut = BatchNorm(Conv1x1(x)): dS -> gradient wrt the shortcut conv's output (no activation), its parameters, then both data gradients
-    LO_TAGGED("tb conv1 dgrad", lo_conv_run(d1, dT, TB(f16, c.pl.o_wd), nullptr, nullptr, dU, nullptr, nullptr, 1, st));
+    LO_TAGGED("tb conv1 dgrad", lo_conv_run(d1, {.in = dT, .w = TB(f16, c.pl.o_wd), .out = dU}, st));
     LO_TRYT(tb_bn_backward(c, dS, F, 0, TB(f16, b.scraw), F, 0, TB(float, b.mrS), k.bn_sc, nullptr, nullptr, dT, F, 0, F, 0, 0, 0, 0, 0,
                            TG(k.sc_b)));
     LO_TAGGED("tb shortcut wgrad", lo_wgrad_run(h->gsc, xin, dT, TB(float, c.pl.o_wslab), TG(k.sc_w), c.inv_g, st));
     LO_TRYT(lo_transpose_cast(TP(k.sc_w), TB(f16, c.pl.o_wt), F, 128, st));
-    LO_TAGGED("tb shortcut dgrad", lo_conv_run(c.dsc, dT, TB(f16, c.pl.o_wt), nullptr, dU, dx_out, nullptr, nullptr, 1, st));
+    LO_TAGGED("tb shortcut dgrad", lo_conv_run(c.dsc, {.in = dT, .w = TB(f16, c.pl.o_wt), .add_src = dU, .out = dx_out}, st));
   }
   return LO_OK;
 }

@@ -4,6 +4,7 @@
 //   dense    (LO_T_DENSE=1) every convolution in full, the chunk-local attention with the reference's write-offset quirk
 //   dropout  (train mode, dropout_p > 0) both 3x3 convs in full (optionally e4m3), the attention still folded
 #include "lo_teacher.h"
+#include "lo_conv.h"
 
 // ---------------------------------------------------------------------------------------------
 // chunk-local attention with the reference's offset quirk (lunar_evaluator.py:203-216): one wave per written position.
@@ -420,7 +421,7 @@ static int t_attn_folded(const TFwd& c, int e, int l, const float* ss) {
     hipLaunchKernelGGL(lo_t_gather_q_kernel, dim3((B * 543 * 16 + 255) / 256), dim3(256), 0, st, TW(f16, h->o_rawA), ss, TW(f16, h->o_qin), B, DROP ? 256 : 0);
   }
   LO_LAUNCH_CHECK("t_gather_q");
-  LO_TAGGED("t_U (igemm)", lo_conv_run(h->gU, TW(f16, h->o_qin), TW(f16, h->o_wu[e][l]), TW(float, h->o_ub[e][l]), nullptr, TW(f16, h->o_U), nullptr, nullptr, 1, st));
+  LO_TAGGED("t_U (igemm)", lo_conv_run(h->gU, {.in = TW(f16, h->o_qin), .w = TW(f16, h->o_wu[e][l]), .bias = TW(float, h->o_ub[e][l]), .out = TW(f16, h->o_U)}, st));
   {
     LoProfScope _p("lo_t_attn_folded", 2.0 * B * 543 * 2 * 8 * 32 * 128, 2.0 * px * 128 + 2.0 * B * 543 * 2112, st);
     if (DROP)
@@ -431,18 +432,22 @@ static int t_attn_folded(const TFwd& c, int e, int l, const float* ss) {
                          0, LoDropSite{0u, 0u}, 0u, 1.0f);
   }
   LO_LAUNCH_CHECK("t_attn_folded");
-  LO_TAGGED("t_proj (igemm)", lo_conv_run(h->gZ, TW(f16, h->o_Z), TW(f16, h->o_wz[e][l]), TP(h->blk[e][l].proj_b), nullptr, TW(f16, h->o_projc), nullptr, nullptr, 1, st));
+  LO_TAGGED("t_proj (igemm)", lo_conv_run(h->gZ, {.in = TW(f16, h->o_Z), .w = TW(f16, h->o_wz[e][l]), .bias = TP(h->blk[e][l].proj_b), .out = TW(f16, h->o_projc)}, st));
   return LO_OK;
 }
 
-// one full-resolution 3x3 conv of the dropout path: e4m3 operands, the fused-tap kernel, or the igemm
-static int t_conv3_full(const TFwd& c, const char* tag, int e, int l, int which, const f16* in, const uint8_t* in8, const float* bias, f16* out) {
+// one full-resolution 3x3 conv of the dropout path: e4m3 operands, the fused-tap kernel, or the igemm; *rows: BatchNorm partial rows it wrote
+static int t_conv3_full(const TFwd& c, const char* tag, int e, int l, int which, const f16* in, const uint8_t* in8, const float* bias, f16* out, int* rows) {
   LoTeacher* h = c.h; void* ws = c.ws; hipStream_t st = c.st;
   LoConvExtra ex{1, TW(float, h->o_bnp)};
   const f16* w = TW(f16, h->o_wp3[e][l][which]);
+  const LoConvOp op{.in = in, .w = w, .bias = bias, .out = out, .ex = &ex};
+  const bool pp = c.f8 || lo_conv3_pp_applies(h->g3);
+  LoConvChoice ch;
+  *rows = lo_conv3_pp_rows(h->g3);
   if (c.f8) { LO_TAGGED(tag, lo_conv3_run_pp_f8(h->g3, in8, TW(uint8_t, h->o_w8[e][l][which]), TW(float, h->o_ws8[e][l][which]), bias, out, st, &ex)); }
-  else if (lo_conv3_pp_applies(h->g3)) { LO_TAGGED(tag, lo_conv3_run_pp_xf(h->g3, in, nullptr, nullptr, 0, w, bias, out, st, &ex)); }
-  else { LO_TAGGED(tag, lo_conv_run(h->g3, in, w, bias, nullptr, out, nullptr, nullptr, 1, st, nullptr, &ex)); }
+  else if (pp) { LO_TAGGED(tag, lo_conv3_run_pp_xf(h->g3, in, nullptr, nullptr, 0, w, bias, out, st, &ex)); }
+  else { LO_TAGGED(tag, lo_conv_run(h->g3, op, st, &ch)); *rows = ch.rows; }
   return LO_OK;
 }
 
@@ -455,9 +460,9 @@ int t_block_dropout(const TFwd& c, int e, int l) {
   const size_t px = (size_t)B * T_HW;
   float* bnp = TW(float, h->o_bnp);
   const bool f8 = c.f8;
-  const int rows3 = lo_conv3_pp_applies(h->g3) ? B * 64 : lo_conv_bn_rows(h->g3);
+  int rows3 = 0;
   LO_TRYT(t_conv3_full(c, f8 ? "t_conv1 (dense, dropout path, e4m3)" : "t_conv1 (dense, dropout path)", e, l, 0, t_x(c, l - 1), t_x8(c, l - 1), TP(k.conv1_b),
-                       TW(f16, h->o_rawA)));
+                       TW(f16, h->o_rawA), &rows3));
   LO_TRYT(t_bn_finalize(h, bnp, rows3, 128, k.bn1, P, ws, c.training, st));
   LO_TRYT(t_drop2d(h, ws, 128, c.d, LO_DS_BLOCK(e, l, 0), st));
   LO_TRYT(t_attn_folded<true>(c, e, l, TW(float, h->o_ssb)));
@@ -467,7 +472,7 @@ int t_block_dropout(const TFwd& c, int e, int l) {
                        c.d.site(LO_DS_BLOCK(e, l, 2)), c.d.thr, c.d.inv_keep, st));
   }
   LO_TRYT(t_conv3_full(c, f8 ? "t_conv2 (dense, dropout path, e4m3)" : "t_conv2 (dense, dropout path)", e, l, 1, TW(f16, h->o_proj),
-                       f8 ? TW(uint8_t, h->o_proj8) : nullptr, TP(k.conv2_b), TW(f16, h->o_rawB)));
+                       f8 ? TW(uint8_t, h->o_proj8) : nullptr, TP(k.conv2_b), TW(f16, h->o_rawB), &rows3));
   LO_TRYT(t_bn_finalize(h, bnp, rows3, 128, k.bn2, P, ws, c.training, st));
   LO_TRYT(t_drop2d(h, ws, 128, c.d, LO_DS_BLOCK(e, l, 3), st));
   // the last block's output feeds nothing but the global average pool: a statistics-only call skips its tail, a full call
@@ -489,15 +494,19 @@ int t_block_sparse(const TFwd& c, int e, int l) {
     LO_TAGGED(l ? "t_conv1 (fused tap, tail on load)" : "t_conv1 (fused tap)",
               lo_conv3_run_pp_xf(h->g3, TW(f16, h->o_feat), l ? TW(f16, h->o_xc[(l - 1) & 1]) : nullptr, TW(f16, h->o_kx[e]), l,
                                  TW(f16, h->o_wp3[e][l][0]), TP(k.conv1_b), TW(f16, h->o_rawA), st, &ex));
-    LO_TRYT(t_bn_finalize(h, bnp, B * 64, 128, k.bn1, P, ws, c.training, st));
+    LO_TRYT(t_bn_finalize(h, bnp, lo_conv3_pp_rows(h->g3), 128, k.bn1, P, ws, c.training, st));
   } else {
-    LO_TAGGED("t_conv1 (igemm)", lo_conv_run(h->g3, t_x(c, l - 1), TW(f16, h->o_wp3[e][l][0]), TP(k.conv1_b), nullptr, TW(f16, h->o_rawA), nullptr, nullptr, 1, st, nullptr, &ex));
-    LO_TRYT(t_bn_finalize(h, bnp, lo_conv_bn_rows(h->g3), 128, k.bn1, P, ws, c.training, st));
+    const LoConvOp c1{.in = t_x(c, l - 1), .w = TW(f16, h->o_wp3[e][l][0]), .bias = TP(k.conv1_b), .out = TW(f16, h->o_rawA), .ex = &ex};
+    LoConvChoice ch;
+    LO_TAGGED("t_conv1 (igemm)", lo_conv_run(h->g3, c1, st, &ch));
+    LO_TRYT(t_bn_finalize(h, bnp, ch.rows, 128, k.bn1, P, ws, c.training, st));
   }
   LO_TRYT(t_attn_folded<false>(c, e, l, TW(float, h->o_ss)));
-  LO_TAGGED("t_conv2c (igemm)", lo_conv_run(h->g3c, TW(f16, h->o_projc), TW(f16, h->o_wp3[e][l][1]), TP(k.conv2_b), nullptr, TW(f16, h->o_rawBc), nullptr, nullptr, 1, st, nullptr, &ex));
-  const int tm = lo_conv_tile_m(h->g3c);
-  LO_REQUIRE(tm == 64 || tm == 128, "teacher sparse path: unexpected conv tile height %d", tm);
+  const LoConvOp c2{.in = TW(f16, h->o_projc), .w = TW(f16, h->o_wp3[e][l][1]), .bias = TP(k.conv2_b), .out = TW(f16, h->o_rawBc), .ex = &ex};
+  LoConvChoice ch2;
+  LO_TAGGED("t_conv2c (igemm)", lo_conv_run(h->g3c, c2, st, &ch2));
+  const int tm = ch2.bm;     // the compact rows below are counted in lo_igemm_nt's M tiles
+  LO_REQUIRE(ch2.kernel == LO_CK_IGEMM && (tm == 64 || tm == 128), "teacher sparse path: unexpected conv kernel %d / tile height %d", ch2.kernel, tm);
   const float* cv = TW(float, h->o_cvec[e][l]);
   LO_TRYT(t_bn_finalize(h, bnp, B * 1024 / tm, 128, k.bn2, P, ws, c.training, st, 1024 / tm, 6 * 128 / tm, cv));
   if (!h->fuse_tail)
@@ -519,20 +528,21 @@ int t_block_dense(const TFwd& c, int e, int l) {
   const int B = h->B;
   float* bnp = TW(float, h->o_bnp);
   LoConvExtra ex{1, bnp};
-  const int mt3 = lo_conv_bn_rows(h->g3);   // BatchNorm partial rows of the conv epilogue (igemm: M tiles)
-  LO_TAGGED("t_conv1 (igemm)", lo_conv_run(h->g3, t_x(c, l - 1), TW(f16, h->o_wp3[e][l][0]), TP(k.conv1_b), nullptr, TW(f16, h->o_rawA), nullptr, nullptr, 1, st, nullptr, &ex));
-  LO_TRYT(t_bn_finalize(h, bnp, mt3, 128, k.bn1, P, ws, c.training, st));
+  const LoConvOp c1{.in = t_x(c, l - 1), .w = TW(f16, h->o_wp3[e][l][0]), .bias = TP(k.conv1_b), .out = TW(f16, h->o_rawA), .ex = &ex};
+  LoConvChoice ch;     // of the launch that just ran: BatchNorm partial rows of its epilogue (igemm: M tiles)
+  LO_TAGGED("t_conv1 (igemm)", lo_conv_run(h->g3, c1, st, &ch));
+  LO_TRYT(t_bn_finalize(h, bnp, ch.rows, 128, k.bn1, P, ws, c.training, st));
   LO_TRYT(t_bn_apply(h, TW(f16, h->o_rawA), nullptr, nullptr, TW(f16, h->o_bnA), 128, 128, 0, 0, nullptr, ws, st));
-  LO_TRYT(lo_conv_run(h->gq, TW(f16, h->o_bnA), TW(f16, h->o_wqkv[e][l]), TP(k.qkv_b), nullptr, TW(f16, h->o_qkv), nullptr, nullptr, 1, st));
+  LO_TRYT(lo_conv_run(h->gq, {.in = TW(f16, h->o_bnA), .w = TW(f16, h->o_wqkv[e][l]), .bias = TP(k.qkv_b), .out = TW(f16, h->o_qkv)}, st));
   {
     LoProfScope _p("lo_t_attn", 0, 0, st);
     int nw = B * 543;
     hipLaunchKernelGGL(lo_t_attn_kernel, dim3((nw + 3) / 4), dim3(256), 0, st, TW(f16, h->o_qkv), TW(f16, h->o_att), B);
   }
   LO_LAUNCH_CHECK("t_attn");
-  LO_TRYT(lo_conv_run(h->gp, TW(f16, h->o_att), TW(f16, h->o_wproj[e][l]), TP(k.proj_b), nullptr, TW(f16, h->o_proj), nullptr, nullptr, 1, st));
-  LO_TRYT(lo_conv_run(h->g3, TW(f16, h->o_proj), TW(f16, h->o_wp3[e][l][1]), TP(k.conv2_b), nullptr, TW(f16, h->o_rawB), nullptr, nullptr, 1, st, nullptr, &ex));
-  LO_TRYT(t_bn_finalize(h, bnp, mt3, 128, k.bn2, P, ws, c.training, st));
+  LO_TRYT(lo_conv_run(h->gp, {.in = TW(f16, h->o_att), .w = TW(f16, h->o_wproj[e][l]), .bias = TP(k.proj_b), .out = TW(f16, h->o_proj)}, st));
+  LO_TRYT(lo_conv_run(h->g3, {.in = TW(f16, h->o_proj), .w = TW(f16, h->o_wp3[e][l][1]), .bias = TP(k.conv2_b), .out = TW(f16, h->o_rawB), .ex = &ex}, st, &ch));
+  LO_TRYT(t_bn_finalize(h, bnp, ch.rows, 128, k.bn2, P, ws, c.training, st));
   return t_bn_apply(h, TW(f16, h->o_rawB), TP(k.layer_scale), t_x(c, l - 1), t_x(c, l), 128, 128, 0, 1, l == 2 ? TW(float, h->o_poolp) : nullptr, ws, st);
 }
 

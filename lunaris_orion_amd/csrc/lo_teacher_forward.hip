@@ -1,6 +1,7 @@
 // Teacher forward executor: the feature extractor forward and the plain ExpertBlock forward (both shared with the full-backward mode,
 // lo_teacher_bwd.hip), and lo_teacher_forward, which picks one of four block forms per call.
 #include "lo_teacher.h"
+#include "lo_conv.h"
 
 // feature extractor (lunar_evaluator.py:105-112) from the images x into the tensors of t
 int t_fe_forward(LoTeacher* h, const float* x, float* P, void* ws, int train, const LoDropCfg& d, bool fold, const TFeDst& t,
@@ -25,14 +26,16 @@ int t_fe_forward(LoTeacher* h, const float* x, float* P, void* ws, int train, co
     }
     // the pointwise conv writes its (LeakyReLU'd, not yet normalised) 64 channels straight into the concatenated tensor
     LoConvExtra exb{1, bnp, 192, 64 * b};
-    LO_TRYT(lo_conv_run(h->gpw, t.dw[b], TW(f16, h->o_wpw[b]), TP(br.pw_b), nullptr, t.cat, nullptr, nullptr, 1, st, nullptr, &exb));
-    const int mt = (int)(px / lo_conv_tile_m(h->gpw));
-    LO_TRYT(t_bn_finalize(h, bnp, mt, 64, br.bn, P, ws, train, st, 1, 1, nullptr, ss_cat + 128 * b, t.mr_br[b]));
+    const LoConvOp pw{.in = t.dw[b], .w = TW(f16, h->o_wpw[b]), .bias = TP(br.pw_b), .out = t.cat, .ex = &exb};
+    LoConvChoice ch;
+    LO_TRYT(lo_conv_run(h->gpw, pw, st, &ch));
+    LO_TRYT(t_bn_finalize(h, bnp, ch.rows, 64, br.bn, P, ws, train, st, 1, 1, nullptr, ss_cat + 128 * b, t.mr_br[b]));
   }
+  LoConvOp fus{.out = t.rawF, .ex = &ex};
   if (fold) {
     // the branch BatchNorms fold into the fusion conv (see lo_t_fold_fusion_kernel)
     LO_TRYT(t_fold_fusion(TP(fe.fus_w), TP(fe.fus_b), ss_cat, TW(f16, h->o_wfus_fold), TW(float, h->o_bfus_fold), st));
-    LO_TRYT(lo_conv_run(h->gfus, t.cat, TW(f16, h->o_wfus_fold), TW(float, h->o_bfus_fold), nullptr, t.rawF, nullptr, nullptr, 1, st, nullptr, &ex));
+    fus.in = t.cat; fus.w = TW(f16, h->o_wfus_fold); fus.bias = TW(float, h->o_bfus_fold);
   } else {
     // Dropout sits between the branch BatchNorms and the fusion conv (lunar_evaluator.py:108-111): normalise + drop, in place -- on a
     // copy where the raw tensor is kept
@@ -45,9 +48,11 @@ int t_fe_forward(LoTeacher* h, const float* x, float* P, void* ws, int train, co
       TOptScope _p(nm.cat_bn_drop, 0, 4.0 * px * 192, st);
       LO_TRYT(t_cat_bn_drop(catd, ss_cat, px * 24, d.site(LO_DS_FE), d.thr, d.inv_keep, st));
     }
-    LO_TRYT(lo_conv_run(h->gfus, catd, TW(f16, h->o_wfus), TP(fe.fus_b), nullptr, t.rawF, nullptr, nullptr, 1, st, nullptr, &ex));
+    fus.in = catd; fus.w = TW(f16, h->o_wfus); fus.bias = TP(fe.fus_b);
   }
-  LO_TRYT(t_bn_finalize(h, bnp, (int)(px / lo_conv_tile_m(h->gfus)), 128, fe.bn_fus, P, ws, train, st, 1, 1, nullptr, nullptr, t.mr_fus));
+  LoConvChoice ch;
+  LO_TRYT(lo_conv_run(h->gfus, fus, st, &ch));
+  LO_TRYT(t_bn_finalize(h, bnp, ch.rows, 128, fe.bn_fus, P, ws, train, st, 1, 1, nullptr, nullptr, t.mr_fus));
   return t_bn_apply(h, t.rawF, nullptr, nullptr, t.feat, 128, 128, 0, 0, t.pool_partial, ws, st, nullptr, false, t.feat8);
 }
 
@@ -63,28 +68,32 @@ int t_block_plain(LoTeacher* h, float* P, void* ws, int e, int l, const LoDropCf
   LoConvExtra ex{1, bnp};
   const LoGeom& g1 = l == 0 ? h->g3a : h->g3b;
   const bool sc = F != 128 && l == 0;
+  LoConvChoice ch;     // of the launch that just ran: its BatchNorm partial rows
   if (sc) {
     // shortcut = BatchNorm(Conv1x1(x)) (in_channels 128 != out_channels F): raw output + its (scale, shift), applied in the tail
     LoConvExtra exs{0, bnp};
-    LO_TAGGED(nm.shortcut, lo_conv_run(h->gsc, xin, TW(f16, h->o_wsc[e]), TP(k.sc_b), nullptr, t.scraw, nullptr, nullptr, 1, st, nullptr, &exs));
-    LO_TRYT(t_bn_finalize(h, bnp, lo_conv_bn_rows(h->gsc), F, k.bn_sc, P, ws, train, st, 1, 1, nullptr, t.ssS, t.mrS));
+    const LoConvOp op{.in = xin, .w = TW(f16, h->o_wsc[e]), .bias = TP(k.sc_b), .out = t.scraw, .ex = &exs};
+    LO_TAGGED(nm.shortcut, lo_conv_run(h->gsc, op, st, &ch));
+    LO_TRYT(t_bn_finalize(h, bnp, ch.rows, F, k.bn_sc, P, ws, train, st, 1, 1, nullptr, t.ssS, t.mrS));
   }
-  LO_TAGGED(nm.conv1, lo_conv_run(g1, xin, TW(f16, h->o_wp3[e][l][0]), TP(k.conv1_b), nullptr, t.rawA, nullptr, nullptr, 1, st, nullptr, &ex));
-  LO_TRYT(t_bn_finalize(h, bnp, lo_conv_bn_rows(g1), F, k.bn1, P, ws, train, st, 1, 1, nullptr, nullptr, t.mrA));
+  const LoConvOp c1{.in = xin, .w = TW(f16, h->o_wp3[e][l][0]), .bias = TP(k.conv1_b), .out = t.rawA, .ex = &ex};
+  LO_TAGGED(nm.conv1, lo_conv_run(g1, c1, st, &ch));
+  LO_TRYT(t_bn_finalize(h, bnp, ch.rows, F, k.bn1, P, ws, train, st, 1, 1, nullptr, nullptr, t.mrA));
   if (d.on) LO_TRYT(t_drop2d(h, ws, F, d, LO_DS_BLOCK(e, l, 0), st));
   LO_TRYT(t_bn_apply(h, t.rawA, nullptr, nullptr, t.bnA, F, F, 0, 0, nullptr, ws, st, nullptr, d.on));
-  LO_TAGGED(nm.qkv, lo_conv_run(h->gqF, t.bnA, TW(f16, h->o_wqkv[e][l]), TP(k.qkv_b), nullptr, t.qkv, nullptr, nullptr, 1, st));
+  LO_TAGGED(nm.qkv, lo_conv_run(h->gqF, {.in = t.bnA, .w = TW(f16, h->o_wqkv[e][l]), .bias = TP(k.qkv_b), .out = t.qkv}, st));
   {
     TOptScope _p(nm.attn, 0, 0, st);
     LO_TRYT(t_attn_generic(F, t.qkv, t.attc, B, d.site(LO_DS_BLOCK(e, l, 1)), d.thr, d.inv_keep, st));
   }
-  LO_TAGGED(nm.proj, lo_conv_run(h->gpc, t.attc, TW(f16, h->o_wproj[e][l]), TP(k.proj_b), nullptr, t.projc, nullptr, nullptr, 1, st));
+  LO_TAGGED(nm.proj, lo_conv_run(h->gpc, {.in = t.attc, .w = TW(f16, h->o_wproj[e][l]), .bias = TP(k.proj_b), .out = t.projc}, st));
   {
     TOptScope _p(nm.projdrop, 0, 2.0 * px * F, st);
     LO_TRYT(t_projdrop(F, t.projc, TP(k.proj_b), t.a2, nullptr, px * (F / 8), d.site(LO_DS_BLOCK(e, l, 2)), d.thr, d.inv_keep, st));
   }
-  LO_TAGGED(nm.conv2, lo_conv_run(h->g3b, t.a2, TW(f16, h->o_wp3[e][l][1]), TP(k.conv2_b), nullptr, t.rawB, nullptr, nullptr, 1, st, nullptr, &ex));
-  LO_TRYT(t_bn_finalize(h, bnp, lo_conv_bn_rows(h->g3b), F, k.bn2, P, ws, train, st, 1, 1, nullptr, nullptr, t.mrB));
+  const LoConvOp c2{.in = t.a2, .w = TW(f16, h->o_wp3[e][l][1]), .bias = TP(k.conv2_b), .out = t.rawB, .ex = &ex};
+  LO_TAGGED(nm.conv2, lo_conv_run(h->g3b, c2, st, &ch));
+  LO_TRYT(t_bn_finalize(h, bnp, ch.rows, F, k.bn2, P, ws, train, st, 1, 1, nullptr, nullptr, t.mrB));
   if (d.on) LO_TRYT(t_drop2d(h, ws, F, d, LO_DS_BLOCK(e, l, 3), st));
   // a block output that feeds nothing but the global average pool is only summed (xout null); a caller that wants neither skips the tail
   if (xout || pool_partial)

@@ -1,6 +1,7 @@
 // Teacher engine: state table in the reference's state_dict order, the parameter offsets resolved from its names, geometries and the
 // workspace plan, create / destroy, the state-table queries and the operand pack (lo_teacher.h).
 #include "lo_teacher.h"
+#include "lo_conv.h"
 #include <memory>
 #include <unordered_map>
 

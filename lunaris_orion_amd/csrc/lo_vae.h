@@ -5,6 +5,7 @@
 //   lo_vae_step.hip  forward, loss, backward
 #pragma once
 #include "lo_internal.h"
+#include "lo_conv.h"
 #include "../../include/lunaris_hip.h"
 #include <stdio.h>
 #include <string.h>

@@ -27,7 +27,14 @@ static int setup_conv_layer(ConvLayer& c, int kind, int B, int H, int W, int Cin
     LO_TRY(lo_make_geom(&c.gd, dk, B, c.Ho, c.Wo, Cout, Cin));
     c.o_wp_f = ar.take(lo_packed_weight_elems(c.gf) * 2);
     c.o_wp_d = ar.take(lo_packed_weight_elems(c.gd) * 2);
-    c.MT = lo_conv_mt(c.gf);
+    // conv_gn's fp16 launch (lo_vae_step.hip).
+    // TODO(fp8 mode, batch >= 64; owner: whoever next touches the fp8 forward -- before any other fp8 work): take c.MT and o_part
+    // from the use the layer really has.  A layer that plan_splitk_and_fp8 later moves to e4m3 operands runs lo_igemm_nt's tiles, and
+    // where lo_conv3x3_pp owns the fp16 form (the 128-channel ResBlock convs from batch 64 up, the 256-channel ones at batch 128)
+    // that launch writes {.f8 = true}.mts rows per sample, not these: it overruns o_part into o_stats / o_P1 of the same layer (both
+    // rewritten before they are read) and lo_gn_fwd misreads the row layout.  Kept as the parent had it here because the fix changes
+    // a workspace size and the fp8 results (profiles/conv_select_ab.md, disagreement 1).
+    c.MT = lo_conv_choose(c.gf, {.bias = true, .gn_partial = true}).mts;
   } else {
     c.Ho = H / 2; c.Wo = W / 2;
     c.MT = 64;
@@ -150,7 +157,7 @@ static void plan_backward_buffers(LoVae* h, Arena& ar) {
   h->o_wslab = ar.take(wslab);
   // The two Linear weight gradients run on the MAIN stream while the decoder's conv weight gradients may still be running on
   // the side stream: they get their own slab.  (Found by the buffer audit of round 2: at latent 512 / 256 both Linear
-  // gradients are written directly and never touch a slab, but at latent 64 / 128 lo_wgrad_nsplit() gives decoder.fc two
+  // gradients are written directly and never touch a slab, but at latent 64 / 128 lo_wgrad_choose() gives decoder.fc two
   // pixel splits, and sharing o_wslab with the side stream was a write-write race on those shapes.)
   size_t b = lo_wgrad_slab_bytes(h->g_head), b2 = lo_wgrad_slab_bytes(h->g_dfc);
   h->o_wslab_lin = ar.take(b > b2 ? b : b2);
@@ -189,7 +196,8 @@ static void plan_splitk_and_fp8(LoVae* h, Arena& ar) {
   h->o_skslab = ar.take(slab > 0 ? slab : 256);
   if (!h->fp8_fwd) return;
   auto enable = [&](ConvLayer& c, size_t* producer_copy) {
-    if (!lo_conv_f8_applies(c.gf) || lo_convt4_patch_applies(c.gf)) return;   // a patch-resident fp16 kernel owns the layer (and its partial-sum rows)
+    if (lo_conv_choose(c.gf, {.bias = true, .gn_partial = true, .f8 = true}).kernel == LO_CK_NONE) return;
+    if (lo_conv_choose(c.gf, {.bias = true, .gn_partial = true}).kernel == LO_CK_CONVT4_PATCH) return;   // a patch-resident fp16 kernel owns the layer (and its partial-sum rows)
     c.f8 = true;
     c.o_wp8 = ar.take(lo_packed_weight_elems(c.gf));
     c.o_wscale = ar.take((size_t)c.gf.n_phase * c.Cout * 4);
@@ -222,7 +230,7 @@ static void plan_gn_fusions(LoVae* h) {
   // round trips (publish, count, poll, read the lines: ~5 us on an otherwise idle CU), and the Mish of the tile (25 VALU operations
   // per element) runs on 2 waves per SIMD with nothing to overlap it, where the separate pass spreads the same arithmetic over
   // every wave slot of the chip.  Which layers qualify is a property of the kernel lo_conv_run picks for the
-  // geometry (lo_conv_gn_fuse_tiles); the fp8 operand mode keeps the separate pass (it also writes the e4m3 copy of the activation).
+  // geometry (LoConvChoice::gn_fuse); the fp8 operand mode keeps the separate pass (it also writes the e4m3 copy of the activation).
   h->fuse_gnf = getenv("LO_GN_FUSE") && atoi(getenv("LO_GN_FUSE")) != 0 && !h->fp8_fwd;
   // ... and the backward's apply pass in the data-gradient epilogue of the consuming layer (LO_GNB_APPLY_FUSE=0: separate
   // lo_gn_bwd_apply launches); needs the fused reduction.  Same mechanism, but here it WINS (+0.8 %: 21 002 / 21 021 against
@@ -236,9 +244,11 @@ static void plan_gn_fusions(LoVae* h) {
   int dev = 0, ncu = 0;
   if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) h->n_cu = ncu;
   else (void)hipGetLastError();
-  if (h->n_cu < 256) h->fuse_gnf = false;      // the forward fusion's two-round rule (lo_conv_gn_fuse_tiles) was only ever checked on 256 CUs
+  if (h->n_cu < 256) h->fuse_gnf = false;      // the forward fusion's two-round rule (LoConvChoice::gn_fuse) was only ever checked on 256 CUs
   for_each_layer(h, [&](ConvLayer& c) {
-    c.gnf = h->fuse_gnf && &c != &h->enc[0][0] && !c.sk_fwd && lo_conv_gn_fuse_tiles(c.gf, &c.gnf_mts, &c.gnf_nt);
+    if (!h->fuse_gnf || &c == &h->enc[0][0] || c.sk_fwd) return;
+    const LoConvChoice ch = lo_conv_choose(c.gf, {.bias = true, .gf = true});
+    c.gnf = ch.gn_fuse; c.gnf_mts = ch.mts; c.gnf_nt = ch.nt;
   });
 }
 

@@ -25,7 +25,7 @@ static int conv_gn(LoVae* h, ConvLayer& c, const f16* in, const f16* other, f16*
   // owns this geometry supports it; the separate lo_gn_fwd pass below is then not run.  Same statistics, same arithmetic, same bits.
   if (c.sk_fwd && !c.f8 && !o_y8) {
     // few output rows: K-split GEMM into fp32 slabs, then ONE (sample, group)-local pass: slab sum + bias -> v, statistics, GroupNorm + Mish
-    LO_TRY(lo_conv_run(c.gf, in, WSP(f16, c.o_wp_f), nullptr, nullptr, nullptr, nullptr, WSP(float, h->o_skslab), c.sk_fwd, st));
+    LO_TRY(lo_conv_run(c.gf, {.in = in, .w = WSP(f16, c.o_wp_f), .slab = WSP(float, h->o_skslab), .nsplit = c.sk_fwd}, st));
     tag.end();
     return lo_splitk_gn_fwd(WSP(float, h->o_skslab), c.sk_fwd, PRM(c.p_b), PRM(c.p_gw), PRM(c.p_gb), other, WSP(f16, c.o_v), y,
                             WSP(float, c.o_stats), h->B, c.Ho * c.Wo, c.Cout, mode, st);
@@ -43,11 +43,11 @@ static int conv_gn(LoVae* h, ConvLayer& c, const f16* in, const f16* other, f16*
   int r_;
   if (c.f8) {
     LO_REQUIRE(o_in8, "fp8 mode: no e4m3 copy of the input of a conv %d->%d", c.Cin, c.Cout);
-    r_ = lo_conv_run_f8(c.gf, WSP(uint8_t, o_in8), WSP(uint8_t, c.o_wp8), WSP(float, c.o_wscale), PRM(c.p_b), nullptr, WSP(f16, c.o_v),
-                        WSP(float, c.o_part), st);
+    r_ = lo_conv_run_f8(c.gf, WSP(uint8_t, o_in8), WSP(uint8_t, c.o_wp8), WSP(float, c.o_wscale),
+                        {.bias = PRM(c.p_b), .out = WSP(f16, c.o_v), .gn_partial = WSP(float, c.o_part)}, st);
   } else {
-    r_ = lo_conv_run(c.gf, in, WSP(f16, c.o_wp_f), PRM(c.p_b), nullptr, WSP(f16, c.o_v), fuse ? nullptr : WSP(float, c.o_part), nullptr, 1, st,
-                     nullptr, nullptr, fuse ? &gf : nullptr);
+    r_ = lo_conv_run(c.gf, {.in = in, .w = WSP(f16, c.o_wp_f), .bias = PRM(c.p_b), .out = WSP(f16, c.o_v),
+                            .gn_partial = fuse ? nullptr : WSP(float, c.o_part), .gf = fuse ? &gf : nullptr}, st);
   }
   tag.end();
   if (r_ != LO_OK) { if (fuse) --c.gnf_epoch; return r_; }
@@ -64,8 +64,7 @@ static int vae_decoder_forward(LoVae* h, const f16* const skips[3], const float*
   const int B = h->B;
   LO_TRY(vae_ensure_sync_init(h, ws, st));
   LO_TRY(vae_wait_level(h, st, 4));
-  LO_TRY(lo_conv_run(h->g_dfc, WSP(f16, h->o_z), WSP(f16, h->o_wp_dfc), PRM(h->idx_dfc_b), nullptr, WSP(f16, h->o_yfc), nullptr,
-                     nullptr, 1, st));
+  LO_TRY(lo_conv_run(h->g_dfc, {.in = WSP(f16, h->o_z), .w = WSP(f16, h->o_wp_dfc), .bias = PRM(h->idx_dfc_b), .out = WSP(f16, h->o_yfc)}, st));
   LO_TRY(lo_nchw_to_nhwc_f16(WSP(f16, h->o_yfc), WSP(f16, h->o_h0), B, 64, 512, st, h->o_h08 ? WSP(uint8_t, h->o_h08) : nullptr));
   const f16* cur = WSP(f16, h->o_h0);
   size_t cur8 = h->o_h08;
@@ -129,8 +128,7 @@ static int vae_encoder_forward(LoVae* h, const float* x, const float* eps, uint6
   // ---- heads + reparameterisation (lunar_generate.py:150-152, 259-261)
   LO_TRY(lo_nhwc_to_nchw_f16(cur, WSP(f16, h->o_xflat), B, 64, 512, st));
   LO_TRY(vae_wait_level(h, st, 3));
-  LO_TRY(lo_conv_run(h->g_head, WSP(f16, h->o_xflat), WSP(f16, h->o_wp_head), nullptr, nullptr, nullptr, nullptr,
-                     WSP(float, h->o_slab_head), h->head_split, st));
+  LO_TRY(lo_conv_run(h->g_head, {.in = WSP(f16, h->o_xflat), .w = WSP(f16, h->o_wp_head), .slab = WSP(float, h->o_slab_head), .nsplit = h->head_split}, st));
   LO_REQUIRE(h->p_off[h->idx_fc_lv_b] == h->p_off[h->idx_fc_mu_b] + (size_t)L, "flat layout: head biases not adjacent");
   LO_TRY(lo_head_reduce(WSP(float, h->o_slab_head), PRM(h->idx_fc_mu_b), eps, seed, WSP(float, h->o_mu), WSP(float, h->o_lv),
                         WSP(f16, h->o_z), WSP(float, h->o_eps), WSP(float, h->o_klp), B, L, h->head_split, st, mu, logvar));
@@ -320,7 +318,7 @@ int VaeBackward::layer(ConvLayer& c, const f16* dy, const f16* other, int mode, 
 int VaeBackward::dgrad_splitk(ConvLayer& c, int k, const f16* dv, f16* din, const f16* add_src, ConvLayer& prod, bool din_has_other_readers) {
   {
     LoProfTag tag("dgrad L%02d kind%d %dx%d %d->%d", k, c.kind, c.Ho, c.Wo, c.gd.Cin, c.gd.Cout);
-    LO_TRY(lo_conv_run(c.gd, dv, WSP(f16, c.o_wp_d), nullptr, nullptr, nullptr, nullptr, WSP(float, h->o_skslab), c.sk_dgrad, st));
+    LO_TRY(lo_conv_run(c.gd, {.in = dv, .w = WSP(f16, c.o_wp_d), .slab = WSP(float, h->o_skslab), .nsplit = c.sk_dgrad}, st));
   }
   LoHandover ho(h, side);       // the pass below writes prod's dv: its launch carries prod's hand-over event
   LO_TRY(lo_splitk_gn_bwd(WSP(float, h->o_skslab), c.sk_dgrad, add_src, WSP(f16, prod.o_v), WSP(float, prod.o_stats), PRM(prod.p_gw),
@@ -338,12 +336,14 @@ int VaeBackward::dgrad(ConvLayer& c, int k, const f16* dv, f16* din, const f16* 
   if (prod && h->fuse_gnb) {
     gb.v = WSP(f16, prod->o_v); gb.stats = WSP(float, prod->o_stats); gb.gamma = PRM(prod->p_gw); gb.beta = PRM(prod->p_gb);
     gb.P1 = WSP(float, prod->o_P1);
-    prod->np1 = lo_conv_gnb_rows(c.gd);
-    int mts = 0, nt = 0;
+    // the launch below, asked with the apply form: np1 rows of P1 per sample either way (the apply form does not change the kernel)
+    const LoConvChoice ch = lo_conv_choose(c.gd, {.add = add_src != nullptr, .gb = true, .gb_apply = true});
+    const int mts = ch.mts, nt = ch.nt;
+    prod->np1 = mts;
     // ... only where the whole grid is resident at once (one workgroup per CU): on the 64-channel 64 x 64 layers (1 024 tiles at
     // batch 64, two rounds of 512) the fused launch is 32-34 us longer than the 27 us pass it replaces, and the step is 0.6 %
     // faster without it there (22 309-22 332 against 22 185-22 202; nowhere: 22 238-22 316)
-    if (h->fuse_gna && lo_conv_gnb_apply_tiles(c.gd, &mts, &nt) && mts == prod->np1 && h->B * mts * nt <= h->n_cu) {
+    if (h->fuse_gna && ch.gnb_apply && h->B * mts * nt <= h->n_cu) {
       gb.dv = WSP(f16, prod->o_dv); gb.P2 = WSP(float, prod->o_P2);
       gb.counter = WSP(unsigned int, prod->o_bcnt);
       gb.target = (++prod->gba_epoch) * (unsigned)mts;
@@ -357,7 +357,7 @@ int VaeBackward::dgrad(ConvLayer& c, int k, const f16* dv, f16* din, const f16* 
   const bool writes_dv = gbp && gbp->dv;      // this launch writes prod's dv: it carries prod's event
   LoProfTag tag("dgrad L%02d kind%d %dx%d %d->%d", k, c.kind, c.Ho, c.Wo, c.gd.Cin, c.gd.Cout);
   LoHandover ho(h, side && writes_dv);
-  int r_ = lo_conv_run(c.gd, dv, WSP(f16, c.o_wp_d), nullptr, add_src, din, nullptr, nullptr, 1, st, gbp);
+  int r_ = lo_conv_run(c.gd, {.in = dv, .w = WSP(f16, c.o_wp_d), .add_src = add_src, .out = din, .gb = gbp}, st);
   if (r_ != LO_OK) { if (writes_dv) { --prod->gba_epoch; prod->dv_done = false; } return r_; }
   if (writes_dv) { LO_TRY(ho.finish(st)); prod->ev_ready = ho.ev; }
   return LO_OK;
@@ -401,8 +401,7 @@ int VaeBackward::decoder_chain(int fused, const float* recon, const float* targe
   LO_TRY(lo_colsum_f16(Gfc, GRD(h->idx_dfc_b), B, 32768, inv, gs));
   if (!fac)      // factored mode: dW = Gfc^T z is never formed (its factors are transposed with the encoder heads')
     LO_TRY(lo_wgrad_run(h->g_dfc, WSP(f16, h->o_z), Gfc, WSP(float, h->o_wslab_lin), GRD(h->idx_dfc_w), inv, gs));
-  LO_TRY(lo_conv_run(h->g_dfc_d, Gfc, WSP(f16, h->o_wp_dfc_t), nullptr, nullptr, nullptr, nullptr, WSP(float, h->o_slab_dz),
-                     h->dfcd_split, st));
+  LO_TRY(lo_conv_run(h->g_dfc_d, {.in = Gfc, .w = WSP(f16, h->o_wp_dfc_t), .slab = WSP(float, h->o_slab_dz), .nsplit = h->dfcd_split}, st));
   return lo_splitk_reduce(WSP(float, h->o_slab_dz), nullptr, dz32, WSP(f16, h->o_dz), B, L, h->dfcd_split, st);
 }
 
@@ -431,7 +430,7 @@ int VaeBackward::latent_and_heads(int fused, const float* gmu, const float* glv,
   } else {
     LO_TRY(lo_wgrad_run(h->g_head, WSP(f16, h->o_xflat), WSP(f16, h->o_dml), WSP(float, h->o_wslab_lin), GRD(h->idx_fc_mu_w), inv, gs));
   }
-  LO_TRY(lo_conv_run(h->g_head_d, WSP(f16, h->o_dml), WSP(f16, h->o_wp_head_t), nullptr, nullptr, Gb, nullptr, nullptr, 1, st));
+  LO_TRY(lo_conv_run(h->g_head_d, {.in = WSP(f16, h->o_dml), .w = WSP(f16, h->o_wp_head_t), .out = Gb}, st));
   LoHandover ho(h->ev_pre, beside && hand_to_side);
   LO_TRY(lo_nchw_to_nhwc_f16(Gb, Ga, B, 64, 512, st));                    // Ga = gradient wrt enc4 output, NHWC
   LO_TRY(ho.finish(st));

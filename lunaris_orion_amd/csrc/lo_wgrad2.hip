@@ -14,7 +14,7 @@
 //   8 waves, all on the same chunk: wave = (A-channel half, F-channel half, tap half); 3 LDS stages, 2 chunks in flight behind
 //   counted vmcnt (every wave issues exactly four 1-KB LDS-DMA instructions per chunk) + one barrier per chunk
 //   output: fp32 slab [split][packed weight layout of the forward geometry], summed by lo_wgrad_reduce_kernel (fixed order)
-#include "lo_internal.h"
+#include "lo_conv.h"
 #include <stdlib.h>
 
 __device__ __attribute__((aligned(256))) unsigned int lo_zero_page_w2[64];

@@ -13,7 +13,7 @@
 //   K loop: chunk = TH x TW pixels (2 x 16, or 4 x 8 for 8-pixel-wide maps), 4 LDS stages per group, 3 chunks in flight
 //   end: group 1 hands its accumulators to group 0 through LDS (fixed order), group 0 writes the fp32 slab
 //   output: fp32 slab [split][packed weight layout], summed in fixed order by lo_wgrad_reduce_kernel (reproducible)
-#include "lo_internal.h"
+#include "lo_conv.h"
 #include <stdlib.h>
 
 __device__ __attribute__((aligned(256))) unsigned int lo_zero_page_w3[64];

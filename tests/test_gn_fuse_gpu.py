@@ -1,4 +1,4 @@
-"""GroupNorm inside the convolution epilogues through a per-sample rendezvous (csrc/lo_common.h: LoGnFuse; lo_internal.h:
+"""GroupNorm inside the convolution epilogues through a per-sample rendezvous (csrc/lo_common.h: LoGnFuse; lo_conv.h:
 LoGnBwdFuse::dv -- the workgroups that hold one sample's tiles exchange their partial sums and wait for each other) against the
 separate passes: the forward form (LO_GN_FUSE=1, opt-in) against lo_gn_fwd, the backward apply (default) against lo_gn_bwd_apply.
 Same statistics, same arithmetic, so every output, every saved activation and every gradient of a training step must agree BIT FOR
@@ -92,7 +92,7 @@ def test_fused_groupnorm_epilogue_equals_the_separate_pass_bit_for_bit(tmp_path,
 
 @pytest.mark.parametrize("B,L", [(2, 256), (5, 256), (64, 512)])
 def test_fused_groupnorm_backward_apply_equals_the_separate_pass(tmp_path, B, L):
-    """The GroupNorm-backward APPLY inside the data-gradient epilogue of the consuming layer (lo_internal.h: LoGnBwdFuse::dv; 11 of
+    """The GroupNorm-backward APPLY inside the data-gradient epilogue of the consuming layer (lo_conv.h: LoGnBwdFuse::dv; 11 of
     the 16 layers) against the separate lo_gn_bwd_apply launches (LO_GNB_APPLY_FUSE=0): the same group sums in the same order and the
     same element arithmetic, so every dv -- hence every weight, GroupNorm and Linear gradient, every loss and every updated
     parameter of a second step -- is bitwise the same, EXCEPT the conv bias gradients of the fused layers: those are sums of dv whose

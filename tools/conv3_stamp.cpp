@@ -1,7 +1,7 @@
 // Diagnostic build of the fused-tap 3x3 kernel with in-kernel shader-clock stamps (tuning aid, not part of the library):
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DLO_STAMPS -x hip tools/conv3_stamp.cpp lunaris_orion_amd/csrc/lo_conv3.hip \
-//         lunaris_orion_amd/csrc/lo_conv.hip -x c++ lunaris_orion_amd/csrc/lo_util.cpp -o /tmp/conv3_stamp && /tmp/conv3_stamp
+//   tools/build_conv3_stamp.sh && tools/_bin/conv3_stamp 64 128 128      (B H C)
 #include "../lunaris_orion_amd/csrc/lo_internal.h"
+#include "../lunaris_orion_amd/csrc/lo_conv.h"
 #include <algorithm>
 #include <stdio.h>
 #include <stdlib.h>
@@ -27,11 +27,12 @@ int main(int argc, char** argv) {
   setenv("LO_HALO", "3", 1);
   g_lo_conv3_stamps = st;
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-  for (int i = 0; i < 3; ++i) lo_conv_run(g, x, w, bias, nullptr, o, nullptr, nullptr, 1, 0);
+  const LoConvOp op{.in = x, .w = w, .bias = bias, .out = o};
+  for (int i = 0; i < 3; ++i) lo_conv_run(g, op, 0);
   hipDeviceSynchronize();
   hipEventRecord(e0, 0);
   const int it = 10;
-  for (int i = 0; i < it; ++i) if (lo_conv_run(g, x, w, bias, nullptr, o, nullptr, nullptr, 1, 0)) { printf("run: %s\n", lo_get_error()); return 1; }
+  for (int i = 0; i < it; ++i) if (lo_conv_run(g, op, 0)) { printf("run: %s\n", lo_get_error()); return 1; }
   hipEventRecord(e1, 0); hipDeviceSynchronize();
   float ms; hipEventElapsedTime(&ms, e0, e1); ms /= it;
   double fl = 2.0 * nx * 9 * C;

@@ -1,6 +1,7 @@
 // Diagnostic build of the multi-tap weight-gradient kernel with in-kernel shader-clock stamps (tuning aid):
 //   tools/build_wgrad3_stamp.sh && /tmp/wgrad3_stamp 64 64 64      (B H C)
 #include "../lunaris_orion_amd/csrc/lo_internal.h"
+#include "../lunaris_orion_amd/csrc/lo_conv.h"
 #include <algorithm>
 #include <stdio.h>
 #include <stdlib.h>
