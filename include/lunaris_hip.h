@@ -68,6 +68,14 @@ int lo_conv_forward_f8(int kind, int B, int H, int W, int Cin, int Cout, const v
  * Cin <= 128.  bn_partial (may be NULL): [B*(H/16)*(W/16)][Cout][2] = (sum, sum of squares) of the stored values per pixel tile. */
 int lo_conv3x3_fused_tap_forward(int B, int H, int W, int Cin, int Cout, int fp8, const void* in, const void* wp, const float* wscale,
                                  const float* bias, int leaky_relu, void* out, float* bn_partial, void* stream);
+/* The 3x3 stride-1 convolution of the feature_dim 256 / 512 teacher (lunar_evaluator.py:242-243,249-250: Conv2d k3 p1 + LeakyReLU(0.2),
+ * and the per-channel sums its BatchNorm needs) on e4m3 operands, implicit-GEMM form: out = fp16(acc * wscale + bias), LeakyReLU on
+ * the rounded value when leaky_relu != 0.  in8 / wp8 / wscale as for lo_conv_forward_f8 (kind LO_KIND_CONV3_S1); Cin % 128 == 0,
+ * Cout % 64 == 0, H and W powers of two, B*H*W a whole number of M tiles.  bn_partial (may be NULL): [*rows_out][Cout][2] = (sum, sum
+ * of squares) of the stored values per M tile, fixed summation order; at most B*H*W/64 rows.  A shape that is not served returns
+ * a non-zero code (lo_last_error says why) and launches nothing. */
+int lo_teacher_conv3x3_forward_f8(int B, int H, int W, int Cin, int Cout, const void* in8, const void* wp8, const float* wscale,
+                                  const float* bias, int leaky_relu, void* out, float* bn_partial, int* rows_out, void* stream);
 /* Linear with split-K: y[M,N] (fp32 and/or fp16) = x[M,K] Wp[N,K]^T + bias.  slab: nsplit*M*N floats. */
 int lo_linear_splitk(int M, int K, int N, const void* x, const void* wp, const float* bias, float* slab, int nsplit,
                      float* out32, void* out16, void* stream);
@@ -282,9 +290,11 @@ int lo_vae_debug_tensor(const LoVae* h, int which, int s, int k, size_t* byte_of
 /* ---- LunarMoETeacher.forward as executed (lunar_evaluator.py:408-462; feature_dim 128) ---------------------------- */
 typedef struct LoTeacher LoTeacher;
 int lo_teacher_create(int batch, int num_experts, int feature_dim, int embedding_dim, LoTeacher** out);
-/* flags: LO_TEACHER_FP8_CONV = the 24 full-resolution 3x3 convolutions of the dropout path (train mode, dropout_p > 0) take OCP
- * e4m3 operands (v_mfma_scale_f32_16x16x128_f8f6f4; activations e4m3(8 x), one weight scale per output channel), fp16 outputs,
- * fp32 BatchNorm statistics; everything else unchanged (BASELINE config 5).  The default path and eval mode stay fp16. */
+/* flags: LO_TEACHER_FP8_CONV = the 24 full-resolution 3x3 convolutions take OCP e4m3 operands (v_mfma_scale_f32_16x16x128_f8f6f4;
+ * activations e4m3(8 x), one weight scale per output channel), fp16 outputs, fp32 BatchNorm statistics; everything else unchanged
+ * (BASELINE config 5).  feature_dim 128: on the dropout path (train mode, dropout_p > 0); the default path and eval mode stay fp16.
+ * feature_dim 256 / 512: in every train-mode lo_teacher_forward call (statistics-only and dropout_p == 0 included); eval mode,
+ * lo_teacher_forward_keep and the full backward stay fp16. */
 #define LO_TEACHER_FP8_CONV 1u
 int lo_teacher_create_ex(int batch, int num_experts, int feature_dim, int embedding_dim, unsigned flags, LoTeacher** out);
 void lo_teacher_destroy(LoTeacher* h);

@@ -39,6 +39,7 @@ SIGNATURES = {
     "lo_pack_weight_f8_for": (i32, [i32] * 6 + [vp, vp, f32p, vp]),
     "lo_conv_forward_f8": (i32, [i32] * 6 + [vp, vp, f32p, f32p, vp, vp, f32p, C.POINTER(C.c_int), vp]),
     "lo_conv3x3_fused_tap_forward": (i32, [i32] * 6 + [vp, vp, f32p, f32p, i32, vp, f32p, vp]),
+    "lo_teacher_conv3x3_forward_f8": (i32, [i32] * 5 + [vp, vp, f32p, f32p, i32, vp, f32p, C.POINTER(C.c_int), vp]),
     "lo_linear_splitk": (i32, [i32, i32, i32, vp, vp, f32p, f32p, i32, f32p, vp, vp]),
     "lo_wgrad_slab_bytes_for": (sz, [i32] * 6),
     "lo_conv_wgrad": (i32, [i32] * 6 + [vp, vp, f32p, f32p, flt, vp]),

@@ -69,6 +69,24 @@ extern "C" int lo_conv3x3_fused_tap_forward(int B, int H, int W, int Cin, int Co
   if (fp8) return lo_conv3_run_pp_f8(g, (const uint8_t*)in, (const uint8_t*)wp, wscale, bias, (f16*)out, S(stream), &ex);
   return lo_conv3_run_pp_xf(g, (const f16*)in, nullptr, nullptr, 0, (const f16*)wp, bias, (f16*)out, S(stream), &ex);
 }
+// the wide teacher's 3x3 stride-1 convolution (feature_dim 256 / 512: 128 -> F, F -> F) on e4m3 operands, implicit-GEMM form, with the
+// teacher epilogue; operands as for lo_conv_forward_f8.  rows_out: the BatchNorm partial rows the launch wrote
+extern "C" int lo_teacher_conv3x3_forward_f8(int B, int H, int W, int Cin, int Cout, const void* in8, const void* wp8, const float* wscale,
+                                             const float* bias, int leaky_relu, void* out, float* bn_partial, int* rows_out, void* stream) {
+  LO_REQUIRE(in8 && wp8 && wscale && out, "lo_teacher_conv3x3_forward_f8: null argument");
+  LoGeom g;
+  LO_TRY(lo_make_geom(&g, LO_CONV3_S1, B, H, W, Cin, Cout));
+  const LoConvExtra ex{leaky_relu ? 1 : 0, bn_partial};
+  const LoConvOp op{.bias = bias, .out = (f16*)out, .ex = &ex};
+  LoConvUse use = lo_conv_use(op);
+  use.f8 = true;
+  const LoConvChoice c = lo_conv_choose(g, use);
+  LO_REQUIRE(c.kernel == LO_CK_IGEMM_F8 && (B * H * W) % c.bm == 0,
+             "lo_teacher_conv3x3_forward_f8: %d -> %d channels on %d x %d x %d is not served on e4m3 operands (Cin %% 128, Cout %% 64, whole M tiles)",
+             Cin, Cout, B, H, W);
+  if (rows_out) *rows_out = c.rows;
+  return lo_conv_run_f8(g, (const uint8_t*)in8, (const uint8_t*)wp8, wscale, op, S(stream));
+}
 extern "C" int lo_linear_splitk(int M, int K, int N, const void* x, const void* wp, const float* bias, float* slab,
                                 int nsplit, float* out32, void* out16, void* stream) {
   LoGeom g;

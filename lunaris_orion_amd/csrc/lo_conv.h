@@ -89,8 +89,10 @@ LoConvChoice lo_conv_choose(const LoGeom& g, const LoConvUse& use);
 int lo_conv_splitk_plan(const LoGeom& g);     // K splits for the few-rows convolutions (128 x 128 split-K tiles + a fused slab pass), 0 = no
 int lo_conv_run(const LoGeom& g, const LoConvOp& op, hipStream_t st, LoConvChoice* chosen = nullptr);   // chosen: the choice it made
 // the same op with both operands in e4m3: in8 = fp8(activation * LO_F8_ACT_SCALE) in the fp16 tensor's layout, w8 / wscale from
-// lo_pack_f8_all; bias, add_src, out, gn_partial of `op` as in the fp16 form
-int lo_conv_run_f8(const LoGeom& g, const uint8_t* in8, const uint8_t* w8, const float* wscale, const LoConvOp& op, hipStream_t st);
+// lo_pack_f8_all; bias, add_src, out, gn_partial of `op` as in the fp16 form, and the teacher epilogue op.ex (activation, BatchNorm
+// partial rows; no concatenated output).  chosen: the choice it made (the rows the launch wrote)
+int lo_conv_run_f8(const LoGeom& g, const uint8_t* in8, const uint8_t* w8, const float* wscale, const LoConvOp& op, hipStream_t st,
+                   LoConvChoice* chosen = nullptr);
 
 // ---- lo_igemm.hip -----------------------------------------------------------------------------------------------------------
 int lo_igemm_run(const LoGeom& g, const LoConvOp& op, const LoConvChoice& c, hipStream_t st);

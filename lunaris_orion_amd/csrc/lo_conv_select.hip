@@ -115,6 +115,10 @@ static void choose_igemm_tile(LoConvChoice& c, const LoGeom& g, int n_z) {   // 
 // e4m3 operands: every shape the e4m3 K step fits, also where a fused-tap fp16 kernel owns the fp16 form (conv by conv the e4m3 implicit
 // GEMM is the faster launch there too: profiles/r04_fp8_per_layer.txt; on the step +0.5 %).  LO_F8_FORCE=0: the round-2 selection (those
 // shapes stay fp16).  Always lo_igemm_nt's tiles, whatever fp16 kernel owns the geometry.
+// The wide teacher's 3x3 convs at 128 x 128 (feature_dim 256 / 512, teacher epilogue: use.ex) were measured against the fp16 launch
+// that owns each geometry (lo_conv3x3_pp), batch 8, three interleaved pairs, e4m3 ahead in every pair -- 128 -> 256: 68-77 us against
+// 95-103; 256 -> 256: 97-101 against 154-158; 128 -> 512: 118-122 against 170-176; 512 -> 512: 313-316 against 535-538
+// (profiles/teacher_fp8_wide_ab.md) -- so none of them is routed back to fp16 here; LoTeacher::fp8a / fp8b follow this answer.
 static LoConvChoice choose_f8(const LoGeom& g) {
   static const bool force = !(getenv("LO_F8_FORCE") && atoi(getenv("LO_F8_FORCE")) == 0);
   LoConvChoice c{};
@@ -209,11 +213,14 @@ int lo_conv_run(const LoGeom& g, const LoConvOp& op, hipStream_t st, LoConvChoic
   return LO_ERR_ARG;
 }
 
-int lo_conv_run_f8(const LoGeom& g, const uint8_t* in8, const uint8_t* w8, const float* wscale, const LoConvOp& op, hipStream_t st) {
-  LO_REQUIRE(!op.gb && !op.ex && !op.gf && !op.slab && op.nsplit <= 1, "lo_conv_run_f8: the e4m3 path has bias, residual add and GroupNorm partials only");
+int lo_conv_run_f8(const LoGeom& g, const uint8_t* in8, const uint8_t* w8, const float* wscale, const LoConvOp& op, hipStream_t st,
+                   LoConvChoice* chosen) {
+  LO_REQUIRE(!op.gb && !op.gf && !op.slab && op.nsplit <= 1 && !(op.ex && op.ex->out_pitch > 0),
+             "lo_conv_run_f8: the e4m3 path has bias, residual add, GroupNorm partials and the teacher epilogue (activation, BatchNorm partials) only");
   LoConvUse u = lo_conv_use(op);
   u.f8 = true;
   const LoConvChoice c = lo_conv_choose(g, u);
+  if (chosen) *chosen = c;
   LO_REQUIRE(c.kernel == LO_CK_IGEMM_F8, "lo_conv_run_f8: geometry not supported (Cin %% 128, Cout %% 64)");
   return lo_igemm_run_f8(g, in8, w8, wscale, op, c, st);
 }

@@ -85,6 +85,8 @@ __global__ __launch_bounds__(256) void lo_igemm_nt(IgemmArgs a) {
   constexpr int WM = BM / 2, WN = BN / 2; // wave tile (2 x 2 waves)
   constexpr int MI = WM / 16, NI = WN / 16;
   constexpr int OPITCH = BN * 2 + 16;     // epilogue staging pitch (bytes)
+  // the epilogue's reduction scratch `red` ([256][16] floats behind the staging tile) lies inside the allocation whatever the ring size
+  static_assert(BM * OPITCH + 16384 <= igemm_lds_bytes<BM, BN, BK, NSTAGE, F8>(), "epilogue scratch outside the LDS allocation");
   // dynamic LDS (igemm_lds_bytes<...>() bytes, passed by the launcher): the deep-pipeline instantiations exceed the 64 KB a static
   // array may have; it is the kernel's only LDS object, so it starts at offset 0 (1 KB-aligned DMA destinations)
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
@@ -690,6 +692,7 @@ int lo_igemm_run_f8(const LoGeom& g, const uint8_t* in8, const uint8_t* w8, cons
   memset(&a, 0, sizeof(a));       // (a.gf.y = null: no fused GroupNorm on the fp8 path)
   a.in = reinterpret_cast<const f16*>(in8); a.w = reinterpret_cast<const f16*>(w8); a.f8_scale = wscale;
   a.bias = op.bias; a.add_src = op.add_src; a.out = op.out; a.gn_partial = op.gn_partial;
+  if (op.ex) { a.act = op.ex->act; a.bn_partial = op.ex->bn_partial; }   // teacher epilogue; the pitched output is not taken (lo_conv_run_f8)
   a.g = g;
   a.M = g.B * g.GH * g.GW;
   a.nsplit = 1;

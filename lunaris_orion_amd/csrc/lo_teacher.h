@@ -100,8 +100,10 @@ struct LoTeacher {
   size_t o_xc[2] = {}, o_kx[8] = {};   // compact rows of x_l (ping-pong), transform constants [3][6][128] fp16 per expert (contiguous)
   size_t o_xc3 = 0, o_poolpe = 0;      // compact rows of x_3 of every expert [E][B][1024][128]; pool partials [E][B][64][128]
   size_t o_ssb = 0;           // per-sample (scale, shift) of a BatchNorm followed by Dropout2d: [B][128][2]
-  // fp8 mode (LO_TEACHER_FP8_CONV; dropout path only): e4m3 weights + row scales of the 24 3x3 convs, e4m3 activations
-  bool fp8 = false;
+  // fp8 mode (LO_TEACHER_FP8_CONV): e4m3 weights + row scales of the 24 3x3 convs, e4m3 activations.  feature_dim 128: the dropout
+  // path only; 256 / 512: every train-mode lo_teacher_forward, per geometry (fp8a: the 128 -> F conv1 of a first block, fp8b: the F -> F
+  // convs), each where lo_conv_choose serves the teacher epilogue on e4m3 operands; fp8 = either
+  bool fp8 = false, fp8a = false, fp8b = false;
   size_t o_w8[8][3][2] = {}, o_ws8[8][3][2] = {}, o_feat8 = 0, o_x8[2] = {}, o_proj8 = 0;
   size_t ws_bytes = 0;
   bool att_zeroed = false;
@@ -152,13 +154,17 @@ int t_fe_forward(LoTeacher* h, const float* x, float* P, void* ws, int train, co
 struct TBlkT { f16 *rawA, *bnA, *qkv, *attc, *projc, *a2, *rawB, *scraw; float *mrA, *mrB, *mrS, *ssS; };
 struct TBlkNames { const char *shortcut, *conv1, *qkv, *proj, *conv2;    // LO_TAGGED tags of the five convolutions
                    const char *attn, *projdrop; };                      // LoProfScope names
+// e4m3 operands of the block's two 3x3 convs (fp8 mode of the wide teacher), each conv on its own: xin8 = the e4m3 copy of xin and
+// w8[0] / ws8[0] conv1's weights (null: conv1 stays fp16); a28 = where proj_drop writes conv2's input as e4m3 INSTEAD of t.a2 and
+// w8[1] / ws8[1] conv2's weights (null: fp16); xout8: the tail also emits the e4m3 copy of xout (null: not wanted)
+struct TBlk8 { const uint8_t* xin8; uint8_t* a28; uint8_t* xout8; const uint8_t* w8[2]; const float* ws8[2]; };
 // ExpertBlock (e, l) in plain form from xin into the tensor set t; xout = the block output (null: not wanted), pool_partial: its
 // per-sample column sums (null: not wanted); both null skips the tail.  train: 1 the step's forward (running statistics move), 2 a
 // recomputation (they do not), 0 eval
 int t_block_plain(LoTeacher* h, float* P, void* ws, int e, int l, const LoDropCfg& d, const TBlkT& t, const f16* xin, f16* xout, int train,
-                  float* pool_partial, const TBlkNames& nm, hipStream_t st);
+                  float* pool_partial, const TBlkNames& nm, hipStream_t st, const TBlk8* f8 = nullptr);
 
-// one lo_teacher_forward call, as the feature_dim-128 block forms see it
+// one lo_teacher_forward call, as the block forms see it
 struct TFwd { LoTeacher* h; float* P; void* ws; hipStream_t st; int training; LoDropCfg d; bool stats_only, f8; };
 
 // ---- lo_teacher_f128.hip ------------------------------------------------------------------------------------------------------------

@@ -60,7 +60,7 @@ int t_fe_forward(LoTeacher* h, const float* x, float* P, void* ws, int train, co
 // 543 positions are ever written" behaviour through compact rows (attc / projc) + one expansion pass, which is also where proj_drop
 // is applied
 int t_block_plain(LoTeacher* h, float* P, void* ws, int e, int l, const LoDropCfg& d, const TBlkT& t, const f16* xin, f16* xout, int train,
-                  float* pool_partial, const TBlkNames& nm, hipStream_t st) {
+                  float* pool_partial, const TBlkNames& nm, hipStream_t st, const TBlk8* f8) {
   const TBlockOff& k = h->blk[e][l];
   const int B = h->B, F = h->F;
   const size_t px = (size_t)B * T_HW;
@@ -77,7 +77,9 @@ int t_block_plain(LoTeacher* h, float* P, void* ws, int e, int l, const LoDropCf
     LO_TRYT(t_bn_finalize(h, bnp, ch.rows, F, k.bn_sc, P, ws, train, st, 1, 1, nullptr, t.ssS, t.mrS));
   }
   const LoConvOp c1{.in = xin, .w = TW(f16, h->o_wp3[e][l][0]), .bias = TP(k.conv1_b), .out = t.rawA, .ex = &ex};
-  LO_TAGGED(nm.conv1, lo_conv_run(g1, c1, st, &ch));
+  const bool c1_f8 = f8 && f8->xin8 && f8->w8[0], c2_f8 = f8 && f8->a28 && f8->w8[1];
+  if (c1_f8) LO_TAGGED(nm.conv1, lo_conv_run_f8(g1, f8->xin8, f8->w8[0], f8->ws8[0], c1, st, &ch));
+  else LO_TAGGED(nm.conv1, lo_conv_run(g1, c1, st, &ch));
   LO_TRYT(t_bn_finalize(h, bnp, ch.rows, F, k.bn1, P, ws, train, st, 1, 1, nullptr, nullptr, t.mrA));
   if (d.on) LO_TRYT(t_drop2d(h, ws, F, d, LO_DS_BLOCK(e, l, 0), st));
   LO_TRYT(t_bn_apply(h, t.rawA, nullptr, nullptr, t.bnA, F, F, 0, 0, nullptr, ws, st, nullptr, d.on));
@@ -89,16 +91,17 @@ int t_block_plain(LoTeacher* h, float* P, void* ws, int e, int l, const LoDropCf
   LO_TAGGED(nm.proj, lo_conv_run(h->gpc, {.in = t.attc, .w = TW(f16, h->o_wproj[e][l]), .bias = TP(k.proj_b), .out = t.projc}, st));
   {
     TOptScope _p(nm.projdrop, 0, 2.0 * px * F, st);
-    LO_TRYT(t_projdrop(F, t.projc, TP(k.proj_b), t.a2, nullptr, px * (F / 8), d.site(LO_DS_BLOCK(e, l, 2)), d.thr, d.inv_keep, st));
+    LO_TRYT(t_projdrop(F, t.projc, TP(k.proj_b), t.a2, c2_f8 ? f8->a28 : nullptr, px * (F / 8), d.site(LO_DS_BLOCK(e, l, 2)), d.thr, d.inv_keep, st));
   }
   const LoConvOp c2{.in = t.a2, .w = TW(f16, h->o_wp3[e][l][1]), .bias = TP(k.conv2_b), .out = t.rawB, .ex = &ex};
-  LO_TAGGED(nm.conv2, lo_conv_run(h->g3b, c2, st, &ch));
+  if (c2_f8) LO_TAGGED(nm.conv2, lo_conv_run_f8(h->g3b, f8->a28, f8->w8[1], f8->ws8[1], c2, st, &ch));
+  else LO_TAGGED(nm.conv2, lo_conv_run(h->g3b, c2, st, &ch));
   LO_TRYT(t_bn_finalize(h, bnp, ch.rows, F, k.bn2, P, ws, train, st, 1, 1, nullptr, nullptr, t.mrB));
   if (d.on) LO_TRYT(t_drop2d(h, ws, F, d, LO_DS_BLOCK(e, l, 3), st));
   // a block output that feeds nothing but the global average pool is only summed (xout null); a caller that wants neither skips the tail
   if (xout || pool_partial)
-    LO_TRYT(t_bn_apply(h, t.rawB, TP(k.layer_scale), sc ? t.scraw : xin, xout, F, F, 0, 1, pool_partial, ws, st, nullptr, d.on, nullptr,
-                       sc ? t.ssS : nullptr));
+    LO_TRYT(t_bn_apply(h, t.rawB, TP(k.layer_scale), sc ? t.scraw : xin, xout, F, F, 0, 1, pool_partial, ws, st, nullptr, d.on,
+                       f8 && xout ? f8->xout8 : nullptr, sc ? t.ssS : nullptr));
   return LO_OK;
 }
 
@@ -112,7 +115,17 @@ static int t_block_wide(const TFwd& c, int e, int l) {
   // the last block's output feeds nothing but the global average pool: a statistics-only call skips its tail, a full call only sums it
   f16* xout = l < 2 ? TW(f16, (l & 1) ? h->o_x1 : h->o_x0) : nullptr;
   float* poolp = (l == 2 && !c.stats_only) ? TW(float, h->o_poolp) : nullptr;
-  return t_block_plain(h, c.P, ws, e, l, c.d, t, xin, xout, c.training, poolp, nm, c.st);
+  if (!c.f8) return t_block_plain(h, c.P, ws, e, l, c.d, t, xin, xout, c.training, poolp, nm, c.st);
+  // fp8 mode: conv1 reads the e4m3 copy of its input (feat8, or the y8 of the previous tail), conv2 the e4m3 output of proj_drop
+  const bool c1 = l == 0 ? h->fp8a : h->fp8b, c2 = h->fp8b;
+  TBlkNames nm8 = nm;
+  if (c1) nm8.conv1 = "t_conv1 (generic, e4m3)";
+  if (c2) nm8.conv2 = "t_conv2 (generic, e4m3)";
+  const TBlk8 f8{c1 ? (l == 0 ? TW(uint8_t, h->o_feat8) : TW(uint8_t, h->o_x8[(l - 1) & 1])) : nullptr, c2 ? TW(uint8_t, h->o_proj8) : nullptr,
+                 (l < 2 && h->fp8b) ? TW(uint8_t, h->o_x8[l & 1]) : nullptr,
+                 {c1 ? TW(uint8_t, h->o_w8[e][l][0]) : nullptr, c2 ? TW(uint8_t, h->o_w8[e][l][1]) : nullptr},
+                 {TW(float, h->o_ws8[e][l][0]), TW(float, h->o_ws8[e][l][1])}};
+  return t_block_plain(h, c.P, ws, e, l, c.d, t, xin, xout, c.training, poolp, nm8, c.st, &f8);
 }
 
 // what must be zero once per workspace: rows / positions that no kernel ever writes
@@ -147,11 +160,12 @@ extern "C" int lo_teacher_forward(LoTeacher* h, const float* x, float* P, void* 
              "lo_teacher_forward: batch %d x feature_dim %d exceeds the 32-bit element index of the dropout mask generator", B, F);
   h->last_p = d.on ? dropout_p : 0.f; h->last_seed = drop_seed;
   h->last_path = d.on ? 2 : (h->sparse && F == 128 ? 0 : 1);
-  const TFwd c{h, P, ws, st, training, d, stats_only, d.on && h->fp8};   // f8: e4m3 operands in the 24 3x3 convolutions of the dropout path
+  // f8: e4m3 operands in the 24 3x3 convolutions -- feature_dim 128: of the dropout path; 256 / 512: of every train-mode call
+  const TFwd c{h, P, ws, st, training, d, stats_only, h->fp8 && (F == 128 ? d.on : training != 0)};
   LO_TRYT(t_zero_once(h, ws, st));
   // ---- feature extractor: the branch BatchNorms fold into the fusion conv unless dropout sits between them
   const TFeDst fd{TW(f16, h->o_raw32), {TW(f16, h->o_dw), TW(f16, h->o_dw), TW(f16, h->o_dw)}, TW(f16, h->o_cat), nullptr, TW(f16, h->o_rawA), TW(f16, h->o_feat),
-                  c.f8 ? TW(uint8_t, h->o_feat8) : nullptr, TW(float, h->o_ss) + 2 * T_FMAX + 2 * 192, nullptr, {nullptr, nullptr, nullptr}, nullptr,
+                  c.f8 && (F == 128 || h->fp8a) ? TW(uint8_t, h->o_feat8) : nullptr, TW(float, h->o_ss) + 2 * T_FMAX + 2 * 192, nullptr, {nullptr, nullptr, nullptr}, nullptr,
                   TW(float, h->o_poolp)};
   static const TFeNames fe_names{"lo_t_conv1", "lo_t_dwconv<3>", "lo_t_dwconv<5>", "lo_t_cat_bn_drop"};
   LO_TRYT(t_fe_forward(h, x, P, ws, training, d, !d.on, fd, fe_names, st));

@@ -170,12 +170,22 @@ static int t_plan_workspace(LoTeacher* h, unsigned flags) {
       h->o_wu[e][l] = take((size_t)1024 * 128 * 2); h->o_ub[e][l] = take(1024 * 4); h->o_wz[e][l] = take((size_t)128 * 1088 * 2);
     }
   h->o_ssb = take((size_t)B * F * 2 * 4);
-  h->fp8 = (flags & LO_TEACHER_FP8_CONV) != 0 && F == 128 && lo_conv3_pp_f8_applies(h->g3);
+  if (flags & LO_TEACHER_FP8_CONV) {
+    if (F == 128) h->fp8 = lo_conv3_pp_f8_applies(h->g3);
+    else {
+      // the plain form: each geometry on its own, where lo_conv_choose serves the teacher epilogue on e4m3 operands
+      LoConvUse u;
+      u.bias = u.ex = u.f8 = true;
+      h->fp8a = lo_conv_choose(h->g3a, u).kernel == LO_CK_IGEMM_F8;
+      h->fp8b = lo_conv_choose(h->g3b, u).kernel == LO_CK_IGEMM_F8;
+      h->fp8 = h->fp8a || h->fp8b;
+    }
+  }
   if (h->fp8) {
     for (int e = 0; e < E; ++e)
       for (int l = 0; l < 3; ++l)
-        for (int c = 0; c < 2; ++c) { h->o_w8[e][l][c] = take((size_t)128 * 9 * 128); h->o_ws8[e][l][c] = take(128 * 4); }
-    h->o_feat8 = take(px * 128); h->o_x8[0] = take(px * 128); h->o_x8[1] = take(px * 128); h->o_proj8 = take(px * 128);
+        for (int c = 0; c < 2; ++c) { h->o_w8[e][l][c] = take((size_t)F * 9 * F); h->o_ws8[e][l][c] = take((size_t)F * 4); }
+    h->o_feat8 = take(px * 128); h->o_x8[0] = take(px * F); h->o_x8[1] = take(px * F); h->o_proj8 = take(px * F);
   }
   h->ws_bytes = off;
   return LO_OK;
@@ -222,9 +232,12 @@ extern "C" int lo_teacher_pack(LoTeacher* h, const float* P, void* ws, void* str
       // feature_dim 128: the fast paths' geometry and their folded operands; else plain operand copies, nothing folded
       LO_TRYT(lo_pack_weight(TP(k.conv1_w), TW(f16, h->o_wp3[e][l][0]), F != 128 ? (l == 0 ? h->g3a : h->g3b) : h->g3, st));
       LO_TRYT(lo_pack_weight(TP(k.conv2_w), TW(f16, h->o_wp3[e][l][1]), F != 128 ? h->g3b : h->g3, st));
-      if (h->fp8)
-        for (int c = 0; c < 2; ++c)
-          LO_TRYT(lo_pack_f8_one(h->g3, TW(f16, h->o_wp3[e][l][c]), TW(uint8_t, h->o_w8[e][l][c]), TW(float, h->o_ws8[e][l][c]), st));
+      for (int c = 0; c < 2 && h->fp8; ++c) {
+        const bool first = l == 0 && c == 0;     // the 128 -> F conv
+        if (F != 128 && !(first ? h->fp8a : h->fp8b)) continue;
+        LO_TRYT(lo_pack_f8_one(F == 128 ? h->g3 : (first ? h->g3a : h->g3b), TW(f16, h->o_wp3[e][l][c]), TW(uint8_t, h->o_w8[e][l][c]),
+                               TW(float, h->o_ws8[e][l][c]), st));
+      }
       LO_TRYT(lo_cast_f32_f16(TP(k.qkv_w), TW(f16, h->o_wqkv[e][l]), (size_t)3 * F * F, st));
       LO_TRYT(lo_cast_f32_f16(TP(k.proj_w), TW(f16, h->o_wproj[e][l]), (size_t)F * F, st));
       if (F != 128 && l == 0) LO_TRYT(lo_cast_f32_f16(TP(k.sc_w), TW(f16, h->o_wsc[e]), (size_t)F * 128, st));

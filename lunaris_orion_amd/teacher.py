@@ -24,6 +24,10 @@ parameter updates by any optimizer are noticed through the parameters' version c
 ``feature_dim``: 128 (the CLI default: folded attention + constant-field shortcuts when no dropout is active) or 256 / 512 (the
 README's High-End recipe, /root/reference/README.md:102-118: a generic path with every tensor at full resolution and the
 ``ExpertBlock.shortcut`` Conv1x1 + BatchNorm of the first block, lunar_evaluator.py:254-257).  ``feature_maps`` is always ``None``.
+
+``mfma_precision="fp8"`` (any ``feature_dim``): the 24 full-resolution 3x3 convolutions of a train-mode forward take OCP e4m3
+operands (fp16 outputs, fp32 BatchNorm statistics); at 256 / 512 these are the 128 -> F and F -> F implicit-GEMM launches that
+carry nearly all of the teacher's time.  Eval mode stays fp16, bit for bit.
 """
 from __future__ import annotations
 
@@ -180,15 +184,15 @@ class LunarMoETeacher(nn.Module):
         # checkpoint calls (lunar_evaluator.py:194-197, 266-275, 411-414).  Default: the reference as it executes (gate + quality heads only).
         self.all_parameters_live = bool(full_backward)
         # mfma_precision (an addition of this build): "fp16" (default, parity-tested) or "fp8" = OCP e4m3 operands in the 24
-        # full-resolution 3x3 convolutions of the train-mode dropout path (BASELINE config 5); eval mode is fp16 either way
+        # full-resolution 3x3 convolutions of a train-mode forward (BASELINE config 5) -- feature_dim 128: on the dropout path
+        # (dropout_rate > 0); 256 / 512: in every train-mode forward, the statistics-only one included.  Eval mode, the kept forward
+        # of the full backward and every backward are fp16 either way
         if mfma_precision not in ("fp16", "fp8"):
             raise ValueError(f"mfma_precision must be 'fp16' or 'fp8', got {mfma_precision!r}")
         self.mfma_precision = mfma_precision
         if feature_dim not in (128, 256, 512) or expert_layers != 3 or intermediate_dim != 256 or rel_pos_size != 8:
             raise NotImplementedError("built: feature_dim 128 (the CLI default), 256 or 512 (README High-End recipe) with expert_layers=3, "
                                       "intermediate_dim=256, rel_pos_size=8 (the CLI defaults)")
-        if feature_dim != 128 and mfma_precision != "fp16":
-            raise NotImplementedError("the fp8 operand mode covers feature_dim 128 only")
         self.num_experts, self.feature_dim, self.dropout_rate = num_experts, feature_dim, dropout_rate
         self.rel_pos_size, self.use_checkpointing, self.expert_layers = rel_pos_size, use_checkpointing, expert_layers
         self.intermediate_dim, self.embedding_dim = intermediate_dim, embedding_dim

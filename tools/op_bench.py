@@ -4,6 +4,7 @@
   python tools/op_bench.py --op conv|wgrad --kind 0 --B 64 --H 32 --Cin 128 --Cout 128 --iters 20
   python tools/op_bench.py --op attn --B 64 --H 8 --Cin 512        (SelfAttention2d forward on a [B, Cin, H, H] map)
   python tools/op_bench.py --op imgdgrad --stride 2|1 --B 64       (images' data gradient: VAE encoder.down1.0 | teacher conv1)
+  python tools/op_bench.py --op tconv --B 8 --pairs 3              (wide teacher 3x3 convs at 128x128, e4m3 against fp16, interleaved; markdown table)
 """
 import argparse
 import ctypes as C
@@ -14,6 +15,56 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lunaris_orion_amd import _lib  # noqa: E402
+
+
+def tconv(a):
+    """The feature_dim 256 / 512 teacher's 3x3 convolutions at 128x128: the e4m3 launch (lo_teacher_conv3x3_forward_f8: LeakyReLU + BatchNorm
+    partial rows) against the fp16 launch of the same shape (lo_conv_forward kind 0 with its partial sums), `--pairs` interleaved pairs of
+    `--iters` launches each after a warm-up of both.  Prints one markdown table row per shape: the best and the worst of the pairs."""
+    lib, st, B, H = _lib.lib, _lib.stream_ptr(), a.B, 128
+    print(f"| shape (B = {B}, 128x128) | fp16 us (pairs) | e4m3 us (pairs) | fp16 TFLOP/s (of 2500) | e4m3 TFLOP/s (of 5000) | e4m3 faster in every pair |")
+    print("|---|---|---|---|---|---|")
+    for Cin, Cout in ((128, 256), (256, 256), (128, 512), (512, 512)):
+        x = torch.nn.functional.leaky_relu(torch.randn(B, H, H, Cin, device="cuda"), 0.2).half()
+        n = lib.lo_packed_weight_elems_for(0, B, H, H, Cin, Cout)
+        wp = (torch.randn(n, device="cuda") * (9 * Cin) ** -0.5).half()
+        bias = torch.randn(Cout, device="cuda") * 0.1
+        x8, w8 = torch.empty(x.numel(), dtype=torch.uint8, device="cuda"), torch.empty(n, dtype=torch.uint8, device="cuda")
+        ws = torch.empty(Cout, device="cuda")
+        _lib.check(lib.lo_quantize_act_f8(x.data_ptr(), x8.data_ptr(), x.numel(), st))
+        _lib.check(lib.lo_pack_weight_f8_for(0, B, H, H, Cin, Cout, wp.data_ptr(), w8.data_ptr(), ws.data_ptr(), st))
+        out = torch.empty(B, H, H, Cout, dtype=torch.float16, device="cuda")
+        part = torch.empty(B * H * H // 64 * Cout * 2, device="cuda")
+        mt, rows = C.c_int(0), C.c_int(0)
+        fl = 2.0 * B * H * H * Cout * 9 * Cin
+
+        def run16():
+            _lib.check(lib.lo_conv_forward(0, B, H, H, Cin, Cout, x.data_ptr(), wp.data_ptr(), bias.data_ptr(), None, out.data_ptr(), part.data_ptr(), C.byref(mt), st))
+
+        def run8():
+            _lib.check(lib.lo_teacher_conv3x3_forward_f8(B, H, H, Cin, Cout, x8.data_ptr(), w8.data_ptr(), ws.data_ptr(), bias.data_ptr(), 1, out.data_ptr(),
+                                                         part.data_ptr(), C.byref(rows), st))
+
+        def timed(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / a.iters * 1e3
+        for fn in (run16, run8):
+            for _ in range(5):
+                fn()
+        torch.cuda.synchronize()
+        t16, t8 = [], []
+        for _ in range(a.pairs):
+            t16.append(timed(run16))
+            t8.append(timed(run8))
+        tf = lambda us: fl / us / 1e6
+        print(f"| {Cin} -> {Cout} | {' / '.join(f'{t:.1f}' for t in t16)} | {' / '.join(f'{t:.1f}' for t in t8)} | "
+              f"{tf(max(t16)):.0f}-{tf(min(t16)):.0f} ({tf(min(t16)) / 2500:.2f}) | {tf(max(t8)):.0f}-{tf(min(t8)):.0f} ({tf(min(t8)) / 5000:.2f}) | "
+              f"{'yes' if all(p8 < p16 for p8, p16 in zip(t8, t16)) else 'NO'} |", flush=True)
 
 
 def main():
@@ -27,7 +78,10 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--stats", type=int, default=1)
     ap.add_argument("--stride", type=int, default=2, help="--op imgdgrad: 2 = the VAE's first conv (64 channels), 1 = the teacher's conv1 (32)")
+    ap.add_argument("--pairs", type=int, default=3, help="--op tconv: interleaved fp16 / e4m3 pairs per shape")
     a = ap.parse_args()
+    if a.op == "tconv":
+        return tconv(a)
     lib = _lib.lib
     B, H, Cin, Cout, kind = a.B, a.H, a.Cin, a.Cout, a.kind
     Ho = H if kind in (0, 3, 6) else (H // 2 if kind in (1, 5) else 2 * H)
