@@ -219,6 +219,33 @@ def test_teacher_input_grad_in_train_mode(drop):
     assert live > 200
 
 
+# ---- 5b. the same x.grad against the fp16-rounding oracle ------------------------------------------------------------------------
+INPUT_GRAD_ROUNDED_BOUND = {"full": 3e-2, "pooled16": 4e-3}      # measured, see the table in tests/test_teacher_fullgrad_gpu.py
+
+
+@pytest.mark.parametrize("drop", [False, True])
+def test_teacher_input_grad_against_the_fp16_rounding_oracle(drop):
+    """lo_teacher_full_backward_dx against x.grad of the oracle that rounds to fp16 where the plain-form forward does
+    (oracle/teacher_ref.py, act_dtype): same structure as _assert_teacher_input_grad_close, bounds from the measurement."""
+    from tests.test_teacher_fullgrad_gpu import _oracle_extras
+    B = 2
+    x = _x(B)
+    t = _teacher(drop)
+    xg = x.cuda().requires_grad_()
+    (QW * -torch.mean(t(xg)["quality_scores"])).backward()
+    got = xg.grad.cpu()
+    ref, ref32 = _oracle_extras(x, drop, act_dtype=torch.float16)["x_grad"], _oracle_extras(x, drop)["x_grad"]
+    pool = lambda a: torch.nn.functional.avg_pool2d(a.double(), 16)
+    full, pooled = _rel(got, ref), _rel(pool(got), pool(ref))
+    print(f"x.grad against the rounding oracle: {full:.4f}, 16x16-pooled {pooled:.4f}  (fp32 oracle: {_rel(got, ref32):.4f}, {_rel(pool(got), pool(ref32)):.4f})")
+    assert full <= INPUT_GRAD_ROUNDED_BOUND["full"], full
+    assert pooled <= INPUT_GRAD_ROUNDED_BOUND["pooled16"], pooled
+    g, r = got.double().flatten(), ref.double().flatten()
+    cos = torch.dot(g, r).item() / (g.norm().item() * r.norm().item())
+    assert cos >= 1.0 - 0.5 * INPUT_GRAD_ROUNDED_BOUND["full"] ** 2 - 1e-6, cos       # what a deviation of that size can do to the direction
+    assert abs(g.norm().item() / r.norm().item() - 1.0) <= 1e-2, (g.norm().item(), r.norm().item())
+
+
 # ---- 6. the teacher as a differentiable reward ----------------------------------------------------------------------------------
 def test_teacher_as_a_differentiable_reward_reaches_the_vae_and_the_images():
     x, eps = _x(2), R.closed_form_eps(2, L)
