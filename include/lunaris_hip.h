@@ -15,6 +15,20 @@
  *     (images / reconstructions NCHW, parameters in their nn.Module layouts);
  *   - gradients flowing between kernels are multiplied by `loss_scale` (fp16 range); every parameter gradient that
  *     leaves the library is un-scaled (true gradient, fp32).
+ *
+ * What the caller provides
+ *   - alignment: every tensor, scratch and workspace pointer is 16-byte aligned (the kernels' widest access: one 16-byte vector
+ *     load / store / LDS-DMA lane, at element offsets that are multiples of 16 bytes from the pointer).  Nothing more is assumed:
+ *     not the 256 / 512 bytes an allocator usually gives.  Tensors of 4-byte elements with fewer than four elements (a bias of
+ *     three, a device scalar) need only their element's alignment;
+ *   - sizes: every buffer needs exactly the number of elements its entry point states below (a size function, a dimension list or
+ *     a count in a comment) and the library touches no byte outside them -- neither reads nor writes; there is no hidden padding
+ *     requirement;
+ *   - contents: inputs are read-only.  Output tensors, scratch buffers (slabs, partial tables, `rows`, `bws`) and workspaces may
+ *     hold ANYTHING before a call (recycled allocator blocks, NaN): the library writes whatever it later reads, and zeroes the
+ *     few regions of a workspace it relies on being zero the first time a handle sees that workspace pointer.  The exceptions are
+ *     named where they occur: the AdamW moments m / v and the 1028-float optimizer `scratch` (its skipped-update counter
+ *     accumulates) start zeroed by the caller.
  */
 #ifndef LUNARIS_HIP_H
 #define LUNARIS_HIP_H
@@ -53,7 +67,9 @@ size_t lo_packed_weight_elems_for(int kind, int B, int H, int W, int Cin, int Co
 /* canonical fp32 weight (nn.Module layout) -> packed fp16 operand of the implicit GEMM */
 int lo_pack_weight_for(int kind, int B, int H, int W, int Cin, int Cout, const float* w, void* wp, void* stream);
 /* out = conv(in) + bias (+ add_src); optional GroupNorm partial sums [B][MT][8][2]; returns MT through *mt_out.
- * in/out/add_src: fp16 NHWC.  Replaces aten::convolution / aten::addmm. */
+ * in/out/add_src: fp16 NHWC.  Replaces aten::convolution / aten::addmm.  gn_partial: exactly B*MT*16 floats; MT is a function of
+ * (kind, B, H, W, Cin, Cout) and of which optional pointers are non-NULL: the same arguments always give the same MT, so a caller
+ * sizes the table from the *mt_out of an earlier call with those arguments (the step executor asks the selection function). */
 int lo_conv_forward(int kind, int B, int H, int W, int Cin, int Cout, const void* in, const void* wp, const float* bias,
                     const void* add_src, void* out, float* gn_partial, int* mt_out, void* stream);
 /* e4m3 operand forms (see LO_VAE_FP8_FWD below; Cin % 128 == 0, Cout % 64 == 0): x8 = fp8(8 * x16) saturating at 448;
@@ -95,14 +111,17 @@ int lo_gn_mish_backward(const void* dy, const void* v, const void* other, const 
                         const float* beta, void* ds, void* dv, float* P1, float* P2, float* dgamma, float* dbeta,
                         float* dbias, int B, int HW, int C, int mode, float scale, void* stream);
 
-/* first conv Conv2d(3,64,k3,s2,p1) on fp32 NCHW images (lunar_generate.py:95) and its weight gradient */
+/* first conv Conv2d(3,64,k3,s2,p1) on fp32 NCHW images (lunar_generate.py:95) and its weight gradient.  x [B,3,128,128], w [64,3,3,3],
+ * bias [64], v fp16 NHWC [B,64,64,64], gn_partial [B][64][8][2] floats (MT = 64), partial B*16*1728 floats, dw [64,3,3,3]. */
 int lo_first_conv_forward(const float* x, const float* w, const float* bias, void* v, float* gn_partial, int B, void* stream);
 int lo_first_conv_wgrad_op(const float* x, const void* dv, float* partial /*B*16*1728*/, float* dw, int B, float scale, void* stream);
 /* data gradient of a 3x3 / padding 1 conv with 3 input channels onto the images: dx fp32 NCHW [B,3,128,128] = scale * conv2d_input(dy, w),
  * dy fp16 NHWC [B][128/stride][128/stride][cout], w fp32 [cout][3][3][3].  Built for (stride 2, cout 64: the VAE's encoder.down1.0) and
  * (stride 1, cout 32: the teacher's feature_extractor.conv1.0).  Deterministic (no atomics). */
 int lo_image_dgrad_op(const void* dy, int cout, int stride, const float* w, int B, float scale, float* dx, void* stream);
-/* final conv Conv2d(32,3,k3,p1)+tanh (+MSE partial sums, B*64 floats) (lunar_generate.py:192,227-228; train_hybrid.py:859) */
+/* final conv Conv2d(32,3,k3,p1)+tanh (+MSE partial sums, B*64 floats) (lunar_generate.py:192,227-228; train_hybrid.py:859).
+ * a4 / da4 fp16 NHWC [B,128,128,32]; w [3,32,3,3], bias / db [3]; recon, target, drecon fp32 NCHW [B,3,128,128]; coef_dev one float;
+ * partial B*64*867 floats of scratch. */
 int lo_final_conv_forward(const void* a4, const float* w, const float* bias, const float* target, float* recon,
                           float* mse_partial, int B, void* stream);
 int lo_final_conv_backward(const void* a4, const float* w, const float* recon, const float* target, const float* drecon,

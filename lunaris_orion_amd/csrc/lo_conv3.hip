@@ -15,6 +15,8 @@
 #include <stdlib.h>
 
 __device__ __attribute__((aligned(256))) unsigned int lo_zero_page3[64];
+// every padding lane of the patch / weight DMA below reads the page's base: 1 address x 16 B per lane
+static_assert(sizeof(lo_zero_page3) >= 1 * 16, "LDS-DMA padding lanes read 16 B at offset 0 of the zero page");
 #define LO_VMCNT(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
 
 __device__ __forceinline__ int lo_xcd_remap3(int bid, int total) {

@@ -4,6 +4,8 @@
 
 // 16 zero bytes x 16: source of every LDS-DMA lane whose row is padding / out of range
 static __device__ __attribute__((aligned(256))) unsigned int lo_zero_page[64];
+// its users (lo_igemm_nt, lo_wgrad_tn) give every padding lane the page's base: 1 address x 16 B per lane
+static_assert(sizeof(lo_zero_page) >= 1 * 16, "LDS-DMA padding lanes read 16 B at offset 0 of the zero page");
 
 #define LO_VMCNT(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
 

@@ -397,6 +397,9 @@ struct LcBwdArgs {
 // lane-linear).  Out-of-image pixels (and the tail of the last 1-KiB instruction) are fetched from a zero page.
 // ---------------------------------------------------------------------------------------------
 __device__ __attribute__((aligned(256))) unsigned int lo_zero_page_e[64];
+// lc_dma_a4: every padding lane reads the SAME 16 B at offset 0 (1 address x 16 B); lc_dma_rt: lane l reads 4 B at 4 l (64 lanes x 4 B).
+static_assert(sizeof(lo_zero_page_e) >= 1 * 16, "lc_dma_a4: 16 B per lane, all lanes at offset 0 of the zero page");
+static_assert(sizeof(lo_zero_page_e) >= 64 * 4, "lc_dma_rt: 64 lanes x 4 B, lane-linear in the zero page");
 #define LC_PATCH_BYTES (21 * 1024)     // 324 pixels x 64 B = 20.25 KiB, in whole 1-KiB DMA instructions
 __device__ __forceinline__ void lc_dma_a4(const f16* __restrict__ a4, unsigned int lds_base, int n, int ty, int tx, int wave, int lane) {
   const unsigned char* zpage = reinterpret_cast<const unsigned char*>(lo_zero_page_e);
@@ -407,7 +410,7 @@ __device__ __forceinline__ void lc_dma_a4(const f16* __restrict__ a4, unsigned i
     const int q = k * 64 + lane, p = q >> 2, slot = q & 3;
     const int y = p / LC_TP, xx = p - y * LC_TP;
     const int iy = ty * LC_T - 1 + y, ix = tx * LC_T - 1 + xx;
-    const void* src = zpage + lane * 4;
+    const void* src = zpage;                                // 16 B per lane: one in-bounds source for every padding lane
     if (p < LC_TP * LC_TP && (unsigned)iy < 128u && (unsigned)ix < 128u) src = a4 + (((size_t)n * 128 + iy) * 128 + ix) * LC_CI + slot * 8;
     lo_dma16(src, __builtin_amdgcn_readfirstlane(lds_base + k * 1024));
   }

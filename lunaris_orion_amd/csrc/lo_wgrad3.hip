@@ -17,6 +17,8 @@
 #include <stdlib.h>
 
 __device__ __attribute__((aligned(256))) unsigned int lo_zero_page_w3[64];
+// every padding lane reads the page's base: 1 address x 16 B per lane
+static_assert(sizeof(lo_zero_page_w3) >= 1 * 16, "LDS-DMA padding lanes read 16 B at offset 0 of the zero page");
 #define LO_VMCNT(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
 
 struct Wgrad3Args {

@@ -85,6 +85,12 @@ class ExpertBlock(nn.Module):
         self.layer_scale = nn.Parameter(torch.ones(1, out_channels, 1, 1) * layer_scale_init)
 
 
+def _alloc_workspace(nbytes: int, device: torch.device) -> torch.Tensor:
+    """Device memory for a teacher engine's workspace (`ws`), full-backward scratch (`bws`) or head-gradient `rows`; contents unspecified, see
+    `vae._alloc_workspace`.  The poisoned-workspace tests swap this function."""
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
 class _TeacherEngine:
     """Native plan + workspace for one batch size; the handle is released with the object (lo_teacher_destroy)."""
 
@@ -93,7 +99,7 @@ class _TeacherEngine:
         _lib.check(_lib.lib.lo_teacher_create_ex(batch, model.num_experts, model.feature_dim, model.embedding_dim,
                                                  1 if model.mfma_precision == "fp8" else 0, C.byref(h)), "lo_teacher_create_ex")
         self.handle = h
-        self.ws = torch.empty(_lib.lib.lo_teacher_workspace_bytes(h), dtype=torch.uint8, device=model._flat.device)
+        self.ws = _alloc_workspace(_lib.lib.lo_teacher_workspace_bytes(h), model._flat.device)
         self.packed_version = None
 
     def __iter__(self):          # (handle, workspace, packed version): the tuple form older call sites unpack
@@ -139,7 +145,7 @@ class _TeacherFunction(torch.autograd.Function):
         gq, gw = cont(gq), cont(gw)
         b, e = C.c_size_t(), C.c_size_t()
         _lib.check(_lib.lib.lo_teacher_grad_range(eng.handle, C.byref(b), C.byref(e)), "lo_teacher_grad_range")
-        rows = torch.empty(w.shape[0] * (e.value - b.value), dtype=torch.float32, device=w.device)
+        rows = _alloc_workspace(w.shape[0] * (e.value - b.value) * 4, w.device).view(torch.float32)
         grads = torch.zeros_like(model._flat)
         dx = None
         if ctx.full and (gq is not None or gw is not None):
@@ -149,7 +155,7 @@ class _TeacherFunction(torch.autograd.Function):
             scr, (gq, gw) = _normalise_upstream([gq, gw])
             B = w.shape[0]
             if getattr(eng, "bws", None) is None:
-                eng.bws = torch.empty(_lib.lib.lo_teacher_full_backward_bytes(eng.handle), dtype=torch.uint8, device=w.device)
+                eng.bws = _alloc_workspace(_lib.lib.lo_teacher_full_backward_bytes(eng.handle), w.device)
             dx = torch.empty_like(ctx.x) if ctx.want_dx and ctx.needs_input_grad[2] else None
             _lib.check(_lib.lib.lo_teacher_full_backward_dx(eng.handle, ctx.x.data_ptr(), model._flat.data_ptr(), eng.ws.data_ptr(), eng.bws.data_ptr(),
                                                             pooled_f.data_ptr(), pooled_e.data_ptr(), raw_q.data_ptr(), w.data_ptr(), _lib.ptr(gq),
@@ -382,7 +388,7 @@ class LunarMoETeacher(nn.Module):
         seed = self._next_drop_seed() if p > 0 else 0
         if keep and self.training:
             if getattr(eng, "bws", None) is None:
-                eng.bws = torch.empty(_lib.lib.lo_teacher_full_backward_bytes(eng.handle), dtype=torch.uint8, device=dev)
+                eng.bws = _alloc_workspace(_lib.lib.lo_teacher_full_backward_bytes(eng.handle), dev)
             _lib.check(_lib.lib.lo_teacher_forward_keep(eng.handle, x.data_ptr(), self._flat.data_ptr(), eng.ws.data_ptr(), eng.bws.data_ptr(),
                                                         p, seed, q.data_ptr(), w.data_ptr(), st.data_ptr(), pr.data_ptr(), sem.data_ptr(),
                                                         _lib.stream_ptr()), "lo_teacher_forward_keep")
@@ -406,10 +412,10 @@ class LunarMoETeacher(nn.Module):
         B = x.shape[0]
         eng = self._engine(B)
         if getattr(eng, "bws", None) is None:
-            eng.bws = torch.empty(_lib.lib.lo_teacher_full_backward_bytes(eng.handle), dtype=torch.uint8, device=x.device)
+            eng.bws = _alloc_workspace(_lib.lib.lo_teacher_full_backward_bytes(eng.handle), x.device)
         b, e = C.c_size_t(), C.c_size_t()
         _lib.check(_lib.lib.lo_teacher_grad_range(eng.handle, C.byref(b), C.byref(e)), "lo_teacher_grad_range")
-        rows = torch.empty(B * (e.value - b.value), dtype=torch.float32, device=x.device)
+        rows = _alloc_workspace(B * (e.value - b.value) * 4, x.device).view(torch.float32)
         grads = torch.empty_like(self._flat)
         if gscale is None:
             gscale = 64.0 * B * 16384.0                      # a power of two for power-of-two batches; any positive value is exact enough

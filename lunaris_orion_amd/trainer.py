@@ -26,6 +26,13 @@ from . import _lib
 from .vae import LunarisCoreVAE
 
 
+def _alloc_scratch(nbytes: int, device: torch.device) -> torch.Tensor:
+    """Device memory the steppers hand to kernels as pure scratch (the head backward's `rows`, the teacher's full-backward `bws`):
+    contents unspecified.  The poisoned-workspace tests swap this function; state the kernels accumulate into (the 1028-float
+    optimizer scratch with its skipped-update counter, AdamW moments) is zero-initialised where it is created and is not scratch."""
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
 def cosine_warm_restarts_lr(base_lr: float, eta_min: float, t0: int, t_mult: int, epoch: int) -> float:
     """torch.optim.lr_scheduler.CosineAnnealingWarmRestarts after ``epoch`` calls of step() (train_hybrid.py:516-521)."""
     t_i, t_cur = t0, epoch
@@ -399,7 +406,7 @@ class HybridStepper(VAEStepper):
         hb, he = self.t_heads_range
         rows = getattr(self, "_t_rows", None)
         if rows is None or rows.numel() != batch * (he - hb):
-            self._t_rows = torch.empty(batch * (he - hb), dtype=torch.float32, device=t._flat.device)
+            self._t_rows = _alloc_scratch(batch * (he - hb) * 4, t._flat.device).view(torch.float32)
         return h, ws
 
     def step(self, images: torch.Tensor, batch_idx: int = 0, eps: Optional[torch.Tensor] = None, **_):
@@ -463,7 +470,7 @@ class HybridStepper(VAEStepper):
         non-reentrant checkpoints): lo_teacher_full_backward on the evaluated images, then lo_teacher_clip_adamw_full."""
         eng = t._engine(recon.shape[0])
         if getattr(eng, "bws", None) is None:
-            eng.bws = torch.empty(_lib.lib.lo_teacher_full_backward_bytes(eng.handle), dtype=torch.uint8, device=recon.device)
+            eng.bws = _alloc_scratch(_lib.lib.lo_teacher_full_backward_bytes(eng.handle), recon.device)
         gscale = 64.0 * recon.shape[0] * 16384.0
         _lib.check(_lib.lib.lo_teacher_full_backward(eng.handle, recon.data_ptr(), t._flat.data_ptr(), eng.ws.data_ptr(), eng.bws.data_ptr(),
                                                      tout["expert_weights"].data_ptr(), float(self.quality_weight) / float(self.accum),

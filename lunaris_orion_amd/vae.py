@@ -311,6 +311,13 @@ class _DecoderFunction(torch.autograd.Function):
         return (None, None, dz) + tuple(dsk[:ns]) + grads
 
 
+def _alloc_workspace(nbytes: int, device: torch.device) -> torch.Tensor:
+    """Device memory for an engine's workspace.  The library promises nothing about what a workspace holds before its first call and
+    zeroes what it needs itself (include/lunaris_hip.h, "What the caller provides"), so recycled allocator blocks are fine; the
+    poisoned-workspace tests swap this function for one that hands out a pre-filled, guard-banded view."""
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
 class _Engine:
     """Native plan + workspace for one (batch, latent_dim, device)."""
 
@@ -318,7 +325,7 @@ class _Engine:
         self.handle = C.c_void_p()
         _lib.check(_lib.lib.lo_vae_create_ex(batch, latent_dim, flags, C.byref(self.handle)), "lo_vae_create_ex")
         self.batch, self.latent_dim, self.device = batch, latent_dim, device
-        self.ws = torch.empty(_lib.lib.lo_vae_workspace_bytes(self.handle), dtype=torch.uint8, device=device)
+        self.ws = _alloc_workspace(_lib.lib.lo_vae_workspace_bytes(self.handle), device)
         self.packed_version = None      # (explicit version, sum of the parameters' version counters) of the last pack
         self.fac_mode = 0               # lo_vae_set_linear_factored: 0 off, 1 single process, 2 data parallel (set by the stepper)
         self.gen_enc = self.gen_dec = 0 # bumped by every call that overwrites the encoder / decoder activations in the workspace

@@ -3,6 +3,8 @@ import ctypes as C
 
 import torch
 
+from tests.guarded import ALIGN, check_guards, gin, guarded
+
 
 def L():
     from lunaris_orion_amd import _lib
@@ -28,14 +30,17 @@ def sync():
     torch.cuda.synchronize()
 
 
-def conv_forward(kind, x_nchw, w, bias, Cout, add_src=None, want_partial=False):
+def conv_forward(kind, x_nchw, w, bias, Cout, add_src=None, want_partial=False, skew=0):
+    """lo_conv_forward on guard-banded buffers of exactly the ABI's sizes (tests/guarded.py); every guard is checked before returning.
+    The GroupNorm partial table is [B][MT][8][2] with MT known only from a call: a first call on a roomy table learns it (MT is a
+    function of the shape and of which optional pointers are set), the checked call gets B*MT*16 floats and not one more."""
     lib = L()
     B, Cin, H, W = x_nchw.shape
-    xin = to_nhwc_h(x_nchw)
+    xin = gin(x_nchw.permute(0, 2, 3, 1), skew, torch.float16)
     n = lib.lib.lo_packed_weight_elems_for(kind, B, H, W, Cin, Cout)
     assert n > 0, lib.lib.lo_last_error()
-    wp = torch.empty(n, dtype=torch.float16, device="cuda")
-    wd = w.contiguous().cuda()
+    wp = guarded(n, torch.float16, "out", skew)
+    wd = gin(w, skew)
     lib.check(lib.lib.lo_pack_weight_for(kind, B, H, W, Cin, Cout, wd.data_ptr(), wp.data_ptr(), lib.stream_ptr()), "pack")
     if kind in (0, 3, 6):
         Ho, Wo = H, W
@@ -43,30 +48,42 @@ def conv_forward(kind, x_nchw, w, bias, Cout, add_src=None, want_partial=False):
         Ho, Wo = H // 2, W // 2
     else:
         Ho, Wo = 2 * H, 2 * W
-    out = torch.full((B, Ho, Wo, Cout), float("nan"), dtype=torch.float16, device="cuda")
-    bd = bias.cuda() if bias is not None else None
-    ad = to_nhwc_h(add_src) if add_src is not None else None
-    part = torch.full((B * 4096 * 16,), float("nan"), dtype=torch.float32, device="cuda") if want_partial else None
+    out = guarded((B, Ho, Wo, Cout), torch.float16, "out", skew)
+    bd = gin(bias, skew) if bias is not None else None
+    ad = gin(add_src.permute(0, 2, 3, 1), skew, torch.float16) if add_src is not None else None
     mt = C.c_int(0)
+    part = None
+    if want_partial:
+        roomy = torch.full((B * 4096 * 16,), float("nan"), dtype=torch.float32, device="cuda")
+        lib.check(lib.lib.lo_conv_forward(kind, B, H, W, Cin, Cout, xin.data_ptr(), wp.data_ptr(), lib.ptr(bd), lib.ptr(ad),
+                                          out.data_ptr(), roomy.data_ptr(), C.byref(mt), lib.stream_ptr()), "conv_forward (MT)")
+        sync()
+        out.fill_(float("nan"))
+        part = guarded((B, mt.value, 8, 2), torch.float32, "out", skew)
     lib.check(lib.lib.lo_conv_forward(kind, B, H, W, Cin, Cout, xin.data_ptr(), wp.data_ptr(), lib.ptr(bd), lib.ptr(ad),
                                       out.data_ptr(), lib.ptr(part), C.byref(mt), lib.stream_ptr()), "conv_forward")
     sync()
+    check_guards(xin, wp, wd, out, bd, ad, part)
     if want_partial:
-        return out, part[: B * mt.value * 16].view(B, mt.value, 8, 2), mt.value
+        assert tuple(part.shape) == (B, mt.value, 8, 2), "MT changed between two calls with the same arguments"
+        return out, part, mt.value
     return out
 
 
-def conv_wgrad(kind, x_nchw, dy_nchw, Cout, wshape, scale=1.0):
+def conv_wgrad(kind, x_nchw, dy_nchw, Cout, wshape, scale=1.0, skew=0):
+    """lo_conv_wgrad on guard-banded buffers; the slab is exactly lo_wgrad_slab_bytes_for bytes."""
     lib = L()
     B, Cin, H, W = x_nchw.shape
-    x = to_nhwc_h(x_nchw)
-    dy = to_nhwc_h(dy_nchw)
+    x = gin(x_nchw.permute(0, 2, 3, 1), skew, torch.float16)
+    dy = gin(dy_nchw.permute(0, 2, 3, 1), skew, torch.float16)
     nb = lib.lib.lo_wgrad_slab_bytes_for(kind, B, H, W, Cin, Cout)
-    slab = torch.empty(max(nb // 4, 1), dtype=torch.float32, device="cuda")
-    grad = torch.full(wshape, float("nan"), dtype=torch.float32, device="cuda")
+    assert nb % 4 == 0
+    slab = guarded(max(nb, ALIGN) // 4, torch.float32, "out", skew)
+    grad = guarded(tuple(wshape), torch.float32, "out", skew)
     lib.check(lib.lib.lo_conv_wgrad(kind, B, H, W, Cin, Cout, x.data_ptr(), dy.data_ptr(), slab.data_ptr(), grad.data_ptr(),
                                     scale, lib.stream_ptr()), "wgrad")
     sync()
+    check_guards(x, dy, slab, grad)
     return grad.cpu()
 
 

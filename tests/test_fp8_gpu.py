@@ -15,7 +15,8 @@ import torch
 import torch.nn.functional as F
 
 from oracle import vae_ref as R
-from tests.hip_helpers import L as LIB, from_nhwc, h16, sync, to_nhwc_h
+from tests.guarded import check_guards, gin, guarded
+from tests.hip_helpers import L as LIB, from_nhwc, h16, sync
 
 pytestmark = pytest.mark.gpu
 KIND_S1, KIND_S2, KIND_T4 = 0, 1, 2
@@ -27,20 +28,30 @@ def _rand(*shape, seed=0, scale=1.0):
     return h16(torch.randn(*shape, generator=g) * scale)
 
 
+def to_nhwc_h(x_nchw, skew=0):
+    """fp32 NCHW (CPU) -> guard-banded fp16 NHWC input on the GPU (tests/guarded.py)."""
+    return gin(x_nchw.permute(0, 2, 3, 1), skew, torch.float16)
+
+
 def _decode(u8):
     return u8.cpu().view(torch.float8_e4m3fn).float()
 
 
 def test_activation_quantiser_matches_torch_e4m3():
+    _activation_quantiser()
+
+
+def _activation_quantiser(skew=0):
     lib = LIB()
     g = torch.Generator().manual_seed(5)
     x = torch.cat([torch.randn(4096, generator=g) * 2.0, torch.tensor([0.0, 1e-4, -3e-4, 55.9, 56.0, 57.0, 1000.0, -1000.0])]).half()
-    xd = x.cuda()
-    q = torch.empty(x.numel(), dtype=torch.uint8, device="cuda")
+    xd = gin(x, skew)
+    q = guarded(x.numel(), torch.uint8, "out", skew)
     lib.check(lib.lib.lo_quantize_act_f8(xd.data_ptr(), q.data_ptr(), x.numel(), lib.stream_ptr()), "quantize")
     sync()
     want = (x.float() * ACT_SCALE).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).float()
     assert torch.equal(_decode(q), want)                       # round-to-nearest-even, saturating, OCP encoding
+    check_guards(xd, q)
 
 
 CASES = [
@@ -57,6 +68,10 @@ CASES = [
 
 @pytest.mark.parametrize("kind,B,Cin,Cout,H", CASES)
 def test_fp8_conv_matches_fp16_kernel_on_dequantised_operands(kind, B, Cin, Cout, H):
+    _fp8_conv(kind, B, Cin, Cout, H)
+
+
+def _fp8_conv(kind, B, Cin, Cout, H, skew=0):
     lib = LIB()
     x = F.mish(_rand(B, Cin, H, H, seed=1))                                    # what these convs read: Mish outputs
     x = h16(x)
@@ -70,23 +85,33 @@ def test_fp8_conv_matches_fp16_kernel_on_dequantised_operands(kind, B, Cin, Cout
         Ho = H if kind == KIND_S1 else H // 2
     bias = _rand(Cout, seed=3, scale=0.1)
     ref32 = ref32 + bias.view(1, -1, 1, 1)
-    xin = to_nhwc_h(x)
+    xin = to_nhwc_h(x, skew)
     n = lib.lib.lo_packed_weight_elems_for(kind, B, H, H, Cin, Cout)
-    wp = torch.empty(n, dtype=torch.float16, device="cuda")
-    lib.check(lib.lib.lo_pack_weight_for(kind, B, H, H, Cin, Cout, w.contiguous().cuda().data_ptr(), wp.data_ptr(), lib.stream_ptr()), "pack")
+    wp = guarded(n, torch.float16, "out", skew)
+    wsrc = gin(w, skew)
+    lib.check(lib.lib.lo_pack_weight_for(kind, B, H, H, Cin, Cout, wsrc.data_ptr(), wp.data_ptr(), lib.stream_ptr()), "pack")
     nph = 4 if kind == KIND_T4 else 1
-    x8 = torch.empty(xin.numel(), dtype=torch.uint8, device="cuda")
-    w8 = torch.empty(n, dtype=torch.uint8, device="cuda")
-    ws = torch.full((nph * Cout,), float("nan"), dtype=torch.float32, device="cuda")
+    x8 = guarded(xin.numel(), torch.uint8, "out", skew)
+    w8 = guarded(n, torch.uint8, "out", skew)
+    ws = guarded(nph * Cout, torch.float32, "out", skew)              # the header's size: wscale[n_phase][Cout]
     lib.check(lib.lib.lo_quantize_act_f8(xin.data_ptr(), x8.data_ptr(), xin.numel(), lib.stream_ptr()), "quantize")
     lib.check(lib.lib.lo_pack_weight_f8_for(kind, B, H, H, Cin, Cout, wp.data_ptr(), w8.data_ptr(), ws.data_ptr(), lib.stream_ptr()), "pack8")
-    out8 = torch.full((B, Ho, Ho, Cout), float("nan"), dtype=torch.float16, device="cuda")
-    part = torch.full((B * 4096 * 16,), float("nan"), dtype=torch.float32, device="cuda")
+    out8 = guarded((B, Ho, Ho, Cout), torch.float16, "out", skew)
+    roomy = torch.full((B * 4096 * 16,), float("nan"), dtype=torch.float32, device="cuda")
     mt = C.c_int(0)
-    bd = bias.cuda()
+    bd = gin(bias, skew)
+    # the partial table is [B][MT][8][2] with MT known only from a call: the first call learns it, the checked one gets exactly that
+    lib.check(lib.lib.lo_conv_forward_f8(kind, B, H, H, Cin, Cout, x8.data_ptr(), w8.data_ptr(), ws.data_ptr(), bd.data_ptr(), None,
+                                         out8.data_ptr(), roomy.data_ptr(), C.byref(mt), lib.stream_ptr()), "conv_f8 (MT)")
+    sync()
+    out8.fill_(float("nan"))
+    part = guarded(B * mt.value * 16, torch.float32, "out", skew)
+    mt0 = mt.value
     lib.check(lib.lib.lo_conv_forward_f8(kind, B, H, H, Cin, Cout, x8.data_ptr(), w8.data_ptr(), ws.data_ptr(), bd.data_ptr(), None,
                                          out8.data_ptr(), part.data_ptr(), C.byref(mt), lib.stream_ptr()), "conv_f8")
     sync()
+    assert mt.value == mt0
+    check_guards(xin, wp, wsrc, x8, w8, ws, out8, bd, part)
     # ---- the weight quantiser: every (phase, channel) row uses the full e4m3 range and stays within half an ulp (2^-4 relative)
     K = n // (nph * Cout)
     wq = _decode(w8).view(nph * Cout, K)
@@ -97,12 +122,13 @@ def test_fp8_conv_matches_fp16_kernel_on_dequantised_operands(kind, B, Cin, Cout
     deq = wq * scale[:, None]
     assert ((deq - wrow).abs() <= wrow.abs() * 2.0 ** -4 + scale[:, None] * 2.0 ** -10 + 1e-12).all()
     # ---- the conv: the fp16 kernel on the dequantised operands multiplies the same numbers
-    xdq = (_decode(x8) / ACT_SCALE).half().view_as(xin).cuda()                   # exact in fp16
-    wdq = deq.half().view(-1).cuda()
-    out16 = torch.full((B, Ho, Ho, Cout), float("nan"), dtype=torch.float16, device="cuda")
+    xdq = gin((_decode(x8) / ACT_SCALE).half().view_as(xin), skew)                     # exact in fp16
+    wdq = gin(deq.half().view(-1), skew)
+    out16 = guarded((B, Ho, Ho, Cout), torch.float16, "out", skew)
     lib.check(lib.lib.lo_conv_forward(kind, B, H, H, Cin, Cout, xdq.data_ptr(), wdq.data_ptr(), bd.data_ptr(), None, out16.data_ptr(),
                                       None, None, lib.stream_ptr()), "conv_f16")
     sync()
+    check_guards(xdq, wdq, out16, bd)
     got, ref = from_nhwc(out8), from_nhwc(out16)
     assert torch.isfinite(got).all()
     err = (got - ref).abs().max().item()
@@ -250,32 +276,40 @@ def test_teacher_fused_tap_conv_fp8_matches_fp16_kernel_on_dequantised_operands(
     """The teacher's 3x3 128->128 convolution kernel (lo_conv3x3_pp) on e4m3 operands against the SAME kernel in fp16 on the
     dequantised operands (same products; fp32 accumulation order differs), LeakyReLU + BatchNorm partial sums included, and the
     quantisation error against the fp32 convolution."""
+    _teacher_fused_tap(B, H)
+
+
+def _teacher_fused_tap(B, H, skew=0):
     lib = LIB()
     Cin = Cout = 128
     x = h16(F.leaky_relu(_rand(B, Cin, H, H, seed=11), 0.2))
     w = _rand(Cout, Cin, 3, 3, seed=12, scale=(Cin * 9) ** -0.5)
     bias = _rand(Cout, seed=13, scale=0.1)
     ref32 = F.leaky_relu(F.conv2d(x, w, bias, padding=1), 0.2)
-    xin = to_nhwc_h(x)
+    xin = to_nhwc_h(x, skew)
     n = lib.lib.lo_packed_weight_elems_for(KIND_S1, B, H, H, Cin, Cout)
-    wp = torch.empty(n, dtype=torch.float16, device="cuda")
-    lib.check(lib.lib.lo_pack_weight_for(KIND_S1, B, H, H, Cin, Cout, w.contiguous().cuda().data_ptr(), wp.data_ptr(), lib.stream_ptr()), "pack")
-    x8 = torch.empty(xin.numel(), dtype=torch.uint8, device="cuda")
-    w8 = torch.empty(n, dtype=torch.uint8, device="cuda")
-    ws = torch.full((Cout,), float("nan"), dtype=torch.float32, device="cuda")
+    wp = guarded(n, torch.float16, "out", skew)
+    wsrc = gin(w, skew)
+    lib.check(lib.lib.lo_pack_weight_for(KIND_S1, B, H, H, Cin, Cout, wsrc.data_ptr(), wp.data_ptr(), lib.stream_ptr()), "pack")
+    x8 = guarded(xin.numel(), torch.uint8, "out", skew)
+    w8 = guarded(n, torch.uint8, "out", skew)
+    ws = guarded(Cout, torch.float32, "out", skew)
     lib.check(lib.lib.lo_quantize_act_f8(xin.data_ptr(), x8.data_ptr(), xin.numel(), lib.stream_ptr()), "quantize")
     lib.check(lib.lib.lo_pack_weight_f8_for(KIND_S1, B, H, H, Cin, Cout, wp.data_ptr(), w8.data_ptr(), ws.data_ptr(), lib.stream_ptr()), "pack8")
     tiles = B * (H // 16) * (H // 16)
-    bd = bias.cuda()
+    bd = gin(bias, skew)
     outs, parts = {}, {}
-    xdq = (_decode(x8) / ACT_SCALE).half().view_as(xin).cuda()
-    wdq = (_decode(w8).view(Cout, -1) * (ws.cpu() * ACT_SCALE)[:, None]).half().view(-1).cuda()
+    sync()
+    check_guards(xin, wp, wsrc, x8, w8, ws)
+    xdq = gin((_decode(x8) / ACT_SCALE).half().view_as(xin), skew)
+    wdq = gin((_decode(w8).view(Cout, -1) * (ws.cpu() * ACT_SCALE)[:, None]).half().view(-1), skew)
     for tag, fp8, a_in, a_w in (("fp8", 1, x8, w8), ("fp16", 0, xdq, wdq)):
-        out = torch.full((B, H, H, Cout), float("nan"), dtype=torch.float16, device="cuda")
-        part = torch.full((tiles, Cout, 2), float("nan"), dtype=torch.float32, device="cuda")
+        out = guarded((B, H, H, Cout), torch.float16, "out", skew)
+        part = guarded((tiles, Cout, 2), torch.float32, "out", skew)     # the header's size: [B*(H/16)*(W/16)][Cout][2]
         lib.check(lib.lib.lo_conv3x3_fused_tap_forward(B, H, H, Cin, Cout, fp8, a_in.data_ptr(), a_w.data_ptr(), ws.data_ptr(), bd.data_ptr(), 1,
                                                        out.data_ptr(), part.data_ptr(), lib.stream_ptr()), "fused_tap " + tag)
         sync()
+        check_guards(a_in, a_w, ws, bd, out, part)
         outs[tag], parts[tag] = from_nhwc(out), part.cpu()
     got, ref = outs["fp8"], outs["fp16"]
     assert torch.isfinite(got).all()
@@ -322,3 +356,17 @@ def test_teacher_fp8_mode_matches_the_fp16_mode_on_the_same_dropout_masks():
     assert torch.equal(a(x.cuda())["quality_scores"], b(x.cuda())["quality_scores"])
     with pytest.raises(ValueError):
         LunarMoETeacher(mfma_precision="int4")
+
+
+# ---- one case of each op with every pointer at (a multiple of 256 B) + 16 B: the alignment include/lunaris_hip.h promises ----------
+def test_activation_quantiser_aligned16():
+    _activation_quantiser(skew=16)
+
+
+def test_fp8_conv_aligned16():
+    _fp8_conv(KIND_S1, 2, 128, 128, 32, skew=16)
+    _fp8_conv(KIND_T4, 2, 512, 256, 8, skew=16)
+
+
+def test_teacher_fused_tap_conv_fp8_aligned16():
+    _teacher_fused_tap(3, 32, skew=16)

@@ -84,14 +84,25 @@ def _assert_first_conv_identity(x, dx, w, dw):
 @pytest.mark.parametrize("stride,cout", [(1, 32), (2, 64)])
 @pytest.mark.parametrize("B", [1, 3, 64])
 def test_image_dgrad_kernel_matches_conv2d_input(stride, cout, B):
+    _image_dgrad_kernel(stride, cout, B)
+
+
+@pytest.mark.parametrize("stride,cout", [(1, 32), (2, 64)])
+def test_image_dgrad_kernel_aligned16(stride, cout):
+    """Every pointer at (a multiple of 256 B) + 16 B: the alignment include/lunaris_hip.h promises."""
+    _image_dgrad_kernel(stride, cout, 3, skew=16)
+
+
+def _image_dgrad_kernel(stride, cout, B, skew=0):
     from lunaris_orion_amd import _lib
+    from tests.guarded import check_guards, gin, guarded
     g = torch.Generator().manual_seed(1000 * stride + B)
     ho = 128 // stride
     dy = torch.randn(B, ho, ho, cout, generator=g).half()          # NHWC, the backward's fp16 layout
     w = torch.randn(cout, 3, 3, 3, generator=g) * 0.2
     scale = 2.0 ** -3
-    dyc, wc = dy.cuda(), w.cuda()
-    dx = torch.full((B, 3, 128, 128), float("nan"), device="cuda")   # every element must be written
+    dyc, wc = gin(dy, skew), gin(w, skew)                                       # guard-banded, exactly the header's sizes (tests/guarded.py)
+    dx = guarded((B, 3, 128, 128), torch.float32, "out", skew)            # pre-filled with NaN: every element must be written
     _lib.check(_lib.lib.lo_image_dgrad_op(dyc.data_ptr(), cout, stride, wc.data_ptr(), B, scale, dx.data_ptr(), _lib.stream_ptr()),
                "lo_image_dgrad_op")
     torch.cuda.synchronize()
@@ -104,10 +115,11 @@ def test_image_dgrad_kernel_matches_conv2d_input(stride, cout, B):
                  (got[:, :, :, -1], ref[:, :, :, -1]), (got[-1], ref[-1])):
         assert _rel(a, b) <= 1e-5, _rel(a, b)
     # deterministic: the same call again gives the same bits
-    dx2 = torch.empty_like(dx)
+    dx2 = guarded((B, 3, 128, 128), torch.float32, "out", skew)
     _lib.check(_lib.lib.lo_image_dgrad_op(dyc.data_ptr(), cout, stride, wc.data_ptr(), B, scale, dx2.data_ptr(), _lib.stream_ptr()),
                "lo_image_dgrad_op")
     assert torch.equal(dx, dx2)
+    check_guards(dyc, wc, dx, dx2)
 
 
 def test_image_dgrad_rejects_shapes_it_is_not_built_for():

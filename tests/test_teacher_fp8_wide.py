@@ -57,27 +57,30 @@ def _decode(u8):
 
 
 @functools.lru_cache(maxsize=None)
-def _op_case(B, H, Cin, Cout):
+def _op_case(B, H, Cin, Cout, skew=0):
     """Operands of one case, quantised once by the library, and the two references (computed once, on the device in fp32 with
     TF32 off): the fp32 conv of the DEQUANTISED operands + bias before the fp16 rounding, and the fp32 conv of the unquantised ones."""
-    from tests.hip_helpers import L, sync, to_nhwc_h
+    from tests.guarded import check_guards, gin, guarded
+    from tests.hip_helpers import L, sync
     lib = L()
     torch.backends.cudnn.allow_tf32 = False
     torch.backends.cuda.matmul.allow_tf32 = False
     x = F_.leaky_relu(_rand(B, Cin, H, H, seed=21), 0.2).half().float()
     w = _rand(Cout, Cin, 3, 3, seed=22, scale=(9 * Cin) ** -0.5)
     bias = _rand(Cout, seed=23, scale=0.1)
-    xin = to_nhwc_h(x)
+    xin = gin(x.permute(0, 2, 3, 1), skew, torch.float16)          # guard-banded buffers of the header's sizes (tests/guarded.py)
     n = lib.lib.lo_packed_weight_elems_for(0, B, H, H, Cin, Cout)
     assert n == Cout * 9 * Cin
-    wp = torch.empty(n, dtype=torch.float16, device="cuda")
-    lib.check(lib.lib.lo_pack_weight_for(0, B, H, H, Cin, Cout, w.contiguous().cuda().data_ptr(), wp.data_ptr(), lib.stream_ptr()), "pack")
-    x8 = torch.empty(xin.numel(), dtype=torch.uint8, device="cuda")
-    w8 = torch.empty(n, dtype=torch.uint8, device="cuda")
-    ws = torch.full((Cout,), float("nan"), dtype=torch.float32, device="cuda")
+    wp = guarded(n, torch.float16, "out", skew)
+    wsrc = gin(w, skew)
+    lib.check(lib.lib.lo_pack_weight_for(0, B, H, H, Cin, Cout, wsrc.data_ptr(), wp.data_ptr(), lib.stream_ptr()), "pack")
+    x8 = guarded(xin.numel(), torch.uint8, "out", skew)
+    w8 = guarded(n, torch.uint8, "out", skew)
+    ws = guarded(Cout, torch.float32, "out", skew)
     lib.check(lib.lib.lo_quantize_act_f8(xin.data_ptr(), x8.data_ptr(), xin.numel(), lib.stream_ptr()), "quantize")
     lib.check(lib.lib.lo_pack_weight_f8_for(0, B, H, H, Cin, Cout, wp.data_ptr(), w8.data_ptr(), ws.data_ptr(), lib.stream_ptr()), "pack8")
     sync()
+    check_guards(xin, wp, wsrc, x8, w8, ws)
     # dequantised operands, back in NCHW / OIHW: the packed layout of this kind is [Cout][tap][Cin]
     xdq = (_decode(x8) / ACT_SCALE).view(B, H, H, Cin).permute(0, 3, 1, 2).contiguous()
     wdq = (_decode(w8).view(Cout, 9 * Cin) * (ws.cpu() * ACT_SCALE)[:, None]).view(Cout, 3, 3, Cin).permute(0, 3, 1, 2).contiguous()
@@ -86,21 +89,23 @@ def _op_case(B, H, Cin, Cout):
     with torch.no_grad():
         pre_dq = (F_.conv2d(xdq.cuda(), wdq.cuda(), None, padding=1) + bias.cuda().view(1, -1, 1, 1)).cpu()
         pre_32 = (F_.conv2d(x.cuda(), w.cuda(), None, padding=1) + bias.cuda().view(1, -1, 1, 1)).cpu()
-    return {"x8": x8, "w8": w8, "ws": ws, "bias": bias.cuda(), "pre_dq": pre_dq, "pre_32": pre_32}
+    return {"x8": x8, "w8": w8, "ws": ws, "bias": gin(bias, skew), "pre_dq": pre_dq, "pre_32": pre_32}
 
 
-def _run_op(c, B, H, Cin, Cout, leaky, want_partial=True):
+def _run_op(c, B, H, Cin, Cout, leaky, want_partial=True, skew=0):
+    from tests.guarded import check_guards, guarded
     from tests.hip_helpers import L, from_nhwc, sync
     lib = L()
-    out = torch.full((B, H, H, Cout), float("nan"), dtype=torch.float16, device="cuda")
-    max_rows = B * H * H // 64
-    part = torch.full((max_rows, Cout, 2), float("nan"), dtype=torch.float32, device="cuda") if want_partial else None
+    out = guarded((B, H, H, Cout), torch.float16, "out", skew)
+    max_rows = B * H * H // 64                                   # the header's bound on the partial rows
+    part = guarded((max_rows, Cout, 2), torch.float32, "out", skew) if want_partial else None
     rows = C.c_int(-1)
     lib.check(lib.lib.lo_teacher_conv3x3_forward_f8(B, H, H, Cin, Cout, c["x8"].data_ptr(), c["w8"].data_ptr(), c["ws"].data_ptr(),
                                                     c["bias"].data_ptr(), leaky, out.data_ptr(), lib.ptr(part), C.byref(rows), lib.stream_ptr()),
               "lo_teacher_conv3x3_forward_f8")
     sync()
     assert 1 <= rows.value <= max_rows
+    check_guards(c["x8"], c["w8"], c["ws"], c["bias"], out, part)
     return from_nhwc(out), (part[: rows.value].cpu() if want_partial else None), rows.value
 
 
@@ -140,6 +145,21 @@ def test_wide_teacher_conv_fp8_matches_the_conv_of_the_dequantised_operands(B, H
     assert torch.allclose(part0.double().sum(dim=0)[:, 0], got0.double().sum(dim=(0, 2, 3)), rtol=1e-4, atol=1e-2)
     got1, _, _ = _run_op(c, B, H, Cin, Cout, 1, want_partial=False)
     assert torch.equal(got1, got)
+
+
+@pytest.mark.gpu
+def test_wide_teacher_conv_fp8_aligned16():
+    """One case with every pointer at (a multiple of 256 B) + 16 B, the alignment include/lunaris_hip.h promises: same reference,
+    same bounds."""
+    B, H, Cin, Cout = 3, 16, 512, 512
+    c = _op_case(B, H, Cin, Cout, 16)
+    ref = F_.leaky_relu(c["pre_dq"].half().float(), 0.2).half().float()
+    got, part, rows = _run_op(c, B, H, Cin, Cout, 1, skew=16)
+    assert torch.isfinite(got).all()
+    assert (got - ref).abs().max().item() <= 3e-3 * max(1.0, ref.abs().max().item())
+    tot = part.double().sum(dim=0)
+    assert torch.allclose(tot[:, 0], got.double().sum(dim=(0, 2, 3)), rtol=1e-4, atol=1e-2)
+    assert torch.allclose(tot[:, 1], (got.double() ** 2).sum(dim=(0, 2, 3)), rtol=1e-4, atol=1e-2)
 
 
 @pytest.mark.gpu
