@@ -1,6 +1,7 @@
 // C ABI (include/lunaris_hip.h): the single-op entry points.  The native VAE step executor is in lo_vae_*.hip.
 #include "lo_internal.h"
 #include "lo_conv.h"
+#include "lo_norm.h"
 #include "../../include/lunaris_hip.h"
 #include <stdio.h>
 #include <string.h>
@@ -109,14 +110,16 @@ extern "C" int lo_conv_wgrad(int kind, int B, int H, int W, int Cin, int Cout, c
 }
 extern "C" int lo_gn_mish_forward(const void* v, const float* gn_partial, int MT, const float* gamma, const float* beta,
                                   const void* other, void* y, float* stats, int B, int HW, int C, int mode, void* stream) {
-  return lo_gn_fwd((const f16*)v, gn_partial, MT, gamma, beta, (const f16*)other, (f16*)y, stats, B, HW, C, mode, S(stream));
+  return lo_gn_forward({(const f16*)v, stats, gamma, beta, B, HW, C},
+                       {.partial = gn_partial, .MT = MT, .other = (const f16*)other, .mode = mode, .y = (f16*)y}, S(stream));
 }
 extern "C" int lo_gn_nchunk_for(int HW, int C) { return lo_gn_nchunk(HW, C); }
 extern "C" int lo_gn_mish_backward(const void* dy, const void* v, const void* other, const float* stats, const float* gamma,
                                    const float* beta, void* ds, void* dv, float* P1, float* P2, float* dgamma, float* dbeta,
                                    float* dbias, int B, int HW, int C, int mode, float scale, void* stream) {
-  return lo_gn_bwd((const f16*)dy, (const f16*)v, (const f16*)other, stats, gamma, beta, (f16*)ds, (f16*)dv, P1, P2, dgamma,
-                   dbeta, dbias, B, HW, C, mode, scale, S(stream));
+  return lo_gn_bwd({(const f16*)v, stats, gamma, beta, B, HW, C},
+                   {.dy = (const f16*)dy, .other = (const f16*)other, .mode = mode, .ds = (f16*)ds, .dv = (f16*)dv, .P1 = P1, .P2 = P2},
+                   dgamma, dbeta, dbias, scale, S(stream));
 }
 extern "C" int lo_first_conv_forward(const float* x, const float* w, const float* bias, void* v, float* gn_partial, int B,
                                      void* stream) {

@@ -1,6 +1,7 @@
 // The convolution family (private to the library): geometry and weight packing (lo_conv_geom.hip), the implicit-GEMM kernel
 // (lo_igemm.hip), the fused-tap and patch-resident kernels (lo_conv3.hip), fp8 packing (lo_conv_f8.hip), the weight gradients
 // (lo_wgrad.hip, lo_wgrad3.hip, lo_wgrad2.hip) and the ONE place that decides which kernel runs an op (lo_conv_select.hip).
+// The GroupNorm + Mish passes between the convs have the same shape of header: lo_norm.h.
 #pragma once
 #include "lo_common.h"
 

@@ -2,7 +2,7 @@
 // with which tile and grid, and how many partial-sum rows its epilogue writes.  lo_conv_run / lo_conv_run_f8 launch what it says;
 // the planners and executors size their buffers and decide their fusions from the same answer, made with the use the later call has.
 #include "lo_conv.h"
-#include "lo_internal.h"
+#include "lo_norm.h"
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>

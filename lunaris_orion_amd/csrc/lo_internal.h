@@ -12,37 +12,6 @@ static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); 
 
 const char* lo_get_error();
 
-// lo_norm.hip
-int lo_gn_nchunk(int HW, int C);
-int lo_gn_fwd(const f16* v, const float* partial, int MT, const float* gamma, const float* beta, const f16* other, f16* y,
-              float* stats, int B, int HW, int C, int mode, hipStream_t st, uint8_t* y8 = nullptr);   // y8: e4m3 copy of y * LO_F8_ACT_SCALE
-int lo_gn_bwd(const f16* dy, const f16* v, const f16* other, const float* stats, const float* gamma, const float* beta,
-              f16* ds, f16* dv, float* P1, float* P2, float* dgamma, float* dbeta, float* dbias, int B, int HW, int C,
-              int mode, float scale, hipStream_t st);
-struct LoGnFinJob { const float* P1; const float* P2; float* dgamma; float* dbeta; float* dbias; int nblk1, nblk2, C, block0; };
-#define LO_GN_FIN_MAX 16
-struct LoGnFinJobs { LoGnFinJob j[LO_GN_FIN_MAX]; int n; };
-// np1 = 0: run the reduce pass here (P1 gets nchunk rows per sample); np1 > 0: P1 already holds np1 rows per sample
-// (written by the fused data-gradient epilogue) and only the apply pass runs
-int lo_gn_bwd_nofinal(const f16* dy, const f16* v, const f16* other, const float* stats, const float* gamma, const float* beta,
-                      f16* ds, f16* dv, float* P1, float* P2, int B, int HW, int C, int mode, hipStream_t st, int np1 = 0);
-int lo_gn_finalize_all(const LoGnFinJobs& jobs, float scale, hipStream_t st);
-// Split-K convolution outputs (fp32 slabs [nsplit][B*HW][C]) consumed by ONE (sample, group)-local pass each:
-//   forward:  v = fp16(bias + sum of the slabs), GroupNorm statistics of the group, y = GroupNorm + Mish (lo_gn_fwd's modes)
-//   backward: dy = fp16(sum of the slabs + add_src), then the one-pass GroupNorm backward of lo_gn_bwd_local (plain mode)
-int lo_splitk_gn_fwd(const float* slab, int nsplit, const float* bias, const float* gamma, const float* beta, const f16* other, f16* v,
-                     f16* y, float* stats, int B, int HW, int C, int mode, hipStream_t st);
-int lo_splitk_gn_bwd(const float* slab, int nsplit, const f16* add_src, const f16* v, const float* stats, const float* gamma,
-                     const float* beta, f16* dy_out, f16* dv, float* P1, float* P2, int B, int HW, int C, hipStream_t st);
-// reduce + apply in one pass where a (sample, group) fits a workgroup; ONE row of P1 / P2 per sample
-bool lo_gn_bwd_local_applies(int HW, int C);
-int lo_gn_bwd_local(const f16* dy, const f16* v, const f16* other, const float* stats, const float* gamma, const float* beta, f16* ds,
-                    f16* dv, float* P1, float* P2, int B, int HW, int C, int mode, hipStream_t st);
-int lo_nhwc_to_nchw_f16(const f16* src, f16* dst, int B, int HW, int C, hipStream_t st);
-int lo_nchw_to_nhwc_f16(const f16* src, f16* dst, int B, int HW, int C, hipStream_t st, uint8_t* dst8 = nullptr);
-int lo_nhwc_f16_to_nchw_f32(const f16* src, float* dst, int B, int HW, int C, float scale, hipStream_t st);   // module-boundary forms
-int lo_nchw_f32_to_nhwc_f16(const float* src, f16* dst, int B, int HW, int C, float scale, hipStream_t st);
-
 // lo_edge.hip
 int lo_first_conv_fwd(const float* x, const float* w, const float* bias, f16* v, float* gn_partial, int B, hipStream_t st);
 int lo_first_conv_wgrad(const float* x, const f16* dv, float* partial, float* dw, int B, float scale, hipStream_t st);

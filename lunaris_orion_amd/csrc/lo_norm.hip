@@ -6,8 +6,9 @@
 // Reference ops replaced: nn.GroupNorm(8, C) + nn.Mish (lunar_generate.py:37-38,42-43,96-97,103-104,110-111,
 // 117-118,170-171,176-177,182-183,188-189), the ResBlock tail mish(out + identity) (:49-53) and the decoder
 // skip additions (:212-222).
-#include "lo_internal.h"
+#include "lo_norm.h"
 #include <stdlib.h>
+#include <type_traits>
 
 #define GN_EPS 1e-5f
 
@@ -569,67 +570,6 @@ __global__ __launch_bounds__(256) void lo_transpose_tile_kernel(const f16* __res
 }
 
 // ---------------------------------------------------------------------------------------------
-// launchers
-// ---------------------------------------------------------------------------------------------
-// profiler name of a launch: the kernel name, or "<kernel> C<channels> HW<pixels> m<mode>" under LO_PROF_LAYERS
-static const char* gn_layer_name(const char* base, int C, int HW, int mode) {
-  if (!g_lo_prof_layers || !g_lo_prof_on) return base;
-  struct Entry { const char* base; int C, HW, mode; char text[56]; };
-  static Entry table[96];             // one stable string per distinct (kernel, shape, mode): the profiler keeps the pointer
-  static int used = 0;
-  for (int i = 0; i < used; ++i)
-    if (table[i].base == base && table[i].C == C && table[i].HW == HW && table[i].mode == mode) return table[i].text;
-  if (used == 96) return base;
-  Entry& e = table[used++];
-  e.base = base; e.C = C; e.HW = HW; e.mode = mode;
-  snprintf(e.text, sizeof(e.text), "%s C%d HW%d m%d", base, C, HW, mode);
-  return e.text;
-}
-int lo_gn_fwd(const f16* v, const float* partial, int MT, const float* gamma, const float* beta, const f16* other,
-              f16* y, float* stats, int B, int HW, int C, int mode, hipStream_t st, uint8_t* y8) {
-  LO_REQUIRE(C % 32 == 0 && C <= 512, "lo_gn_fwd: C=%d unsupported", C);
-  GnFwdArgs a{v, partial, gamma, beta, other, y, stats, HW, C, MT, lo_gn_nchunk(HW, C), mode, y8};
-  LoProfScope _p(gn_layer_name("lo_gn_fwd", C, HW, mode), 0, 2.0 * B * HW * C * (mode ? 3 : 2), st);
-  if (mode == GN_MODE_PLAIN) hipLaunchKernelGGL(lo_gn_fwd_kernel<GN_MODE_PLAIN>, dim3(a.nchunk, B), dim3(256), 0, st, a);
-  else if (mode == GN_MODE_SKIP) hipLaunchKernelGGL(lo_gn_fwd_kernel<GN_MODE_SKIP>, dim3(a.nchunk, B), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(lo_gn_fwd_kernel<GN_MODE_RES>, dim3(a.nchunk, B), dim3(256), 0, st, a);
-  LO_LAUNCH_CHECK("gn_fwd");
-  return LO_OK;
-}
-
-int lo_gn_bwd_nofinal(const f16* dy, const f16* v, const f16* other, const float* stats, const float* gamma, const float* beta,
-                      f16* ds, f16* dv, float* P1, float* P2, int B, int HW, int C, int mode, hipStream_t st, int np1) {
-  LO_REQUIRE(C % 32 == 0 && C <= 512, "lo_gn_bwd: C=%d unsupported", C);
-  GnBwdArgs a{dy, v, other, stats, gamma, beta, ds, dv, P1, P2, HW, C, lo_gn_nchunk(HW, C), mode, 0};
-  a.np1 = np1 > 0 ? np1 : a.nchunk;
-  if (np1 == 0) {
-    LoProfScope _p(gn_layer_name("lo_gn_bwd_reduce", C, HW, mode), 0, 2.0 * B * HW * C * (mode == 2 ? 4 : 2), st);
-    const bool g4 = C == 32;
-    if (mode == GN_MODE_RES) {
-      if (g4) hipLaunchKernelGGL((lo_gn_bwd_reduce_kernel<true, true>), dim3(a.nchunk, B), dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((lo_gn_bwd_reduce_kernel<true, false>), dim3(a.nchunk, B), dim3(256), 0, st, a);
-    } else {
-      if (g4) hipLaunchKernelGGL((lo_gn_bwd_reduce_kernel<false, true>), dim3(a.nchunk, B), dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((lo_gn_bwd_reduce_kernel<false, false>), dim3(a.nchunk, B), dim3(256), 0, st, a);
-    }
-  }
-  LO_LAUNCH_CHECK("gn_bwd_reduce");
-  {
-    LoProfScope _p(gn_layer_name("lo_gn_bwd_apply", C, HW, mode), 0, 2.0 * B * HW * C * (mode == 2 ? 4 : 3), st);
-    const bool g4 = C == 32;
-    if (mode == GN_MODE_RES) {
-      if (g4) LO_LAUNCH_STOP((lo_gn_bwd_apply_kernel<true, true>), dim3(a.nchunk, B), dim3(256), 0, st, a);
-      else LO_LAUNCH_STOP((lo_gn_bwd_apply_kernel<true, false>), dim3(a.nchunk, B), dim3(256), 0, st, a);
-    } else {
-      if (g4) LO_LAUNCH_STOP((lo_gn_bwd_apply_kernel<false, true>), dim3(a.nchunk, B), dim3(256), 0, st, a);
-      else LO_LAUNCH_STOP((lo_gn_bwd_apply_kernel<false, false>), dim3(a.nchunk, B), dim3(256), 0, st, a);
-    }
-  }
-  LO_LAUNCH_CHECK("gn_bwd_apply");
-  return LO_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
 // Forward counterpart for split-K convolutions: one workgroup per (sample, group) sums the K-split slabs of its 8-channel chunks,
 // adds the bias, rounds to fp16 (v, stored: the backward needs it), takes the group's mean / rstd over those fp16 values (fixed-order
 // sums, double at the end like lo_gn_group_stats) and applies GroupNorm + Mish (lo_gn_apply8: the modes of lo_gn_fwd).
@@ -701,64 +641,144 @@ __global__ __launch_bounds__(256) void lo_splitk_gn_fwd_kernel(SplitkGnFwdArgs a
     }
   }
 }
-int lo_splitk_gn_fwd(const float* slab, int nsplit, const float* bias, const float* gamma, const float* beta, const f16* other, f16* v,
-                     f16* y, float* stats, int B, int HW, int C, int mode, hipStream_t st) {
-  LO_REQUIRE(lo_gn_bwd_local_applies(HW, C) && slab && bias && v && y && stats && nsplit >= 1 && (mode == 0 || other),
-             "lo_splitk_gn_fwd: bad arguments (HW=%d, C=%d)", HW, C);
-  SplitkGnFwdArgs a{slab, nsplit, (size_t)B * HW * C, bias, gamma, beta, other, v, y, stats, HW, C, mode};
-  const int E = HW / (256 / ((C >> 3) >> 3));
-  LoProfScope _p(gn_layer_name("lo_splitk_gn_fwd", C, HW, mode), 0, (double)B * HW * C * (4.0 * nsplit + 4.0 + (mode ? 2.0 : 0.0)), st);
-  const dim3 grid(8, B);
-  if (E <= 1) hipLaunchKernelGGL((lo_splitk_gn_fwd_kernel<1>), grid, dim3(256), 0, st, a);
-  else if (E == 2) hipLaunchKernelGGL((lo_splitk_gn_fwd_kernel<2>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((lo_splitk_gn_fwd_kernel<4>), grid, dim3(256), 0, st, a);
-  LO_LAUNCH_CHECK("splitk_gn_fwd");
-  return LO_OK;
+// ---------------------------------------------------------------------------------------------
+// launchers
+// ---------------------------------------------------------------------------------------------
+// profiler name of a launch: the kernel name, or "<kernel> C<channels> HW<pixels> m<mode>" under LO_PROF_LAYERS
+static const char* gn_layer_name(const char* base, int C, int HW, int mode) {
+  if (!g_lo_prof_layers || !g_lo_prof_on) return base;
+  struct Entry { const char* base; int C, HW, mode; char text[56]; };
+  static Entry table[96];             // one stable string per distinct (kernel, shape, mode): the profiler keeps the pointer
+  static int used = 0;
+  for (int i = 0; i < used; ++i)
+    if (table[i].base == base && table[i].C == C && table[i].HW == HW && table[i].mode == mode) return table[i].text;
+  if (used == 96) return base;
+  Entry& e = table[used++];
+  e.base = base; e.C = C; e.HW = HW; e.mode = mode;
+  snprintf(e.text, sizeof(e.text), "%s C%d HW%d m%d", base, C, HW, mode);
+  return e.text;
 }
-int lo_splitk_gn_bwd(const float* slab, int nsplit, const f16* add_src, const f16* v, const float* stats, const float* gamma,
-                     const float* beta, f16* dy_out, f16* dv, float* P1, float* P2, int B, int HW, int C, hipStream_t st) {
-  LO_REQUIRE(lo_gn_bwd_local_applies(HW, C) && slab && v && stats && dv && P1 && P2 && nsplit >= 1, "lo_splitk_gn_bwd: bad arguments (HW=%d, C=%d)", HW, C);
-  GnBwdArgs a{nullptr, v, nullptr, stats, gamma, beta, nullptr, dv, P1, P2, HW, C, 1, GN_MODE_PLAIN, 1};
-  const GnSlabSrc ss{slab, nsplit, add_src, dy_out, (size_t)B * HW * C};
+
+// One dispatch per kernel template.  The (RES, G4) and rows-per-thread (E) ladders, written once: fn gets the template arguments as
+// integral constants.
+template <bool V> using GnBool = std::integral_constant<bool, V>;
+template <typename F>
+static inline void gn_pick_res_g4(int mode, int C, F&& fn) {
+  const bool g4 = C == 32;
+  if (mode == GN_MODE_RES) { if (g4) fn(GnBool<true>{}, GnBool<true>{}); else fn(GnBool<true>{}, GnBool<false>{}); }
+  else { if (g4) fn(GnBool<false>{}, GnBool<true>{}); else fn(GnBool<false>{}, GnBool<false>{}); }
+}
+template <typename F>
+static inline void gn_pick_e(int HW, int C, F&& fn) {      // (sample, group)-local kernels: E = pixel rows per thread
   const int E = HW / (256 / ((C >> 3) >> 3));
-  LoProfScope _p(gn_layer_name("lo_splitk_gn_bwd", C, HW, 0), 0, (double)B * HW * C * (4.0 * nsplit + 4.0 + (add_src ? 2.0 : 0.0)), st);
-  const dim3 grid(8, B);
-  if (E <= 1) LO_LAUNCH_STOP((lo_gn_bwd_local_kernel<false, 1, true>), grid, dim3(256), 0, st, a, ss);
-  else if (E == 2) LO_LAUNCH_STOP((lo_gn_bwd_local_kernel<false, 2, true>), grid, dim3(256), 0, st, a, ss);
-  else LO_LAUNCH_STOP((lo_gn_bwd_local_kernel<false, 4, true>), grid, dim3(256), 0, st, a, ss);
-  LO_LAUNCH_CHECK("splitk_gn_bwd");
+  if (E <= 1) fn(std::integral_constant<int, 1>{});
+  else if (E == 2) fn(std::integral_constant<int, 2>{});
+  else fn(std::integral_constant<int, 4>{});
+}
+static void gn_launch_fwd(const GnFwdArgs& a, int B, hipStream_t st) {
+  if (a.mode == GN_MODE_PLAIN) hipLaunchKernelGGL(lo_gn_fwd_kernel<GN_MODE_PLAIN>, dim3(a.nchunk, B), dim3(256), 0, st, a);
+  else if (a.mode == GN_MODE_SKIP) hipLaunchKernelGGL(lo_gn_fwd_kernel<GN_MODE_SKIP>, dim3(a.nchunk, B), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(lo_gn_fwd_kernel<GN_MODE_RES>, dim3(a.nchunk, B), dim3(256), 0, st, a);
+}
+static void gn_launch_reduce(const GnBwdArgs& a, int B, hipStream_t st) {
+  gn_pick_res_g4(a.mode, a.C, [&](auto res, auto g4) {
+    hipLaunchKernelGGL((lo_gn_bwd_reduce_kernel<res(), g4()>), dim3(a.nchunk, B), dim3(256), 0, st, a);
+  });
+}
+static void gn_launch_apply(const GnBwdArgs& a, int B, hipStream_t st) {
+  gn_pick_res_g4(a.mode, a.C, [&](auto res, auto g4) {
+    LO_LAUNCH_STOP((lo_gn_bwd_apply_kernel<res(), g4()>), dim3(a.nchunk, B), dim3(256), 0, st, a);
+  });
+}
+static void gn_launch_splitk_fwd(const SplitkGnFwdArgs& a, int B, hipStream_t st) {
+  gn_pick_e(a.HW, a.C, [&](auto e) { hipLaunchKernelGGL((lo_splitk_gn_fwd_kernel<e()>), dim3(8, B), dim3(256), 0, st, a); });
+}
+static void gn_launch_local(const GnBwdArgs& a, const GnSlabSrc& ss, int B, hipStream_t st) {
+  gn_pick_e(a.HW, a.C, [&](auto e) {
+    if (ss.slab) LO_LAUNCH_STOP((lo_gn_bwd_local_kernel<false, e(), true>), dim3(8, B), dim3(256), 0, st, a, ss);
+    else if (a.mode == GN_MODE_RES) LO_LAUNCH_STOP((lo_gn_bwd_local_kernel<true, e()>), dim3(8, B), dim3(256), 0, st, a, ss);
+    else LO_LAUNCH_STOP((lo_gn_bwd_local_kernel<false, e()>), dim3(8, B), dim3(256), 0, st, a, ss);
+  });
+}
+
+int lo_gn_forward(const LoGnLayer& l, const LoGnFwd& op, hipStream_t st) {
+  const int B = l.B, HW = l.HW, C = l.C, mode = op.mode;
+  f16* v = const_cast<f16*>(l.v);               // the forward is what writes the layer's statistics (and, from slabs, v)
+  float* stats = const_cast<float*>(l.stats);
+  if (op.slab) {
+    LO_REQUIRE(lo_gn_bwd_local_applies(HW, C) && op.bias && v && op.y && stats && op.nsplit >= 1 && (mode == 0 || op.other) && !op.y8,
+               "lo_splitk_gn_fwd: bad arguments (HW=%d, C=%d)", HW, C);
+    SplitkGnFwdArgs a{op.slab, op.nsplit, (size_t)B * HW * C, op.bias, l.gamma, l.beta, op.other, v, op.y, stats, HW, C, mode};
+    LoProfScope _p(gn_layer_name("lo_splitk_gn_fwd", C, HW, mode), 0, (double)B * HW * C * (4.0 * op.nsplit + 4.0 + (mode ? 2.0 : 0.0)), st);
+    gn_launch_splitk_fwd(a, B, st);
+    LO_LAUNCH_CHECK("splitk_gn_fwd");
+    return LO_OK;
+  }
+  LO_REQUIRE(C % 32 == 0 && C <= 512, "lo_gn_fwd: C=%d unsupported", C);
+  GnFwdArgs a{l.v, op.partial, l.gamma, l.beta, op.other, op.y, stats, HW, C, op.MT, lo_gn_nchunk(HW, C), mode, op.y8};
+  LoProfScope _p(gn_layer_name("lo_gn_fwd", C, HW, mode), 0, 2.0 * B * HW * C * (mode ? 3 : 2), st);
+  gn_launch_fwd(a, B, st);
+  LO_LAUNCH_CHECK("gn_fwd");
   return LO_OK;
 }
 
-// the one-pass (sample, group)-local form: P1 / P2 get ONE row per sample
+// the one-pass (sample, group)-local forms: P1 / P2 get ONE row per sample
 bool lo_gn_bwd_local_applies(int HW, int C) {
   const int G = C >> 3;
   return C % 64 == 0 && G <= 64 && (long)HW * G <= 8192 && HW % (256 / (G >> 3)) == 0 && HW / (256 / (G >> 3)) <= 4;
 }
-int lo_gn_bwd_local(const f16* dy, const f16* v, const f16* other, const float* stats, const float* gamma, const float* beta, f16* ds,
-                    f16* dv, float* P1, float* P2, int B, int HW, int C, int mode, hipStream_t st) {
-  LO_REQUIRE(lo_gn_bwd_local_applies(HW, C), "lo_gn_bwd_local: HW=%d, C=%d does not fit one workgroup per (sample, group)", HW, C);
-  GnBwdArgs a{dy, v, other, stats, gamma, beta, ds, dv, P1, P2, HW, C, 1, mode, 1};
-  const int E = HW / (256 / ((C >> 3) >> 3));
-  LoProfScope _p(gn_layer_name("lo_gn_bwd_local", C, HW, mode), 0, 2.0 * B * HW * C * (mode == 2 ? 5 : 3), st);
-  const dim3 grid(8, B);
-  const GnSlabSrc ss{nullptr, 0, nullptr, nullptr, 0};
-#define LO_GNL(RES_, E_) LO_LAUNCH_STOP((lo_gn_bwd_local_kernel<RES_, E_>), grid, dim3(256), 0, st, a, ss)
-  if (mode == GN_MODE_RES) { if (E <= 1) LO_GNL(true, 1); else if (E == 2) LO_GNL(true, 2); else LO_GNL(true, 4); }
-  else { if (E <= 1) LO_GNL(false, 1); else if (E == 2) LO_GNL(false, 2); else LO_GNL(false, 4); }
-#undef LO_GNL
-  LO_LAUNCH_CHECK("gn_bwd_local");
+
+// THE decision: which backward form serves (layer shape, use) and the P1 / P2 rows per sample it leaves
+LoGnChoice lo_gn_bwd_choose(int HW, int C, const LoGnUse& use) {
+  const int nchunk = lo_gn_nchunk(HW, C);
+  if (use.slab && lo_gn_bwd_local_applies(HW, C)) return {LO_GNB_SLAB_LOCAL, {1, 1}};
+  if (use.rows_in_P1 > 0) return {LO_GNB_APPLY_ONLY, {use.rows_in_P1, nchunk}};
+  if (use.allow_local && lo_gn_bwd_local_applies(HW, C)) return {LO_GNB_LOCAL, {1, 1}};
+  return {LO_GNB_TWO_PASS, {nchunk, nchunk}};
+}
+
+int lo_gn_backward(const LoGnLayer& l, const LoGnBwd& op, hipStream_t st, LoGnRows* rows) {
+  const int B = l.B, HW = l.HW, C = l.C, mode = op.mode;
+  const LoGnChoice ch = lo_gn_bwd_choose(HW, C, lo_gn_use(op));
+  if (rows) *rows = ch.rows;
+  // GnBwdArgs::nchunk / np1 are the rows of P2 / P1 in every form (the grid's chunk count, or 1 for the local forms)
+  GnBwdArgs a{op.dy, l.v, op.other, l.stats, l.gamma, l.beta, op.ds, op.dv, op.P1, op.P2, HW, C, ch.rows.p2, mode, ch.rows.p1};
+  if (op.slab) {
+    LO_REQUIRE(ch.form == LO_GNB_SLAB_LOCAL && mode == GN_MODE_PLAIN && !op.dy && !op.other && !op.ds && l.v && l.stats && op.dv && op.P1 &&
+               op.P2 && op.nsplit >= 1, "lo_splitk_gn_bwd: bad arguments (HW=%d, C=%d)", HW, C);
+    const GnSlabSrc ss{op.slab, op.nsplit, op.add_src, op.dy_out, (size_t)B * HW * C};
+    LoProfScope _p(gn_layer_name("lo_splitk_gn_bwd", C, HW, 0), 0, (double)B * HW * C * (4.0 * op.nsplit + 4.0 + (op.add_src ? 2.0 : 0.0)), st);
+    gn_launch_local(a, ss, B, st);
+    LO_LAUNCH_CHECK("splitk_gn_bwd");
+    return LO_OK;
+  }
+  if (ch.form == LO_GNB_LOCAL) {
+    LoProfScope _p(gn_layer_name("lo_gn_bwd_local", C, HW, mode), 0, 2.0 * B * HW * C * (mode == 2 ? 5 : 3), st);
+    gn_launch_local(a, GnSlabSrc{nullptr, 0, nullptr, nullptr, 0}, B, st);
+    LO_LAUNCH_CHECK("gn_bwd_local");
+    return LO_OK;
+  }
+  LO_REQUIRE(C % 32 == 0 && C <= 512, "lo_gn_bwd: C=%d unsupported", C);
+  if (ch.form == LO_GNB_TWO_PASS) {
+    LoProfScope _p(gn_layer_name("lo_gn_bwd_reduce", C, HW, mode), 0, 2.0 * B * HW * C * (mode == 2 ? 4 : 2), st);
+    gn_launch_reduce(a, B, st);
+  }
+  LO_LAUNCH_CHECK("gn_bwd_reduce");
+  {
+    LoProfScope _p(gn_layer_name("lo_gn_bwd_apply", C, HW, mode), 0, 2.0 * B * HW * C * (mode == 2 ? 4 : 3), st);
+    gn_launch_apply(a, B, st);
+  }
+  LO_LAUNCH_CHECK("gn_bwd_apply");
   return LO_OK;
 }
 
-int lo_gn_bwd(const f16* dy, const f16* v, const f16* other, const float* stats, const float* gamma, const float* beta,
-              f16* ds, f16* dv, float* P1, float* P2, float* dgamma, float* dbeta, float* dbias, int B, int HW, int C,
-              int mode, float scale, hipStream_t st) {
-  int r = lo_gn_bwd_nofinal(dy, v, other, stats, gamma, beta, ds, dv, P1, P2, B, HW, C, mode, st, 0);
+int lo_gn_bwd(const LoGnLayer& l, const LoGnBwd& op, float* dgamma, float* dbeta, float* dbias, float scale, hipStream_t st) {
+  LoGnRows rows;
+  int r = lo_gn_backward(l, op, st, &rows);
   if (r != LO_OK) return r;
   LoProfScope _p3("lo_gn_param_finalize", 0, 0, st);
-  hipLaunchKernelGGL(lo_gn_param_finalize_kernel, dim3((C + 15) / 16), dim3(256), 0, st, P1, P2, dgamma, dbeta, dbias,
-                     B * lo_gn_nchunk(HW, C), C, scale);
+  hipLaunchKernelGGL(lo_gn_param_finalize_kernel, dim3((l.C + 15) / 16), dim3(256), 0, st, op.P1, op.P2, dgamma, dbeta, dbias,
+                     l.B * rows.p1, l.C, scale);
   LO_LAUNCH_CHECK("gn_param_finalize");
   return LO_OK;
 }

@@ -2,11 +2,11 @@
 // SURVEY §3.4, §8 row A12) -- fp16 NHWC activations, fp32 BatchNorm statistics -- and its backward.
 //   lo_teacher_plan.hip       state table, parameter offsets, workspace plan, create / destroy, queries, pack
 //   lo_teacher_kernels.hip    kernels every path shares (first conv, BatchNorm finalize / apply, depthwise convs, the generic
-//                             attention, dropout glue) behind host launchers
+//                             attention, dropout glue) behind host launchers; the BatchNorm ones take an op struct (TBnFinalize, TBnApply)
 //   lo_teacher_f128.hip       feature_dim 128: the sparse / dense / dropout forms of an ExpertBlock and their kernels
 //   lo_teacher_heads.hip      gate / quality / semantic / embedding heads, their backward, reward bookkeeping
 //   lo_teacher_forward.hip    feature extractor forward, plain ExpertBlock forward, lo_teacher_forward
-//   lo_teacher_bwd_block.hip  full backward: BatchNorm and ExpertBlock backward
+//   lo_teacher_bwd_block.hip  full backward: BatchNorm (op struct TbBnBwd) and ExpertBlock backward
 //   lo_teacher_bwd.hip        full backward: plan, feature extractor backward, executor, clip + AdamW
 // There is no relocatable device code: a kernel is launched only from the unit that defines it; the ones other units need sit
 // behind a one-line host launcher, which is also where feature_dim picks the template argument.
@@ -117,13 +117,23 @@ struct LoTeacher {
 };
 
 // ---- lo_teacher_kernels.hip ---------------------------------------------------------------------------------------------------------
-// BatchNorm finalize of partial rows into (scale, shift): the shared slot o_ss, or ss_dst; mr: (mean, rstd) kept for the backward.
-// training: 1 batch statistics + running-statistics update, 2 batch statistics only, 0 running statistics
-int t_bn_finalize(LoTeacher* h, const float* partial, int nrow, int C, const TBnOff& bn, float* P, void* ws, int training, hipStream_t st,
-                  int tps = 1, int vtps = 1, const float* cvec = nullptr, float* ss_dst = nullptr, float* mr = nullptr);
-int t_bn_apply(LoTeacher* h, const f16* raw, const float* ls, const f16* identity, f16* y, int C, int dst_pitch, int dst_off, int mode,
-               float* pool_partial, void* ws, hipStream_t st, const float* cvec = nullptr, bool per_sample = false, uint8_t* y8 = nullptr,
-               const float* id_ss = nullptr);
+// BatchNorm finalize of `nrow` partial rows into (scale, shift): the shared slot o_ss, or ss_dst; mr: (mean, rstd) kept for the backward.
+// training: 1 batch statistics + running-statistics update, 2 batch statistics only, 0 running statistics.  tps / vtps / cvec: the
+// sparse path's compact rows (tiles per sample, of which valid; the constant vectors that stand for the rest)
+struct TBnFinalize {
+  const float* partial; int nrow, C; const TBnOff& bn; int training;
+  int tps = 1, vtps = 1; const float* cvec = nullptr; float* ss_dst = nullptr; float* mr = nullptr;
+};
+int t_bn_finalize(LoTeacher* h, float* P, void* ws, const TBnFinalize& op, hipStream_t st);
+// BatchNorm apply from the (scale, shift) of the last finalize (per_sample: the Dropout2d table o_ssb), BnApplyArgs::mode:
+enum TBnMode { T_BN_PLAIN = 0, T_BN_TAIL = 1, T_BN_TAIL_SPARSE = 2 };   // y = BN(raw); ExpertBlock tail; the tail on the sparse raw tensor + cvec
+struct TBnApply {
+  const f16* raw; const float* ls = nullptr; const f16* identity = nullptr; f16* y = nullptr; int C;
+  int dst_pitch = C, dst_off = 0;      // y has dst_pitch channels per pixel and gets its C from channel dst_off
+  int mode = T_BN_PLAIN; float* pool_partial = nullptr; const float* cvec = nullptr; bool per_sample = false;
+  uint8_t* y8 = nullptr; const float* id_ss = nullptr;       // e4m3 copy of y; (scale, shift) of a BatchNorm on the identity branch
+};
+int t_bn_apply(LoTeacher* h, void* ws, const TBnApply& op, hipStream_t st);
 int t_pool_finalize(const float* partial, float* pooled, int nblk, int C, int total, hipStream_t st);
 int t_pool(LoTeacher* h, float* pooled, int C, void* ws, hipStream_t st);      // from the pool partials of the last t_bn_apply (o_poolp)
 int t_conv1(const float* x, const float* w, const float* bias, f16* out, float* bn_partial, int B, hipStream_t st);
@@ -200,10 +210,18 @@ struct TbCtx {
   LoDropCfg d; float gscale, inv_g;
   LoGeom d1a, d1b, dq, dpc, dsc;          // data gradients of a block's conv 128->F, conv F->F, qkv, proj on the compact rows, shortcut
 };
-// BatchNorm backward of one layer: upstream din -> gradient wrt the conv output (out), parameter gradients into G
-int tb_bn_backward(TbCtx& c, const f16* din, int din_pitch, int din_off, const f16* raw, int raw_pitch, int raw_off, const float* mr,
-                   const TBnOff& bn, const float* ls, float* dls, f16* out, int out_pitch, int out_off, int C, int act, int dmode,
-                   uint32_t site, int didx_pitch, int didx_off, float* dbias = nullptr);
+// BatchNorm backward of one layer: upstream din -> gradient wrt the conv output (out), parameter gradients into G (dbias: the bias
+// gradient of the conv in front).  A view = C channels of a [pix][pitch] tensor from channel `off`
+struct TbView { const f16* p; int pitch, off = 0; };
+struct TbViewOut { f16* p; int pitch, off = 0; };
+enum TbAct { TB_ACT_NONE = 0, TB_ACT_LRELU = 1 };                          // TbBnArgs::act: the stored tensor is LeakyReLU(conv)
+enum TbDropMode { TB_DROP_NONE = 0, TB_DROP_2D = 1, TB_DROP_ELEM = 2 };    // TbBnArgs::dmode: Dropout2d (index b*C + c), Dropout (pix*idx_pitch + idx_off + c)
+struct TbDrop { int mode = TB_DROP_NONE; uint32_t site = 0; int idx_pitch = 0, idx_off = 0; };   // behind the BatchNorm; off when the call has no dropout
+struct TbBnBwd {
+  TbView din, raw; const float* mr; const TBnOff& bn; const float* ls = nullptr; float* dls = nullptr;
+  TbViewOut out; int C; int act = TB_ACT_NONE; TbDrop drop = {}; float* dbias = nullptr;
+};
+int tb_bn_backward(TbCtx& c, const TbBnBwd& op);
 // backward of ExpertBlock (e, l): scratch holds its recomputation; y = the block output, dy / dpool = its gradient.
 // dx_out = gradient wrt the block input (conv1's data gradient + the identity branch's)
 int tb_block_backward(TbCtx& c, int e, int l, const f16* xin, const f16* y, const f16* dy, const float* dpool, f16* dx_out);

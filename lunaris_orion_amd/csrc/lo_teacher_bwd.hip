@@ -317,8 +317,8 @@ static int tb_fe_backward(TbCtx& c, const float* x, float* dx) {
   const int B = h->B;
   const size_t px = (size_t)B * T_HW;
   f16* dcf = TB(f16, c.pl.o_dA);                   // gradient wrt the fusion conv's output [pix][128]
-  LO_TRYT(tb_bn_backward(c, TB(f16, c.pl.o_dfeat), 128, 0, TB(f16, c.pl.o_rawF), 128, 0, TB(float, c.pl.o_mr[7]), fe.bn_fus, nullptr, nullptr,
-                         dcf, 128, 0, 128, 1, 0, 0, 0, 0, TG(fe.fus_b)));
+  LO_TRYT(tb_bn_backward(c, {.din = {TB(f16, c.pl.o_dfeat), 128}, .raw = {TB(f16, c.pl.o_rawF), 128}, .mr = TB(float, c.pl.o_mr[7]),
+                             .bn = fe.bn_fus, .out = {dcf, 128}, .C = 128, .act = TB_ACT_LRELU, .dbias = TG(fe.fus_b)}));
   // fusion conv 192 -> 128 as three 64-channel slices (the GEMM kernels want power-of-two channel counts)
   LoGeom g64, d64;
   LO_TRYT(lo_make_geom(&g64, LO_LINEAR, B, 128, 128, 64, 128));
@@ -344,8 +344,9 @@ static int tb_fe_backward(TbCtx& c, const float* x, float* dx) {
     const TBranchOff& br = fe.br[b];
     const int K = b == 1 ? 5 : 3;
     // Dropout (element index pix * 192 + 64 b + c), BatchNorm of the branch, LeakyReLU
-    LO_TRYT(tb_bn_backward(c, TB(f16, c.pl.o_dcat), 192, 64 * b, TB(f16, c.pl.o_cat), 192, 64 * b, TB(float, c.pl.o_mr[4 + b]), br.bn, nullptr, nullptr,
-                           dpw, 64, 0, 64, 1, 2, LO_DS_FE, 192, 64 * b, TG(br.pw_b)));
+    LO_TRYT(tb_bn_backward(c, {.din = {TB(f16, c.pl.o_dcat), 192, 64 * b}, .raw = {TB(f16, c.pl.o_cat), 192, 64 * b},
+                               .mr = TB(float, c.pl.o_mr[4 + b]), .bn = br.bn, .out = {dpw, 64}, .C = 64, .act = TB_ACT_LRELU,
+                               .drop = {TB_DROP_ELEM, LO_DS_FE, 192, 64 * b}, .dbias = TG(br.pw_b)}));
     hipLaunchKernelGGL(lo_tb_pw_wgrad_kernel, dim3((unsigned)(px / 1024)), dim3(256), 0, st, dpw, 64, 0, TB(f16, c.pl.o_dwb[b]), TB(float, c.pl.o_part));
     LO_LAUNCH_CHECK("tb_pw_wgrad");
     LO_TRYT(lo_colsum(TB(float, c.pl.o_part), TG(br.pw_w), (int)(px / 1024), 2048, 2048, c.inv_g, st));
@@ -365,7 +366,8 @@ static int tb_fe_backward(TbCtx& c, const float* x, float* dx) {
     LO_TRYT(lo_colsum(TB(float, c.pl.o_bpart), TG(br.dw_b), B * 128, 32, 32, c.inv_g, st));
   }
   // BatchNorm + LeakyReLU of conv1, then its weight gradient and -- for a caller whose images require grad -- its data gradient
-  LO_TRYT(tb_bn_backward(c, dn0, 32, 0, TB(f16, c.pl.o_raw32), 32, 0, TB(float, c.pl.o_mr[3]), fe.bn1, nullptr, nullptr, ddw, 32, 0, 32, 1, 0, 0, 0, 0));
+  LO_TRYT(tb_bn_backward(c, {.din = {dn0, 32}, .raw = {TB(f16, c.pl.o_raw32), 32}, .mr = TB(float, c.pl.o_mr[3]), .bn = fe.bn1,
+                             .out = {ddw, 32}, .C = 32, .act = TB_ACT_LRELU}));
   hipLaunchKernelGGL(lo_tb_conv1_wgrad_kernel, dim3(128, B), dim3(256), 0, st, x, ddw, TB(float, c.pl.o_part), TB(float, c.pl.o_bpart));
   LO_LAUNCH_CHECK("tb_conv1_wgrad");
   LO_TRYT(lo_colsum(TB(float, c.pl.o_part), TG(fe.conv1_w), B * 128, 864, 864, c.inv_g, st));

@@ -333,18 +333,19 @@ __global__ __launch_bounds__(256) void lo_tb_colsum_kernel(const f16* __restrict
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-int tb_bn_backward(TbCtx& c, const f16* din, int din_pitch, int din_off, const f16* raw, int raw_pitch, int raw_off, const float* mr,
-                   const TBnOff& bn, const float* ls, float* dls, f16* out, int out_pitch, int out_off, int C, int act, int dmode,
-                   uint32_t site, int didx_pitch, int didx_off, float* dbias) {
+int tb_bn_backward(TbCtx& c, const TbBnBwd& op) {
   LoTeacher* h = c.h; float* P = c.P; float* G = c.G; void* bws = c.bws;
+  const TBnOff& bn = op.bn;
+  const float* ls = op.ls; float* dls = op.dls; float* dbias = op.dbias;
+  const int C = op.C;
   TbBnArgs a;
   memset(&a, 0, sizeof(a));
-  a.din = din; a.din_pitch = din_pitch; a.din_off = din_off; a.raw = raw; a.raw_pitch = raw_pitch; a.raw_off = raw_off; a.mr = mr;
-  a.gamma = TP(bn.weight); a.ls = ls; a.coef = TB(float, c.pl.o_coef); a.partial = TB(float, c.pl.o_part);
+  a.din = op.din.p; a.din_pitch = op.din.pitch; a.din_off = op.din.off; a.raw = op.raw.p; a.raw_pitch = op.raw.pitch; a.raw_off = op.raw.off;
+  a.mr = op.mr; a.gamma = TP(bn.weight); a.ls = ls; a.coef = TB(float, c.pl.o_coef); a.partial = TB(float, c.pl.o_part);
   a.bpartial = dbias ? TB(float, c.pl.o_part) : nullptr;       // the reduce pass's rows have been consumed by the finalize launch by then
-  a.out = out; a.out_pitch = out_pitch; a.out_off = out_off; a.C = C; a.act = act;
-  a.dmode = (c.d.on && dmode) ? dmode : 0; a.ds = c.d.site(site); a.thr = c.d.thr; a.inv_keep = c.d.inv_keep;
-  a.didx_pitch = didx_pitch; a.didx_off = didx_off;
+  a.out = op.out.p; a.out_pitch = op.out.pitch; a.out_off = op.out.off; a.C = C; a.act = op.act;
+  a.dmode = c.d.on ? op.drop.mode : TB_DROP_NONE; a.ds = c.d.site(op.drop.site); a.thr = c.d.thr; a.inv_keep = c.d.inv_keep;
+  a.didx_pitch = op.drop.idx_pitch; a.didx_off = op.drop.idx_off;
   LO_REQUIRE(C % 8 == 0 && 256 % (C / 8) == 0, "tb_bn_backward: C = %d", C);
   {
     LoProfScope _p("lo_tb_bn_reduce", 0, 4.0 * h->B * T_HW * C, c.st);
@@ -411,8 +412,9 @@ int tb_block_backward(TbCtx& c, int e, int l, const f16* xin, const f16* y, cons
   hipLaunchKernelGGL(lo_tb_tail_kernel, dim3((unsigned)((nchunk + 255) / 256)), dim3(256), 0, st, y, dy, dpool, c.gscale / (float)T_HW, dS, lgc8, nchunk);
   LO_LAUNCH_CHECK("tb_tail");
   // BatchNorm2 (+ layer_scale, Dropout2d): dS -> dT = gradient wrt conv2's output
-  LO_TRYT(tb_bn_backward(c, dS, F, 0, TB(f16, b.rawB), F, 0, TB(float, b.mrB), k.bn2, TP(k.layer_scale), TG(k.layer_scale),
-                         dT, F, 0, F, 1, 1, LO_DS_BLOCK(e, l, 3), 0, 0, TG(k.conv2_b)));
+  LO_TRYT(tb_bn_backward(c, {.din = {dS, F}, .raw = {TB(f16, b.rawB), F}, .mr = TB(float, b.mrB), .bn = k.bn2, .ls = TP(k.layer_scale),
+                             .dls = TG(k.layer_scale), .out = {dT, F}, .C = F, .act = TB_ACT_LRELU,
+                             .drop = {TB_DROP_2D, LO_DS_BLOCK(e, l, 3)}, .dbias = TG(k.conv2_b)}));
   LO_TAGGED("tb conv2 wgrad", lo_wgrad_run(h->g3b, TB(f16, b.a2), dT, TB(float, c.pl.o_wslab), TG(k.conv2_w), c.inv_g, st));
   LO_TRYT(lo_pack_weight(TP(k.conv2_w), TB(f16, c.pl.o_wd), c.d1b, st));
   LO_TAGGED("tb conv2 dgrad", lo_conv_run(c.d1b, {.in = dT, .w = TB(f16, c.pl.o_wd), .out = dU}, st));     // dU = d a2
@@ -431,8 +433,8 @@ int tb_block_backward(TbCtx& c, int e, int l, const f16* xin, const f16* y, cons
   LO_TRYT(lo_transpose_cast(TP(k.qkv_w), TB(f16, c.pl.o_wt), 3 * F, F, st));
   LO_TAGGED("tb qkv dgrad", lo_conv_run(c.dq, {.in = TB(f16, c.pl.o_dqkv), .w = TB(f16, c.pl.o_wt), .out = dU}, st));      // dU = d a1
   // Dropout2d, BatchNorm1: dU -> dT = gradient wrt conv1's output
-  LO_TRYT(tb_bn_backward(c, dU, F, 0, TB(f16, b.rawA), F, 0, TB(float, b.mrA), k.bn1, nullptr, nullptr, dT, F, 0, F, 1, 1,
-                         LO_DS_BLOCK(e, l, 0), 0, 0, TG(k.conv1_b)));
+  LO_TRYT(tb_bn_backward(c, {.din = {dU, F}, .raw = {TB(f16, b.rawA), F}, .mr = TB(float, b.mrA), .bn = k.bn1, .out = {dT, F}, .C = F,
+                             .act = TB_ACT_LRELU, .drop = {TB_DROP_2D, LO_DS_BLOCK(e, l, 0)}, .dbias = TG(k.conv1_b)}));
   const LoGeom& g1 = l == 0 ? h->g3a : h->g3b;
   const LoGeom& d1 = l == 0 ? c.d1a : c.d1b;
   LO_TAGGED("tb conv1 wgrad", lo_wgrad_run(g1, xin, dT, TB(float, c.pl.o_wslab), TG(k.conv1_w), c.inv_g, st));
@@ -442,8 +444,8 @@ int tb_block_backward(TbCtx& c, int e, int l, const f16* xin, const f16* y, cons
   } else {
     // shortcut = BatchNorm(Conv1x1(x)): dS -> gradient wrt the shortcut conv's output (no activation), its parameters, then both data gradients
     LO_TAGGED("tb conv1 dgrad", lo_conv_run(d1, {.in = dT, .w = TB(f16, c.pl.o_wd), .out = dU}, st));
-    LO_TRYT(tb_bn_backward(c, dS, F, 0, TB(f16, b.scraw), F, 0, TB(float, b.mrS), k.bn_sc, nullptr, nullptr, dT, F, 0, F, 0, 0, 0, 0, 0,
-                           TG(k.sc_b)));
+    LO_TRYT(tb_bn_backward(c, {.din = {dS, F}, .raw = {TB(f16, b.scraw), F}, .mr = TB(float, b.mrS), .bn = k.bn_sc, .out = {dT, F}, .C = F,
+                               .dbias = TG(k.sc_b)}));
     LO_TAGGED("tb shortcut wgrad", lo_wgrad_run(h->gsc, xin, dT, TB(float, c.pl.o_wslab), TG(k.sc_w), c.inv_g, st));
     LO_TRYT(lo_transpose_cast(TP(k.sc_w), TB(f16, c.pl.o_wt), F, 128, st));
     LO_TAGGED("tb shortcut dgrad", lo_conv_run(c.dsc, {.in = dT, .w = TB(f16, c.pl.o_wt), .add_src = dU, .out = dx_out}, st));

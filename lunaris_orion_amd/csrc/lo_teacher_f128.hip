@@ -463,7 +463,7 @@ int t_block_dropout(const TFwd& c, int e, int l) {
   int rows3 = 0;
   LO_TRYT(t_conv3_full(c, f8 ? "t_conv1 (dense, dropout path, e4m3)" : "t_conv1 (dense, dropout path)", e, l, 0, t_x(c, l - 1), t_x8(c, l - 1), TP(k.conv1_b),
                        TW(f16, h->o_rawA), &rows3));
-  LO_TRYT(t_bn_finalize(h, bnp, rows3, 128, k.bn1, P, ws, c.training, st));
+  LO_TRYT(t_bn_finalize(h, P, ws, {.partial = bnp, .nrow = rows3, .C = 128, .bn = k.bn1, .training = c.training}, st));
   LO_TRYT(t_drop2d(h, ws, 128, c.d, LO_DS_BLOCK(e, l, 0), st));
   LO_TRYT(t_attn_folded<true>(c, e, l, TW(float, h->o_ssb)));
   {
@@ -473,13 +473,14 @@ int t_block_dropout(const TFwd& c, int e, int l) {
   }
   LO_TRYT(t_conv3_full(c, f8 ? "t_conv2 (dense, dropout path, e4m3)" : "t_conv2 (dense, dropout path)", e, l, 1, TW(f16, h->o_proj),
                        f8 ? TW(uint8_t, h->o_proj8) : nullptr, TP(k.conv2_b), TW(f16, h->o_rawB), &rows3));
-  LO_TRYT(t_bn_finalize(h, bnp, rows3, 128, k.bn2, P, ws, c.training, st));
+  LO_TRYT(t_bn_finalize(h, P, ws, {.partial = bnp, .nrow = rows3, .C = 128, .bn = k.bn2, .training = c.training}, st));
   LO_TRYT(t_drop2d(h, ws, 128, c.d, LO_DS_BLOCK(e, l, 3), st));
   // the last block's output feeds nothing but the global average pool: a statistics-only call skips its tail, a full call
   // only sums it (no 268 MB store)
   if (l < 2 || !c.stats_only)
-    LO_TRYT(t_bn_apply(h, TW(f16, h->o_rawB), TP(k.layer_scale), t_x(c, l - 1), l < 2 ? t_x(c, l) : nullptr, 128, 128, 0, 1,
-                       (l == 2 && !c.stats_only) ? TW(float, h->o_poolp) : nullptr, ws, st, nullptr, true, l < 2 ? t_x8(c, l) : nullptr));
+    LO_TRYT(t_bn_apply(h, ws, {.raw = TW(f16, h->o_rawB), .ls = TP(k.layer_scale), .identity = t_x(c, l - 1), .y = l < 2 ? t_x(c, l) : nullptr,
+                               .C = 128, .mode = T_BN_TAIL, .pool_partial = (l == 2 && !c.stats_only) ? TW(float, h->o_poolp) : nullptr,
+                               .per_sample = true, .y8 = l < 2 ? t_x8(c, l) : nullptr}, st));
   return LO_OK;
 }
 
@@ -494,12 +495,12 @@ int t_block_sparse(const TFwd& c, int e, int l) {
     LO_TAGGED(l ? "t_conv1 (fused tap, tail on load)" : "t_conv1 (fused tap)",
               lo_conv3_run_pp_xf(h->g3, TW(f16, h->o_feat), l ? TW(f16, h->o_xc[(l - 1) & 1]) : nullptr, TW(f16, h->o_kx[e]), l,
                                  TW(f16, h->o_wp3[e][l][0]), TP(k.conv1_b), TW(f16, h->o_rawA), st, &ex));
-    LO_TRYT(t_bn_finalize(h, bnp, lo_conv3_pp_rows(h->g3), 128, k.bn1, P, ws, c.training, st));
+    LO_TRYT(t_bn_finalize(h, P, ws, {.partial = bnp, .nrow = lo_conv3_pp_rows(h->g3), .C = 128, .bn = k.bn1, .training = c.training}, st));
   } else {
     const LoConvOp c1{.in = t_x(c, l - 1), .w = TW(f16, h->o_wp3[e][l][0]), .bias = TP(k.conv1_b), .out = TW(f16, h->o_rawA), .ex = &ex};
     LoConvChoice ch;
     LO_TAGGED("t_conv1 (igemm)", lo_conv_run(h->g3, c1, st, &ch));
-    LO_TRYT(t_bn_finalize(h, bnp, ch.rows, 128, k.bn1, P, ws, c.training, st));
+    LO_TRYT(t_bn_finalize(h, P, ws, {.partial = bnp, .nrow = ch.rows, .C = 128, .bn = k.bn1, .training = c.training}, st));
   }
   LO_TRYT(t_attn_folded<false>(c, e, l, TW(float, h->o_ss)));
   const LoConvOp c2{.in = TW(f16, h->o_projc), .w = TW(f16, h->o_wp3[e][l][1]), .bias = TP(k.conv2_b), .out = TW(f16, h->o_rawBc), .ex = &ex};
@@ -508,9 +509,11 @@ int t_block_sparse(const TFwd& c, int e, int l) {
   const int tm = ch2.bm;     // the compact rows below are counted in lo_igemm_nt's M tiles
   LO_REQUIRE(ch2.kernel == LO_CK_IGEMM && (tm == 64 || tm == 128), "teacher sparse path: unexpected conv kernel %d / tile height %d", ch2.kernel, tm);
   const float* cv = TW(float, h->o_cvec[e][l]);
-  LO_TRYT(t_bn_finalize(h, bnp, B * 1024 / tm, 128, k.bn2, P, ws, c.training, st, 1024 / tm, 6 * 128 / tm, cv));
+  LO_TRYT(t_bn_finalize(h, P, ws, {.partial = bnp, .nrow = B * 1024 / tm, .C = 128, .bn = k.bn2, .training = c.training, .tps = 1024 / tm,
+                                   .vtps = 6 * 128 / tm, .cvec = cv}, st));
   if (!h->fuse_tail)
-    return t_bn_apply(h, TW(f16, h->o_rawBc), TP(k.layer_scale), t_x(c, l - 1), t_x(c, l), 128, 128, 0, 2, l == 2 ? TW(float, h->o_poolp) : nullptr, ws, st, cv);
+    return t_bn_apply(h, ws, {.raw = TW(f16, h->o_rawBc), .ls = TP(k.layer_scale), .identity = t_x(c, l - 1), .y = t_x(c, l), .C = 128,
+                              .mode = T_BN_TAIL_SPARSE, .pool_partial = l == 2 ? TW(float, h->o_poolp) : nullptr, .cvec = cv}, st);
   f16* kx = TW(f16, h->o_kx[e]) + l * 6 * 128;
   {
     LoProfScope _p("lo_t_tail (rows 0..7 + constants)", 0, 0, st);
@@ -531,8 +534,8 @@ int t_block_dense(const TFwd& c, int e, int l) {
   const LoConvOp c1{.in = t_x(c, l - 1), .w = TW(f16, h->o_wp3[e][l][0]), .bias = TP(k.conv1_b), .out = TW(f16, h->o_rawA), .ex = &ex};
   LoConvChoice ch;     // of the launch that just ran: BatchNorm partial rows of its epilogue (igemm: M tiles)
   LO_TAGGED("t_conv1 (igemm)", lo_conv_run(h->g3, c1, st, &ch));
-  LO_TRYT(t_bn_finalize(h, bnp, ch.rows, 128, k.bn1, P, ws, c.training, st));
-  LO_TRYT(t_bn_apply(h, TW(f16, h->o_rawA), nullptr, nullptr, TW(f16, h->o_bnA), 128, 128, 0, 0, nullptr, ws, st));
+  LO_TRYT(t_bn_finalize(h, P, ws, {.partial = bnp, .nrow = ch.rows, .C = 128, .bn = k.bn1, .training = c.training}, st));
+  LO_TRYT(t_bn_apply(h, ws, {.raw = TW(f16, h->o_rawA), .y = TW(f16, h->o_bnA), .C = 128}, st));
   LO_TRYT(lo_conv_run(h->gq, {.in = TW(f16, h->o_bnA), .w = TW(f16, h->o_wqkv[e][l]), .bias = TP(k.qkv_b), .out = TW(f16, h->o_qkv)}, st));
   {
     LoProfScope _p("lo_t_attn", 0, 0, st);
@@ -542,8 +545,9 @@ int t_block_dense(const TFwd& c, int e, int l) {
   LO_LAUNCH_CHECK("t_attn");
   LO_TRYT(lo_conv_run(h->gp, {.in = TW(f16, h->o_att), .w = TW(f16, h->o_wproj[e][l]), .bias = TP(k.proj_b), .out = TW(f16, h->o_proj)}, st));
   LO_TRYT(lo_conv_run(h->g3, {.in = TW(f16, h->o_proj), .w = TW(f16, h->o_wp3[e][l][1]), .bias = TP(k.conv2_b), .out = TW(f16, h->o_rawB), .ex = &ex}, st, &ch));
-  LO_TRYT(t_bn_finalize(h, bnp, ch.rows, 128, k.bn2, P, ws, c.training, st));
-  return t_bn_apply(h, TW(f16, h->o_rawB), TP(k.layer_scale), t_x(c, l - 1), t_x(c, l), 128, 128, 0, 1, l == 2 ? TW(float, h->o_poolp) : nullptr, ws, st);
+  LO_TRYT(t_bn_finalize(h, P, ws, {.partial = bnp, .nrow = ch.rows, .C = 128, .bn = k.bn2, .training = c.training}, st));
+  return t_bn_apply(h, ws, {.raw = TW(f16, h->o_rawB), .ls = TP(k.layer_scale), .identity = t_x(c, l - 1), .y = t_x(c, l), .C = 128,
+                            .mode = T_BN_TAIL, .pool_partial = l == 2 ? TW(float, h->o_poolp) : nullptr}, st);
 }
 
 // x_3 of every expert is pooled in ONE pass over feat (the full-resolution x_l were never written)

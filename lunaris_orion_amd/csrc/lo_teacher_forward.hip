@@ -16,7 +16,7 @@ int t_fe_forward(LoTeacher* h, const float* x, float* P, void* ws, int train, co
     LO_TRYT(t_conv1(x, TP(fe.conv1_w), TP(fe.conv1_b), t.raw32, bnp, B, st));
   }
   // the depthwise convs read BN(conv1) through its (scale, shift): kept in a private slot, the shared one is reused below
-  LO_TRYT(t_bn_finalize(h, bnp, B * 128, 32, fe.bn1, P, ws, train, st, 1, 1, nullptr, t.ss32, t.mr32));
+  LO_TRYT(t_bn_finalize(h, P, ws, {.partial = bnp, .nrow = B * 128, .C = 32, .bn = fe.bn1, .training = train, .ss_dst = t.ss32, .mr = t.mr32}, st));
   float* ss_cat = TW(float, h->o_ss_cat);
   for (int b = 0; b < 3; ++b) {
     const TBranchOff& br = fe.br[b];
@@ -29,7 +29,8 @@ int t_fe_forward(LoTeacher* h, const float* x, float* P, void* ws, int train, co
     const LoConvOp pw{.in = t.dw[b], .w = TW(f16, h->o_wpw[b]), .bias = TP(br.pw_b), .out = t.cat, .ex = &exb};
     LoConvChoice ch;
     LO_TRYT(lo_conv_run(h->gpw, pw, st, &ch));
-    LO_TRYT(t_bn_finalize(h, bnp, ch.rows, 64, br.bn, P, ws, train, st, 1, 1, nullptr, ss_cat + 128 * b, t.mr_br[b]));
+    LO_TRYT(t_bn_finalize(h, P, ws, {.partial = bnp, .nrow = ch.rows, .C = 64, .bn = br.bn, .training = train, .ss_dst = ss_cat + 128 * b,
+                                     .mr = t.mr_br[b]}, st));
   }
   LoConvOp fus{.out = t.rawF, .ex = &ex};
   if (fold) {
@@ -52,8 +53,8 @@ int t_fe_forward(LoTeacher* h, const float* x, float* P, void* ws, int train, co
   }
   LoConvChoice ch;
   LO_TRYT(lo_conv_run(h->gfus, fus, st, &ch));
-  LO_TRYT(t_bn_finalize(h, bnp, ch.rows, 128, fe.bn_fus, P, ws, train, st, 1, 1, nullptr, nullptr, t.mr_fus));
-  return t_bn_apply(h, t.rawF, nullptr, nullptr, t.feat, 128, 128, 0, 0, t.pool_partial, ws, st, nullptr, false, t.feat8);
+  LO_TRYT(t_bn_finalize(h, P, ws, {.partial = bnp, .nrow = ch.rows, .C = 128, .bn = fe.bn_fus, .training = train, .mr = t.mr_fus}, st));
+  return t_bn_apply(h, ws, {.raw = t.rawF, .y = t.feat, .C = 128, .pool_partial = t.pool_partial, .y8 = t.feat8}, st);
 }
 
 // Plain form of an ExpertBlock (lunar_evaluator.py:260-275): every tensor at full resolution; the attention keeps the reference's "only
@@ -74,15 +75,15 @@ int t_block_plain(LoTeacher* h, float* P, void* ws, int e, int l, const LoDropCf
     LoConvExtra exs{0, bnp};
     const LoConvOp op{.in = xin, .w = TW(f16, h->o_wsc[e]), .bias = TP(k.sc_b), .out = t.scraw, .ex = &exs};
     LO_TAGGED(nm.shortcut, lo_conv_run(h->gsc, op, st, &ch));
-    LO_TRYT(t_bn_finalize(h, bnp, ch.rows, F, k.bn_sc, P, ws, train, st, 1, 1, nullptr, t.ssS, t.mrS));
+    LO_TRYT(t_bn_finalize(h, P, ws, {.partial = bnp, .nrow = ch.rows, .C = F, .bn = k.bn_sc, .training = train, .ss_dst = t.ssS, .mr = t.mrS}, st));
   }
   const LoConvOp c1{.in = xin, .w = TW(f16, h->o_wp3[e][l][0]), .bias = TP(k.conv1_b), .out = t.rawA, .ex = &ex};
   const bool c1_f8 = f8 && f8->xin8 && f8->w8[0], c2_f8 = f8 && f8->a28 && f8->w8[1];
   if (c1_f8) LO_TAGGED(nm.conv1, lo_conv_run_f8(g1, f8->xin8, f8->w8[0], f8->ws8[0], c1, st, &ch));
   else LO_TAGGED(nm.conv1, lo_conv_run(g1, c1, st, &ch));
-  LO_TRYT(t_bn_finalize(h, bnp, ch.rows, F, k.bn1, P, ws, train, st, 1, 1, nullptr, nullptr, t.mrA));
+  LO_TRYT(t_bn_finalize(h, P, ws, {.partial = bnp, .nrow = ch.rows, .C = F, .bn = k.bn1, .training = train, .mr = t.mrA}, st));
   if (d.on) LO_TRYT(t_drop2d(h, ws, F, d, LO_DS_BLOCK(e, l, 0), st));
-  LO_TRYT(t_bn_apply(h, t.rawA, nullptr, nullptr, t.bnA, F, F, 0, 0, nullptr, ws, st, nullptr, d.on));
+  LO_TRYT(t_bn_apply(h, ws, {.raw = t.rawA, .y = t.bnA, .C = F, .per_sample = d.on}, st));
   LO_TAGGED(nm.qkv, lo_conv_run(h->gqF, {.in = t.bnA, .w = TW(f16, h->o_wqkv[e][l]), .bias = TP(k.qkv_b), .out = t.qkv}, st));
   {
     TOptScope _p(nm.attn, 0, 0, st);
@@ -96,12 +97,13 @@ int t_block_plain(LoTeacher* h, float* P, void* ws, int e, int l, const LoDropCf
   const LoConvOp c2{.in = t.a2, .w = TW(f16, h->o_wp3[e][l][1]), .bias = TP(k.conv2_b), .out = t.rawB, .ex = &ex};
   if (c2_f8) LO_TAGGED(nm.conv2, lo_conv_run_f8(h->g3b, f8->a28, f8->w8[1], f8->ws8[1], c2, st, &ch));
   else LO_TAGGED(nm.conv2, lo_conv_run(h->g3b, c2, st, &ch));
-  LO_TRYT(t_bn_finalize(h, bnp, ch.rows, F, k.bn2, P, ws, train, st, 1, 1, nullptr, nullptr, t.mrB));
+  LO_TRYT(t_bn_finalize(h, P, ws, {.partial = bnp, .nrow = ch.rows, .C = F, .bn = k.bn2, .training = train, .mr = t.mrB}, st));
   if (d.on) LO_TRYT(t_drop2d(h, ws, F, d, LO_DS_BLOCK(e, l, 3), st));
   // a block output that feeds nothing but the global average pool is only summed (xout null); a caller that wants neither skips the tail
   if (xout || pool_partial)
-    LO_TRYT(t_bn_apply(h, t.rawB, TP(k.layer_scale), sc ? t.scraw : xin, xout, F, F, 0, 1, pool_partial, ws, st, nullptr, d.on,
-                       f8 && xout ? f8->xout8 : nullptr, sc ? t.ssS : nullptr));
+    LO_TRYT(t_bn_apply(h, ws, {.raw = t.rawB, .ls = TP(k.layer_scale), .identity = sc ? t.scraw : xin, .y = xout, .C = F, .mode = T_BN_TAIL,
+                               .pool_partial = pool_partial, .per_sample = d.on, .y8 = f8 && xout ? f8->xout8 : nullptr,
+                               .id_ss = sc ? t.ssS : nullptr}, st));
   return LO_OK;
 }
 

@@ -521,8 +521,11 @@ __global__ __launch_bounds__(256) void lo_t_fold_fusion_kernel(const float* __re
 // ---------------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------------
-int t_bn_finalize(LoTeacher* h, const float* partial, int nrow, int C, const TBnOff& bn, float* P, void* ws, int training, hipStream_t st,
-                  int tps, int vtps, const float* cvec, float* ss_dst, float* mr) {
+int t_bn_finalize(LoTeacher* h, float* P, void* ws, const TBnFinalize& op, hipStream_t st) {
+  const float* partial = op.partial;
+  int nrow = op.nrow, tps = op.tps, vtps = op.vtps;
+  const int C = op.C, training = op.training;
+  const TBnOff& bn = op.bn;
   LoProfScope _p("lo_bn_finalize", 0, 0, st);
   if (training && nrow > 256) {
     // two stages: 64 row splits in parallel, then the 64 split sums
@@ -534,14 +537,14 @@ int t_bn_finalize(LoTeacher* h, const float* partial, int nrow, int C, const TBn
   }
   hipLaunchKernelGGL(lo_bn_finalize_kernel, dim3((C + 15) / 16), dim3(256), 0, st, partial, nrow, C, (float)((size_t)h->B * T_HW),
                      TP(bn.weight), TP(bn.bias), TP(bn.running_mean), TP(bn.running_var), training,
-                     ss_dst ? ss_dst : TW(float, h->o_ss), tps, vtps, cvec, (float)h->B, mr);   // ss_dst: (scale, shift) kept elsewhere than the shared slot
+                     op.ss_dst ? op.ss_dst : TW(float, h->o_ss), tps, vtps, op.cvec, (float)h->B, op.mr);   // ss_dst: (scale, shift) kept elsewhere than the shared slot
   LO_LAUNCH_CHECK("bn_finalize");
   return LO_OK;
 }
-int t_bn_apply(LoTeacher* h, const f16* raw, const float* ls, const f16* identity, f16* y, int C, int dst_pitch, int dst_off, int mode,
-               float* pool_partial, void* ws, hipStream_t st, const float* cvec, bool per_sample, uint8_t* y8, const float* id_ss) {
-  BnApplyArgs a{raw, per_sample ? TW(float, h->o_ssb) : TW(float, h->o_ss), ls, identity, y, pool_partial, C, dst_pitch, dst_off, mode,
-                T_HW / 64, cvec, per_sample ? 2 * C : 0, y8, id_ss};
+int t_bn_apply(LoTeacher* h, void* ws, const TBnApply& op, hipStream_t st) {
+  const int C = op.C, mode = op.mode;
+  BnApplyArgs a{op.raw, op.per_sample ? TW(float, h->o_ssb) : TW(float, h->o_ss), op.ls, op.identity, op.y, op.pool_partial, C,
+                op.dst_pitch, op.dst_off, mode, T_HW / 64, op.cvec, op.per_sample ? 2 * C : 0, op.y8, op.id_ss};
   LoProfScope _p(mode ? "lo_bn_apply (block tail)" : "lo_bn_apply", 0, 2.0 * h->B * T_HW * C * (mode == 1 ? 3 : 2), st);
   hipLaunchKernelGGL(lo_bn_apply_kernel, dim3(64, h->B), dim3(256), 0, st, a);
   LO_LAUNCH_CHECK("bn_apply");

@@ -3,9 +3,11 @@
 //   lo_vae_plan.hip  workspace plan, create / destroy, queries
 //   lo_vae_opt.hip   operand refresh (packs, casts) and the pipelined optimizer step
 //   lo_vae_step.hip  forward, loss, backward
+// What it launches: the convolution family (lo_conv.h), the GroupNorm family (lo_norm.h), the rest (lo_internal.h).
 #pragma once
 #include "lo_internal.h"
 #include "lo_conv.h"
+#include "lo_norm.h"
 #include "../../include/lunaris_hip.h"
 #include <stdio.h>
 #include <string.h>
@@ -27,7 +29,9 @@ struct ConvLayer {           // conv + GroupNorm + Mish
   size_t o_v = 0, o_a = 0;   // raw conv output, activation after GN+Mish(+...)
   size_t o_part = 0, o_stats = 0;   // GN partial sums, saved stats
   size_t o_P1 = 0, o_P2 = 0; // GN backward partial sums (kept until the fused finalize at the end of backward)
-  int np1 = 0;               // >0: P1 rows per sample written by the consumer's fused data-gradient epilogue
+  // rows of P1 / P2 per sample: what the buffers hold (setup_conv_layer) and what this backward has left in them so far (0 = nothing
+  // yet; written by vae_record_rows alone, reset by VaeBackward::begin, summed by vae_gn_finalize)
+  int prow_cap = 0, np1 = 0, np2 = 0;
   int MT = 0;
   size_t o_dv = 0;           // gradient wrt the raw conv output (GroupNorm backward -> data / weight gradient); one per layer, so the
                              // side-stream weight gradient of layer k never shares a buffer with what the main stream writes next
@@ -43,7 +47,7 @@ struct ConvLayer {           // conv + GroupNorm + Mish
   // arrival counters [B][8], launches so far, and -- per backward -- whether o_dv / P2 were already produced that way
   size_t o_bcnt = 0;
   unsigned gba_epoch = 0;
-  bool dv_done = false; int np2 = 0;
+  bool dv_done = false;
   hipEvent_t ev_ready = nullptr;   // dv_done: the event bound to the launch that wrote this layer's dv (null: none was bound)
   // few-rows layers (the 8 x 8 stage): forward / data gradient as a K-split 128 x 128-tile GEMM into fp32 slabs + ONE fused
   // (sample, group)-local pass (slab sum + bias + GroupNorm [+ Mish | backward]); 0 = the one-launch kernel
@@ -128,6 +132,20 @@ static inline void for_each_layer(H* h, F&& fn) {   // H: LoVae or const LoVae
   for (int s = 0; s < 4; ++s)
     for (int k = 0; k < 3; ++k) fn(h->enc[s][k]);
   for (int s = 0; s < 4; ++s) fn(h->dec[s]);
+}
+
+// the GroupNorm of a conv layer, as lo_norm.h's calls name it: expects `P` and `ws` like the macros above
+static inline LoGnLayer vae_gn_layer(const LoVae* h, const ConvLayer& c, const float* P, void* ws) {
+  return {WSP(f16, c.o_v), WSP(float, c.o_stats), PRM(c.p_gw), PRM(c.p_gb), h->B, c.Ho * c.Wo, c.Cout};
+}
+// the ONE writer of np1 / np2, called BEFORE the launch that writes the rows: they must fit what setup_conv_layer sized P1 / P2 for.
+// A count of 0 = that launch does not write the buffer: what is recorded for it stays
+static inline int vae_record_rows(ConvLayer& c, LoGnRows r) {
+  LO_REQUIRE(r.p1 <= c.prow_cap && r.p2 <= c.prow_cap, "GroupNorm backward %dx%dx%d: %d / %d rows of P1 / P2 per sample, room for %d",
+             c.Ho, c.Wo, c.Cout, r.p1, r.p2, c.prow_cap);
+  if (r.p1 > 0) c.np1 = r.p1;
+  if (r.p2 > 0) c.np2 = r.p2;
+  return LO_OK;
 }
 
 // ---- stream plumbing -------------------------------------------------------------------------------------------------------------

@@ -45,9 +45,9 @@ static int setup_conv_layer(ConvLayer& c, int kind, int B, int H, int W, int Cin
   c.o_part = ar.take((size_t)B * c.MT * 16 * 4);
   c.o_stats = ar.take((size_t)B * 16 * 4);
   int nchunk = lo_gn_nchunk(c.Ho * c.Wo, Cout);
-  int p1rows = nchunk > (c.Ho * c.Wo) / 64 ? nchunk : (c.Ho * c.Wo) / 64;   // >= tiles per sample of any data-gradient epilogue
-  c.o_P1 = ar.take((size_t)B * p1rows * Cout * 2 * 4);
-  c.o_P2 = ar.take((size_t)B * p1rows * Cout * 4);     // nchunk rows (lo_gn_bwd_apply) or one row per tile (fused apply)
+  c.prow_cap = nchunk > (c.Ho * c.Wo) / 64 ? nchunk : (c.Ho * c.Wo) / 64;   // >= tiles per sample of any data-gradient epilogue
+  c.o_P1 = ar.take((size_t)B * c.prow_cap * Cout * 2 * 4);
+  c.o_P2 = ar.take((size_t)B * c.prow_cap * Cout * 4);     // nchunk rows (lo_gn_bwd_apply) or one row per tile (fused apply)
   c.o_dv = ar.take(act);
   c.o_xbuf = ar.take((size_t)B * LO_GNF_MAX_TILES * 128);
   c.o_xcnt = ar.take((size_t)B * 4);

@@ -27,8 +27,8 @@ static int conv_gn(LoVae* h, ConvLayer& c, const f16* in, const f16* other, f16*
     // few output rows: K-split GEMM into fp32 slabs, then ONE (sample, group)-local pass: slab sum + bias -> v, statistics, GroupNorm + Mish
     LO_TRY(lo_conv_run(c.gf, {.in = in, .w = WSP(f16, c.o_wp_f), .slab = WSP(float, h->o_skslab), .nsplit = c.sk_fwd}, st));
     tag.end();
-    return lo_splitk_gn_fwd(WSP(float, h->o_skslab), c.sk_fwd, PRM(c.p_b), PRM(c.p_gw), PRM(c.p_gb), other, WSP(f16, c.o_v), y,
-                            WSP(float, c.o_stats), h->B, c.Ho * c.Wo, c.Cout, mode, st);
+    return lo_gn_forward(vae_gn_layer(h, c, P, ws),
+                         {.slab = WSP(float, h->o_skslab), .nsplit = c.sk_fwd, .bias = PRM(c.p_b), .other = other, .mode = mode, .y = y}, st);
   }
   const bool fuse = c.gnf && !c.f8 && !o_y8;
   LoGnFuse gf;
@@ -52,8 +52,8 @@ static int conv_gn(LoVae* h, ConvLayer& c, const f16* in, const f16* other, f16*
   tag.end();
   if (r_ != LO_OK) { if (fuse) --c.gnf_epoch; return r_; }
   if (fuse) return LO_OK;
-  return lo_gn_fwd(WSP(f16, c.o_v), WSP(float, c.o_part), c.MT, PRM(c.p_gw), PRM(c.p_gb), other, y, WSP(float, c.o_stats), h->B,
-                   c.Ho * c.Wo, c.Cout, mode, st, o_y8 ? WSP(uint8_t, o_y8) : nullptr);
+  return lo_gn_forward(vae_gn_layer(h, c, P, ws), {.partial = WSP(float, c.o_part), .MT = c.MT, .other = other, .mode = mode, .y = y,
+                                                   .y8 = o_y8 ? WSP(uint8_t, o_y8) : nullptr}, st);
 }
 
 // decoder (lunar_generate.py:194-229) from the latent z (fp16, in the workspace); use_skips=false is the `skips=[]`
@@ -110,8 +110,8 @@ static int vae_encoder_forward(LoVae* h, const float* x, const float* eps, uint6
     ConvLayer& c2 = h->enc[s][2];
     if (s == 0) {
       LO_TRY(lo_first_conv_fwd(x, PRM(c0.p_w), PRM(c0.p_b), WSP(f16, c0.o_v), WSP(float, c0.o_part), B, st));
-      LO_TRY(lo_gn_fwd(WSP(f16, c0.o_v), WSP(float, c0.o_part), c0.MT, PRM(c0.p_gw), PRM(c0.p_gb), nullptr, WSP(f16, c0.o_a),
-                       WSP(float, c0.o_stats), B, c0.Ho * c0.Wo, c0.Cout, 0, st, c0.o_a8 ? WSP(uint8_t, c0.o_a8) : nullptr));
+      LO_TRY(lo_gn_forward(vae_gn_layer(h, c0, P, ws), {.partial = WSP(float, c0.o_part), .MT = c0.MT, .y = WSP(f16, c0.o_a),
+                                                        .y8 = c0.o_a8 ? WSP(uint8_t, c0.o_a8) : nullptr}, st));
       LO_TRY(vae_wait_level(h, st, 1));
     } else {
       // the last stage's packed weights are refreshed at the END of the side-stream chain of a pipelined optimizer step
@@ -197,18 +197,20 @@ static int vae_gn_finalize(LoVae* h, unsigned enc_mask, bool dec, float* G, void
   LoGnFinJobs jobs;
   jobs.n = 0;
   int blocks = 0;
+  bool rows_ok = true;        // every layer summed here has gone through vae_record_rows in this backward
   auto add = [&](ConvLayer& c) {
     LoGnFinJob& j = jobs.j[jobs.n++];
     j.P1 = WSP(float, c.o_P1); j.P2 = WSP(float, c.o_P2);
     j.dgamma = GRD(c.p_gw); j.dbeta = GRD(c.p_gb); j.dbias = GRD(c.p_b);
-    j.nblk2 = B * (c.np2 > 0 ? c.np2 : lo_gn_nchunk(c.Ho * c.Wo, c.Cout));
-    j.nblk1 = c.np1 > 0 ? B * c.np1 : j.nblk2;
+    rows_ok = rows_ok && c.np1 > 0 && c.np2 > 0;
+    j.nblk1 = B * c.np1; j.nblk2 = B * c.np2;
     j.C = c.Cout; j.block0 = blocks;
     blocks += (c.Cout + 3) / 4;
   };
   for (int s = 0; s < 4; ++s)
     if (enc_mask & (1u << s)) for (int k = 0; k < 3; ++k) add(h->enc[s][k]);
   if (dec) for (int s = 0; s < 4; ++s) add(h->dec[s]);
+  LO_REQUIRE(rows_ok, "GroupNorm finalize: a layer's backward has not run (no P1 / P2 rows recorded)");
   return lo_gn_finalize_all(jobs, inv, st);
 }
 
@@ -248,6 +250,7 @@ struct VaeBackward {
         Ga(WSP(f16, h_->o_G[0])), Gb(WSP(f16, h_->o_G[1])), Gc(WSP(f16, h_->o_G[2])), Gd(WSP(f16, h_->o_G[3])) {}
 
   int begin(bool first_call);
+  int gn_backward(ConvLayer& c, const LoGnBwd& op);
   int layer(ConvLayer& c, const f16* dy, const f16* other, int mode, const f16* layer_in, f16* ds, f16* din, const f16* add_src,
             ConvLayer* prod = nullptr, bool din_has_other_readers = false);
   int dgrad_splitk(ConvLayer& c, int k, const f16* dv, f16* din, const f16* add_src, ConvLayer& prod, bool din_has_other_readers);
@@ -272,10 +275,19 @@ int VaeBackward::begin(bool first_call) {
   return LO_OK;
 }
 
+// GroupNorm backward of layer c in the form lo_gn_bwd_choose picks for (c, op); op.P1 / P2, rows_in_P1 and allow_local are filled here
+int VaeBackward::gn_backward(ConvLayer& c, const LoGnBwd& op_in) {
+  LoGnBwd op = op_in;
+  op.P1 = WSP(float, c.o_P1); op.P2 = WSP(float, c.o_P2);
+  op.rows_in_P1 = c.np1; op.allow_local = h->gn_local;
+  LO_TRY(vae_record_rows(c, lo_gn_bwd_choose(c.Ho * c.Wo, c.Cout, lo_gn_use(op)).rows));
+  return lo_gn_backward(vae_gn_layer(h, c, P, ws), op, st);
+}
+
 // backward of one conv+GN+Mish layer.  dy: gradient wrt the layer's activation output (after mish, before any skip add).
 // Produces the parameter gradients and, when din != null, the gradient wrt the layer input (+ add_src).
 // prod: the conv+GN+Mish layer (mode plain / skip) whose activation gradient this layer's data gradient produces;
-// its GroupNorm-backward reduction is then fused into the data-gradient epilogue (prod->np1 records the row count).
+// its GroupNorm-backward reduction is then fused into the data-gradient epilogue (vae_record_rows keeps the row count).
 int VaeBackward::layer(ConvLayer& c, const f16* dy, const f16* other, int mode, const f16* layer_in, f16* ds, f16* din,
                        const f16* add_src, ConvLayer* prod, bool din_has_other_readers) {
   // every layer has its own dv buffer: the side-stream weight gradient of layer k may still be reading it while the main
@@ -288,16 +300,9 @@ int VaeBackward::layer(ConvLayer& c, const f16* dy, const f16* other, int mode, 
   if (c.dv_done) { ready = c.ev_ready; c.ev_ready = nullptr; }
   else {
     LoHandover ho(h, side);
-    if (c.np1 == 0 && h->gn_local && lo_gn_bwd_local_applies(c.Ho * c.Wo, c.Cout)) {
-      // nobody has reduced this layer yet and a (sample, group) fits a workgroup: reduce + apply in ONE pass (the ResBlock tails of
-      // the 16 x 16 and 8 x 8 stages), one P1 / P2 row per sample
-      LO_TRY(lo_gn_bwd_local(dy, WSP(f16, c.o_v), other, WSP(float, c.o_stats), PRM(c.p_gw), PRM(c.p_gb), ds, dv, WSP(float, c.o_P1),
-                             WSP(float, c.o_P2), h->B, c.Ho * c.Wo, c.Cout, mode, st));
-      c.np1 = 1; c.np2 = 1;
-    } else {
-      LO_TRY(lo_gn_bwd_nofinal(dy, WSP(f16, c.o_v), other, WSP(float, c.o_stats), PRM(c.p_gw), PRM(c.p_gb), ds, dv,
-                               WSP(float, c.o_P1), WSP(float, c.o_P2), h->B, c.Ho * c.Wo, c.Cout, mode, st, c.np1));
-    }
+    // apply only where the consumer's data gradient has reduced this layer already; else ONE pass where a (sample, group) fits a
+    // workgroup (the ResBlock tails of the 16 x 16 and 8 x 8 stages), else reduce + apply
+    LO_TRY(gn_backward(c, {.dy = dy, .other = other, .mode = mode, .ds = ds, .dv = dv}));
     LO_TRY(ho.finish(st));
     ready = ho.ev;
   }
@@ -308,7 +313,7 @@ int VaeBackward::layer(ConvLayer& c, const f16* dy, const f16* other, int mode, 
     LO_TRY(lo_wgrad_run(c.gf, layer_in, dv, WSP(float, h->o_wslab), GRD(c.p_w), inv, side ? h->side : st));
   }
   if (!din) return LO_OK;
-  if (prod && c.sk_dgrad && lo_gn_bwd_local_applies(prod->Ho * prod->Wo, prod->Cout))
+  if (prod && c.sk_dgrad && lo_gn_bwd_choose(prod->Ho * prod->Wo, prod->Cout, {.slab = true}).form == LO_GNB_SLAB_LOCAL)
     return dgrad_splitk(c, k, dv, din, add_src, *prod, din_has_other_readers);
   return dgrad(c, k, dv, din, add_src, prod, din_has_other_readers);
 }
@@ -321,12 +326,11 @@ int VaeBackward::dgrad_splitk(ConvLayer& c, int k, const f16* dv, f16* din, cons
     LO_TRY(lo_conv_run(c.gd, {.in = dv, .w = WSP(f16, c.o_wp_d), .slab = WSP(float, h->o_skslab), .nsplit = c.sk_dgrad}, st));
   }
   LoHandover ho(h, side);       // the pass below writes prod's dv: its launch carries prod's hand-over event
-  LO_TRY(lo_splitk_gn_bwd(WSP(float, h->o_skslab), c.sk_dgrad, add_src, WSP(f16, prod.o_v), WSP(float, prod.o_stats), PRM(prod.p_gw),
-                          PRM(prod.p_gb), din_has_other_readers ? din : nullptr, WSP(f16, prod.o_dv), WSP(float, prod.o_P1),
-                          WSP(float, prod.o_P2), h->B, prod.Ho * prod.Wo, prod.Cout, st));
+  LO_TRY(gn_backward(prod, {.slab = WSP(float, h->o_skslab), .nsplit = c.sk_dgrad, .add_src = add_src,
+                            .dy_out = din_has_other_readers ? din : nullptr, .dv = WSP(f16, prod.o_dv)}));
   LO_TRY(ho.finish(st));
   prod.ev_ready = ho.ev;
-  prod.dv_done = true; prod.np1 = 1; prod.np2 = 1;
+  prod.dv_done = true;
   return LO_OK;
 }
 
@@ -339,18 +343,18 @@ int VaeBackward::dgrad(ConvLayer& c, int k, const f16* dv, f16* din, const f16* 
     // the launch below, asked with the apply form: np1 rows of P1 per sample either way (the apply form does not change the kernel)
     const LoConvChoice ch = lo_conv_choose(c.gd, {.add = add_src != nullptr, .gb = true, .gb_apply = true});
     const int mts = ch.mts, nt = ch.nt;
-    prod->np1 = mts;
     // ... only where the whole grid is resident at once (one workgroup per CU): on the 64-channel 64 x 64 layers (1 024 tiles at
     // batch 64, two rounds of 512) the fused launch is 32-34 us longer than the 27 us pass it replaces, and the step is 0.6 %
     // faster without it there (22 309-22 332 against 22 185-22 202; nowhere: 22 238-22 316)
-    if (h->fuse_gna && ch.gnb_apply && h->B * mts * nt <= h->n_cu) {
+    const bool apply = h->fuse_gna && ch.gnb_apply && h->B * mts * nt <= h->n_cu;
+    LO_TRY(vae_record_rows(*prod, {mts, apply ? mts : 0}));      // without the apply this launch leaves P2 alone: prod's own layer() runs that pass
+    if (apply) {
       gb.dv = WSP(f16, prod->o_dv); gb.P2 = WSP(float, prod->o_P2);
       gb.counter = WSP(unsigned int, prod->o_bcnt);
       gb.target = (++prod->gba_epoch) * (unsigned)mts;
       gb.fail = WSP(unsigned int, h->o_sync_fail);
       gb.keep_out = din_has_other_readers;      // the decoder's data gradients are also the encoder's skip gradients
       prod->dv_done = true;
-      prod->np2 = mts;
     }
     gbp = &gb;
   }
@@ -483,8 +487,7 @@ int VaeBackward::encoder_stages(int s_hi, int s_lo, const float* x, float* dx) {
     const f16* dv0 = Gd;
     if (c0.dv_done) dv0 = WSP(f16, c0.o_dv);      // conv1's data gradient has already applied this layer's GroupNorm backward
     else
-      LO_TRY(lo_gn_bwd_nofinal(Gc, WSP(f16, c0.o_v), nullptr, WSP(float, c0.o_stats), PRM(c0.p_gw), PRM(c0.p_gb), nullptr, Gd,
-                               WSP(float, c0.o_P1), WSP(float, c0.o_P2), B, 64 * 64, 64, 0, st, c0.np1));
+      LO_TRY(gn_backward(c0, {.dy = Gc, .dv = Gd}));
     LO_TRY(lo_first_conv_wgrad(x, dv0, WSP(float, h->o_fcw_part), GRD(c0.p_w), B, inv, st));
     // the images' gradient (lo_vae_backward_dx / lo_vae_encoder_backward_dx): the same dv0 through the transposed first conv
     if (dx) LO_TRY(lo_image_dgrad(dv0, 64, 2, PRM(c0.p_w), B, inv, dx, st));

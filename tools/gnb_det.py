@@ -1,4 +1,5 @@
-"""Run-to-run bitwise reproducibility of the batch-64 gradient, N repetitions (used with LO_GNB_FUSE=1)."""
+"""Run-to-run bitwise reproducibility of the gradient at batch 16 / 32 / 64, N repetitions each (the fused GroupNorm-backward
+reduction it was written for is the default; LO_GNB_FUSE=0 turns it off)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
