@@ -123,11 +123,26 @@ int lo_quantize_f8(const f16* x, uint8_t* x8, size_t n, hipStream_t st);
 
 // ---- weight gradients: lo_wgrad.hip (per-tap kernel, reduce, selection), lo_wgrad3.hip, lo_wgrad2.hip ---------------------------
 enum LoWgradKernel { LO_WK_WGRAD3 = 0, LO_WK_WGRAD2, LO_WK_TN };
-struct LoWgradChoice { int kernel; int nsplit; };   // nsplit: pixel splits = slabs the caller provides
+enum LoWgradReduce { LO_WR_NONE = 0, LO_WR_ROWS, LO_WR_CONVT, LO_WR_SCATTER };
+// The whole plan of the weight gradient of g, computed by lo_wgrad_choose and nowhere else: a GEMM launch whose workgroups each own
+// one channel tile over one range of K units and write one fp32 slab per split, then a reduce launch that sums the slabs.
+struct LoWgradChoice {
+  int kernel;                   // LoWgradKernel
+  int bmw, bnw, bkp, stages;    // lo_wgrad_tn: output x reduced channels of a tile, pixels per K step, LDS stages
+  int taps;                     // lo_wgrad_tn: (phase, tap) pairs, a workgroup each
+  int tw;                       // lo_wgrad3x3_mt: chunk width (16: 2 x 16 pixels, 8: 4 x 8)
+  bool convt;                   // lo_wgrad_s2_mt: the transposed-convolution form
+  int tiles;                    // workgroups per split
+  int units, units_per_split;   // K units (lo_wgrad_tn: bkp-pixel steps; multi-tap kernels: 32-position chunks)
+  int nsplit;                   // splits launched = slabs written = slabs the reduce reads; none is empty
+  int slabs;                    // slabs the caller provides (lo_wgrad_slab_bytes); >= nsplit
+  dim3 grid, block;             // the GEMM launch
+  bool direct;                  // the GEMM launch writes the scaled gradient itself: no slab, no reduce
+  int reduce;                   // LoWgradReduce
+  dim3 rgrid, rblock;           // the reduce launch
+};
 LoWgradChoice lo_wgrad_choose(const LoGeom& g);
 int lo_wgrad_run(const LoGeom& g, const f16* x, const f16* dy, float* slab, float* grad, float scale, hipStream_t st);
 size_t lo_wgrad_slab_bytes(const LoGeom& g);
-int lo_wgrad3_nsplit(const LoGeom& g);   // multi-tap 3x3 stride-1 weight-gradient kernel: pixel splits, 0 = does not apply
-int lo_wgrad3_run(const LoGeom& g, const f16* x, const f16* dy, float* slab, hipStream_t st, int* nsplit_out);
-int lo_wgrad2_nsplit(const LoGeom& g);   // multi-tap weight-gradient kernel of the stride-2 layers: position splits, 0 = does not apply
-int lo_wgrad2_run(const LoGeom& g, const f16* x, const f16* dy, float* slab, hipStream_t st, int* nsplit_out);
+int lo_wgrad3_run(const LoGeom& g, const LoWgradChoice& p, const f16* x, const f16* dy, float* slab, hipStream_t st);
+int lo_wgrad2_run(const LoGeom& g, const LoWgradChoice& p, const f16* x, const f16* dy, float* slab, hipStream_t st);

@@ -72,8 +72,8 @@ struct LoTeacher {
   int B = 0, E = 0, I = 256, emb = 0, layers = 3;
   int F = 128;                // feature_dim: 128 (fast paths) or 256 / 512 (plain form: every tensor at full resolution)
   // plain form of a block (feature_dim 256 / 512, and any feature_dim in the full-backward mode): conv 128->F, conv F->F, qkv F->3F,
-  // shortcut 128->F (1x1), proj on the compact rows
-  LoGeom g3a{}, g3b{}, gqF{}, gsc{}, gpc{};
+  // shortcut 128->F (1x1), proj on the compact rows; gfw: a 64-channel slice of the fusion conv 192 -> 128 (its weight gradient)
+  LoGeom g3a{}, g3b{}, gqF{}, gsc{}, gpc{}, gfw{};
   size_t o_wsc[8] = {}, o_sc = 0, o_ss_sc = 0, o_attc = 0;   // packed shortcut weights per expert, raw shortcut output, its (scale, shift), compact attention rows
   // state table (the reference's state_dict order) and where its named parameters sit
   std::vector<std::string> names;

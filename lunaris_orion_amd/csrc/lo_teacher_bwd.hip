@@ -16,6 +16,7 @@
 // the teacher's flat gradient buffer (layout = the state table, like lo_teacher_heads_backward).
 #include "lo_teacher.h"
 #include "lo_conv.h"
+#include <algorithm>
 
 // out = a + b (+ dpool broadcast): fp16 tensors of n8 8-element chunks
 __global__ __launch_bounds__(256) void lo_tb_add_kernel(const f16* __restrict__ a, const f16* __restrict__ b, const float* __restrict__ dpool,
@@ -200,6 +201,11 @@ __global__ void lo_tb_wt_kernel(const float* __restrict__ src, f16* __restrict__
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
+// every geometry the full backward passes to lo_wgrad_run (through o_wslab): tb_plan sizes the slab from this list and the executor
+// launches from the same objects.  (gsc runs at feature_dim 256 / 512 only.)
+struct TbWgradGeoms { const LoGeom* g[6]; };
+static TbWgradGeoms tb_wgrad_geoms(const LoTeacher* h) { return {{&h->g3a, &h->g3b, &h->gqF, &h->gpc, &h->gsc, &h->gfw}}; }
+
 static void tb_plan(const LoTeacher* h, TbPlan* p) {
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t r = off; off += (bytes + 255) & ~(size_t)255; return r; };
@@ -237,13 +243,7 @@ static void tb_plan(const LoTeacher* h, TbPlan* p) {
   p->o_bpart = take((size_t)h->B * 128 * 32 * 4);
   p->o_coef = take(512 * 2 * 4);
   size_t slab = 0;
-  auto ws_of = [&](int kind, int H, int W, int ci, int co) {
-    LoGeom g;
-    if (lo_make_geom(&g, kind, h->B, H, W, ci, co) == LO_OK) { const size_t b = lo_wgrad_slab_bytes(g); if (b > slab) slab = b; }
-  };
-  ws_of(LO_CONV3_S1, 128, 128, 128, (int)F); ws_of(LO_CONV3_S1, 128, 128, (int)F, (int)F);
-  ws_of(LO_LINEAR, 128, 128, (int)F, 3 * (int)F); ws_of(LO_LINEAR, 8, 128, (int)F, (int)F); ws_of(LO_LINEAR, 128, 128, 128, (int)F);
-  ws_of(LO_LINEAR, 128, 128, 64, 128);
+  for (const LoGeom* g : tb_wgrad_geoms(h).g) slab = std::max(slab, lo_wgrad_slab_bytes(*g));
   p->o_wslab = take(slab + 256);
   p->o_wd = take(F * 9 * F * 2);                 // packed data-gradient weights of a 3x3 conv
   p->o_wt = take(3 * F * F * 2);                 // transposed 1x1 weights
@@ -320,14 +320,13 @@ static int tb_fe_backward(TbCtx& c, const float* x, float* dx) {
   LO_TRYT(tb_bn_backward(c, {.din = {TB(f16, c.pl.o_dfeat), 128}, .raw = {TB(f16, c.pl.o_rawF), 128}, .mr = TB(float, c.pl.o_mr[7]),
                              .bn = fe.bn_fus, .out = {dcf, 128}, .C = 128, .act = TB_ACT_LRELU, .dbias = TG(fe.fus_b)}));
   // fusion conv 192 -> 128 as three 64-channel slices (the GEMM kernels want power-of-two channel counts)
-  LoGeom g64, d64;
-  LO_TRYT(lo_make_geom(&g64, LO_LINEAR, B, 128, 128, 64, 128));
+  LoGeom d64;
   LO_TRYT(lo_make_geom(&d64, LO_LINEAR, B, 128, 128, 128, 64));
   for (int b = 0; b < 3; ++b) {
     const size_t nchunk = px * 8;
     hipLaunchKernelGGL(lo_tb_slice64_kernel, dim3((unsigned)((nchunk + 255) / 256)), dim3(256), 0, st, TB(f16, c.pl.o_catd), 64 * b, TB(f16, c.pl.o_cat64), nchunk);
     LO_LAUNCH_CHECK("tb_slice64");
-    LO_TAGGED("tb fusion wgrad", lo_wgrad_run(g64, TB(f16, c.pl.o_cat64), dcf, TB(float, c.pl.o_wslab), TB(float, c.pl.o_tmpw), c.inv_g, st));
+    LO_TAGGED("tb fusion wgrad", lo_wgrad_run(h->gfw, TB(f16, c.pl.o_cat64), dcf, TB(float, c.pl.o_wslab), TB(float, c.pl.o_tmpw), c.inv_g, st));
     hipLaunchKernelGGL(lo_tb_scatter_cols_kernel, dim3(32), dim3(256), 0, st, TB(float, c.pl.o_tmpw), TG(fe.fus_w), 64 * b);
     LO_LAUNCH_CHECK("tb_scatter_cols");
     // data gradient of the slice: dcat[pix][64 b + ci] = sum_co dcf[pix][co] W[co][64 b + ci]  (operand [ci][co], written at its channel offset)

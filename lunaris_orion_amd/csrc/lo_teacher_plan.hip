@@ -105,6 +105,7 @@ static int t_make_geoms(LoTeacher* h) {
   LO_TRYT(lo_make_geom(&h->gqF, LO_LINEAR, B, 128, 128, F, 3 * F));
   LO_TRYT(lo_make_geom(&h->gsc, LO_LINEAR, B, 128, 128, 128, F));
   LO_TRYT(lo_make_geom(&h->gpc, LO_LINEAR, B, 8, 128, F, F));
+  LO_TRYT(lo_make_geom(&h->gfw, LO_LINEAR, B, 128, 128, 64, 128));
   h->qrows = ((B * 543 + 127) / 128) * 128;
   LO_TRYT(lo_make_geom(&h->gU, LO_LINEAR, h->qrows / 128, 1, 128, 128, 1024));
   LO_TRYT(lo_make_geom(&h->gZ, LO_LINEAR, B, 8, 128, 1088, 128));

@@ -259,7 +259,7 @@ static void plan_gn_fusions(LoVae* h) {
 // 17 beside the side stream's AdamW, data-gradient launches 55-65 us instead of 36-44 beside the weight gradients.
 // (A CU-masked side stream -- hipExtStreamCreateWithCUMask with 64 / 128 / 192 / all 256 bits set -- was tried in round 3 to
 // fence the side work off: 10 300-12 700 sprites/s against 22 300 with ANY mask, the full one included, so the masked queue
-// itself is the cost on this stack; what does help is fewer, longer side workgroups: see lo_wgrad3_nsplit / lo_wgrad2_nsplit.)
+// itself is the cost on this stack; what does help is fewer, longer side workgroups: see the multi-tap split policy in lo_wgrad.hip.)
 static void create_side_stream(LoVae* h) {
   h->overlap = getenv("LO_NO_OVERLAP") == nullptr;
   if (!h->overlap) return;

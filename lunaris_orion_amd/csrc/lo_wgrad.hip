@@ -29,14 +29,8 @@ struct WgradArgs {
 };
 
 // LDS-DMA staged like lo_igemm_nt.  Tiles are [32 pixel rows][BMW or BNW channels] fp16, unpadded; the transposed
-// fragment reads (ds_read_b64_tr_b16) are kept conflict-free by XOR-swizzling 32-byte blocks inside a row:
-//   256-byte rows: block ^= row & 7        128-byte rows: block ^= (row >> 1) & 3
+// fragment reads (ds_read_b64_tr_b16) are kept conflict-free by the block swizzle lo_tr_swz (lo_conv_dev.h).
 // Output channels n >= Cout (a 32-channel layer run with the 64-wide tile) read the zero page and are not stored.
-template <int RB>
-__device__ __forceinline__ int lo_tr_swz(int row) {
-  return RB == 256 ? (row & 7) : ((row >> 1) & 3);
-}
-
 template <int BMW, int BNW, int NSTAGE, int BKP>
 __global__ __launch_bounds__(256) void lo_wgrad_tn(WgradArgs a) {
   static_assert(BKP == 32 || BKP == 64, "pixels per K step");
@@ -326,96 +320,156 @@ static bool lo_wgrad_reduce_convt_applies(const LoGeom& g) {
 static bool lo_wgrad_reduce_rows_applies(const LoGeom& g) {
   return g.n_phase == 1 && g.T[0] == 9 && g.sc == 9 && g.sn == 9 * g.Cin && g.wofs[0] == 0 && g.Cin % 64 == 0;
 }
-// slab [nsplit][packed] -> canonical fp32 gradient (scaled): the coalescing form where the geometry allows it
-static int lo_wgrad_reduce_launch(const float* slab, float* grad, const LoGeom& g, int total, int nsplit, float scale, hipStream_t st) {
-  if (lo_wgrad_reduce_rows_applies(g)) {
-    const int G = nsplit >= 4 ? 4 : (nsplit < 1 ? 1 : nsplit);
-    hipLaunchKernelGGL(lo_wgrad_reduce_rows_kernel, dim3(g.Cout * (g.Cin / 64)), dim3(16, 9, G), 0, st, slab, grad, g, total, nsplit, scale);
-  } else if (lo_wgrad_reduce_convt_applies(g)) {
-    hipLaunchKernelGGL(lo_wgrad_reduce_convt_kernel, dim3((g.Cout / 4) * (g.Cin / 16)), dim3(256), 0, st, slab, grad, g, total, nsplit, scale);
-  } else {
-    hipLaunchKernelGGL(lo_wgrad_reduce_kernel, dim3((total / 4 + 63) / 64), dim3(256), 0, st, slab, grad, g, total, nsplit, scale);
-  }
-  LO_LAUNCH_CHECK("wgrad_reduce");
-  return LO_OK;
+
+// ---------------------------------------------------------------------------------------------
+// The plan (LoWgradChoice, lo_conv.h): kernel, tile, K split, both launches.  Nothing below or in the launchers recomputes any of it.
+// ---------------------------------------------------------------------------------------------
+// lo_wgrad3x3_mt: 3x3 stride 1, 64-channel tiles, maps cut into 2 x 16 or 4 x 8 chunks
+static bool wgrad3_applies(const LoGeom& g) {
+  if (g.n_phase != 1 || g.T[0] != 9 || g.in_stride != 1 || g.out_stride != 1) return false;
+  if (g.Cin % 64 || g.Cout % 64 || g.Hin != g.Hout || g.Win != g.Wout) return false;
+  if (g.Win % 16 == 0) return g.Hin % 2 == 0;
+  return g.Win == 8 && g.Hin % 4 == 0;
 }
-
-static inline int wgrad_bmw(const LoGeom& g) { return g.Cout % 128 == 0 ? 128 : 64; }
-static inline int wgrad_bnw(const LoGeom& g) { return g.Cin % 128 == 0 ? 128 : 64; }
-
-static inline int wgrad_bkp(const LoGeom& g) { return ((long)g.B * g.GH * g.GW) % 64 == 0 && (long)g.B * g.GH * g.GW >= 1024 ? 64 : 32; }
-
+// lo_wgrad_s2_mt: a coarse tensor (64-channel tiles, 4 x 8 chunks) against a fine one of twice the resolution
+struct Wgrad2Shape { bool convt; int Hc, Wc, Ca, Cf; };
+static bool wgrad2_applies(const LoGeom& g, Wgrad2Shape* s) {
+  const bool s2 = g.n_phase == 1 && g.T[0] == 9 && g.in_stride == 2 && g.out_stride == 1;                  // Conv2d k3 s2 p1 forward geometry
+  const bool ct = g.n_phase == 4 && g.in_stride == 1 && g.out_stride == 2 && g.T[0] == 4 && g.T[3] == 4;   // ConvTranspose2d k4 s2 p1
+  if (!s2 && !ct) return false;
+  *s = {ct, s2 ? g.Hout : g.Hin, s2 ? g.Wout : g.Win, s2 ? g.Cout : g.Cin, s2 ? g.Cin : g.Cout};
+  return s->Hc % 4 == 0 && s->Wc % 8 == 0 && s->Ca % 64 == 0 && (s->Cf % 64 == 0 || s->Cf == 32);
+}
 // LO_WGRAD_S2=0: the stride-2 layers' weight gradients through the per-tap kernel lo_wgrad_tn (the round-2 path; A/B)
 static bool lo_wgrad_s2_enabled() {
   static const bool on = [] { const char* e = getenv("LO_WGRAD_S2"); return !(e && atoi(e) == 0); }();
   return on;
 }
 
-// pixel splits of the per-tap kernel lo_wgrad_tn for this geometry
-static int wgrad_tn_nsplit(const LoGeom& g) {
-  int bmw = wgrad_bmw(g), bnw = wgrad_bnw(g), bkp = wgrad_bkp(g);
-  int taps = 0;
-  for (int p = 0; p < g.n_phase; ++p) taps += g.T[p];
-  long tiles = (long)((g.Cout + bmw - 1) / bmw) * (g.Cin / bnw) * taps;
-  int M = g.B * g.GH * g.GW;
-  int ms_total = (M + bkp - 1) / bkp;
-  constexpr int target = 768;      // 512 / 768 / 1024 swept in round 2: inside +-0.5 %
-  long want = (target + tiles - 1) / tiles;
-  // every split writes (and the reduce pass re-reads) one fp32 slab: keep the slab traffic under ~24 MB per launch,
-  // but never go below one workgroup per CU
-  const long slab_bytes = (long)lo_geom_packed_elems(g) * 4;
-  long cap = (24L << 20) / (slab_bytes > 0 ? slab_bytes : 1);
-  long floor_wgs = (256 + tiles - 1) / tiles;
+// The split policy: as many K splits as bring the launch to `target` workgroups, but
+//   - every split writes (and the reduce pass re-reads) one fp32 slab: the slab traffic stays under ~24 MB per launch ...
+//   - ... unless that leaves fewer than `floor` workgroups;
+//   - at least `min_units` K units per split, at most `max_splits` splits.
+struct WgradPolicy { int target, floor, min_units, max_splits; };
+// Per-tap kernel: target 512 / 768 / 1024 swept in round 2, inside +-0.5 %; never below one workgroup per CU; 8 K steps per split.
+static constexpr WgradPolicy kPolicyTn = {768, 256, 8, 256};
+// Multi-tap kernels: they run on the side stream BESIDE the dependent chain, and every CU one of their 512-thread workgroups holds is
+// lost to the chain.  Round 3, sprites/s on the step (interleaved on one box) | serial time of the 8 lo_wgrad3x3_mt launches:
+//   target 256 / floor 256 (one workgroup per CU at least)   21 854-21 994 | 0.240 ms
+//   192 / 192                                                22 375-22 499 | 0.269 ms
+//   256 / 128                                                22 513-22 706 | 0.303 ms   <- shipped
+//   128 / 64                                                 22 544-22 747 | 0.340 ms
+// fewer, longer workgroups (and less slab traffic) win on the step although the launch alone takes longer.  The same for
+// lo_wgrad_s2_mt: with the per-tap policy (>= 256 workgroups) it LOST 1 % on the step against the kernel it replaces (21 014-21 067
+// against 21 215-21 251) although alone it is faster: a multi-tap tile has 9 / 16 times fewer tiles per layer, so filling 256 CUs
+// took up to 32 position splits and 64 MB of slab per layer.  With a floor of 128: 22 262-22 317 against 21 955-22 019 for the
+// per-tap kernel on the same box (+1.3 %).  (max_splits cannot bind below a target of 256.)
+static constexpr WgradPolicy kPolicyMt = {256, 128, 4, 256};
+
+static int wgrad_wanted_splits(long tiles, long units, long packed_bytes, const WgradPolicy& p) {
+  long want = (p.target + tiles - 1) / tiles;
+  long cap = (24L << 20) / (packed_bytes > 0 ? packed_bytes : 1);
+  const long floor_wgs = (p.floor + tiles - 1) / tiles;
   if (cap < floor_wgs) cap = floor_wgs;
   if (want > cap) want = cap;
-  if (want < 1) want = 1;
-  if (want > ms_total / 8) want = ms_total / 8 > 0 ? ms_total / 8 : 1;   // at least 8 K steps per split
-  if (want > 256) want = 256;
-  return (int)want;
+  if (want > units / p.min_units) want = units / p.min_units;
+  if (want > p.max_splits) want = p.max_splits;
+  return want < 1 ? 1 : (int)want;
 }
 
-// which weight-gradient kernel runs g, and the number of pixel splits it will use (callers size the slab with it)
 LoWgradChoice lo_wgrad_choose(const LoGeom& g) {
-  if (int n3 = lo_wgrad3_nsplit(g)) return {LO_WK_WGRAD3, n3};   // multi-tap kernel (3x3 stride 1)
-  if (lo_wgrad_s2_enabled())
-    if (int n2 = lo_wgrad2_nsplit(g)) return {LO_WK_WGRAD2, n2}; // multi-tap kernel of the stride-2 layers (k3 s2, transposed k4 s2)
-  return {LO_WK_TN, wgrad_tn_nsplit(g)};
+  LoWgradChoice c{};
+  const WgradPolicy* pol = &kPolicyMt;
+  Wgrad2Shape s2;
+  if (wgrad3_applies(g)) {
+    c.kernel = LO_WK_WGRAD3;
+    c.tw = g.Win % 16 == 0 ? 16 : 8;
+    c.tiles = (g.Cout / 64) * (g.Cin / 64);
+    c.units = g.B * g.Hin * g.Win / 32;
+    c.block = dim3(512);
+  } else if (lo_wgrad_s2_enabled() && wgrad2_applies(g, &s2)) {
+    c.kernel = LO_WK_WGRAD2;
+    c.convt = s2.convt;
+    c.tiles = (s2.Ca / 64) * ((s2.Cf + 63) / 64);
+    c.units = g.B * s2.Hc * s2.Wc / 32;
+    c.block = dim3(512);
+  } else {
+    c.kernel = LO_WK_TN;
+    pol = &kPolicyTn;
+    const long M = (long)g.B * g.GH * g.GW;
+    c.bmw = g.Cout % 128 == 0 ? 128 : 64;
+    c.bnw = g.Cin % 128 == 0 ? 128 : 64;
+    c.bkp = M % 64 == 0 && M >= 1024 ? 64 : 32;
+    c.stages = c.bkp == 64 && c.bmw + c.bnw > 192 ? 2 : 3;   // 64-pixel steps: 3 LDS stages where the tile fits (+0.9 % on the step over 2)
+    for (int p = 0; p < g.n_phase; ++p) c.taps += g.T[p];
+    c.tiles = ((g.Cout + c.bmw - 1) / c.bmw) * (g.Cin / c.bnw) * c.taps;
+    c.units = (int)((M + c.bkp - 1) / c.bkp);
+    c.block = dim3(256);
+  }
+  const int total = lo_geom_packed_elems(g);
+  const int want = wgrad_wanted_splits(c.tiles, c.units, (long)total * 4, *pol);
+  c.units_per_split = (c.units + want - 1) / want;
+  c.nsplit = (c.units + c.units_per_split - 1) / c.units_per_split;   // the one "no empty split" rule: trailing splits past the last unit go
+  // Exported sizes (lo_wgrad_slab_bytes_for, the workspace sizes) keep the counts they have always had: the wanted count for
+  // lo_wgrad_tn and lo_wgrad3x3_mt -- there slabs > nsplit wherever the rule above dropped a split, and the slabs past nsplit are
+  // neither written nor read -- and the written count for lo_wgrad_s2_mt.
+  c.slabs = c.kernel == LO_WK_WGRAD2 ? c.nsplit : want;
+  c.grid = dim3(c.tiles * c.nsplit);
+  c.direct = c.kernel == LO_WK_TN && c.nsplit == 1 && g.sc == 1;      // one split of a Linear layer
+  // the reduce: the coalescing form where the geometry allows it
+  if (c.direct) {
+    c.reduce = LO_WR_NONE;
+  } else if (lo_wgrad_reduce_rows_applies(g)) {
+    c.reduce = LO_WR_ROWS;
+    c.rgrid = dim3(g.Cout * (g.Cin / 64));
+    c.rblock = dim3(16, 9, c.nsplit >= 4 ? 4 : c.nsplit);             // z: split groups
+  } else if (lo_wgrad_reduce_convt_applies(g)) {
+    c.reduce = LO_WR_CONVT;
+    c.rgrid = dim3((g.Cout / 4) * (g.Cin / 16));
+    c.rblock = dim3(256);
+  } else {
+    c.reduce = LO_WR_SCATTER;
+    c.rgrid = dim3((total / 4 + 63) / 64);
+    c.rblock = dim3(256);
+  }
+  return c;
 }
 
-// the per-tap kernel; *direct: it wrote the canonical gradient itself (one split of a Linear layer), no reduce pass
-static int wgrad_tn_launch(const LoGeom& g, const f16* x, const f16* dy, float* slab, float* grad, float scale, int nsplit, hipStream_t st,
-                           bool* direct) {
+size_t lo_wgrad_slab_bytes(const LoGeom& g) { return (size_t)lo_wgrad_choose(g).slabs * lo_geom_packed_elems(g) * sizeof(float); }
+
+// ---------------------------------------------------------------------------------------------
+// launchers: arguments from (g, plan)
+// ---------------------------------------------------------------------------------------------
+static int wgrad_tn_run(const LoGeom& g, const LoWgradChoice& p, const f16* x, const f16* dy, float* slab, float* grad, float scale, hipStream_t st) {
+  LO_REQUIRE(g.Cin % 64 == 0 && g.Cout % 32 == 0, "lo_wgrad_run: need Cin %% 64 == 0 and Cout %% 32 == 0 (Cin=%d Cout=%d)", g.Cin, g.Cout);
+  LO_REQUIRE(g.lg_hin >= 0 && g.lg_win >= 0 && g.lg_cin >= 0 && g.lg_hout >= 0 && g.lg_wout >= 0,
+             "lo_wgrad_run: tensor dims must be powers of two");
   WgradArgs a;
   a.x = x; a.dy = dy; a.slab = slab; a.g = g; a.grad = grad; a.scale = scale;
   a.M = g.B * g.GH * g.GW;
   a.packed_elems = lo_geom_packed_elems(g);
-  a.nsplit = nsplit;
-  a.direct = (a.nsplit == 1 && g.sc == 1) ? 1 : 0;
-  const int bkp = wgrad_bkp(g);
-  int ms_total = (a.M + bkp - 1) / bkp;
-  a.msteps_per_split = (ms_total + a.nsplit - 1) / a.nsplit;
-  LO_REQUIRE(g.Cin % 64 == 0 && g.Cout % 32 == 0, "lo_wgrad_run: need Cin %% 64 == 0 and Cout %% 32 == 0 (Cin=%d Cout=%d)", g.Cin, g.Cout);
-  LO_REQUIRE(g.lg_hin >= 0 && g.lg_win >= 0 && g.lg_cin >= 0 && g.lg_hout >= 0 && g.lg_wout >= 0,
-             "lo_wgrad_run: tensor dims must be powers of two");
-  int taps = 0;
-  for (int p = 0; p < g.n_phase; ++p) taps += g.T[p];
-  int bmw = wgrad_bmw(g), bnw = wgrad_bnw(g);
-  a.taps = taps;
-  dim3 grid(((g.Cout + bmw - 1) / bmw) * (g.Cin / bnw) * taps * a.nsplit);
-  constexpr int wg_stages = 3;     // 64-pixel steps: LDS stages (3 where the tile fits: +0.9 % on the step over 2)
-#define LO_WG(BMW, BNW)                                                                            \
-  do {                                                                                             \
-    if (bkp == 64 && wg_stages == 3 && (BMW + BNW) <= 192) hipLaunchKernelGGL((lo_wgrad_tn<BMW, BNW, 3, 64>), grid, dim3(256), 0, st, a);   \
-    else if (bkp == 64) hipLaunchKernelGGL((lo_wgrad_tn<BMW, BNW, 2, 64>), grid, dim3(256), 0, st, a);   \
-    else hipLaunchKernelGGL((lo_wgrad_tn<BMW, BNW, 3, 32>), grid, dim3(256), 0, st, a);             \
+  a.taps = p.taps; a.nsplit = p.nsplit; a.msteps_per_split = p.units_per_split;
+  a.direct = p.direct ? 1 : 0;
+#define LO_WG(BMW, BNW)                                                                                                          \
+  do {                                                                                                                           \
+    if (p.bkp == 64 && p.stages == 3) hipLaunchKernelGGL((lo_wgrad_tn<BMW, BNW, 3, 64>), p.grid, p.block, 0, st, a);             \
+    else if (p.bkp == 64) hipLaunchKernelGGL((lo_wgrad_tn<BMW, BNW, 2, 64>), p.grid, p.block, 0, st, a);                         \
+    else hipLaunchKernelGGL((lo_wgrad_tn<BMW, BNW, 3, 32>), p.grid, p.block, 0, st, a);                                          \
   } while (0)
-  if (bmw == 128 && bnw == 128) LO_WG(128, 128);
-  else if (bmw == 128 && bnw == 64) LO_WG(128, 64);
-  else if (bmw == 64 && bnw == 128) LO_WG(64, 128);
+  if (p.bmw == 128 && p.bnw == 128) LO_WG(128, 128);
+  else if (p.bmw == 128 && p.bnw == 64) LO_WG(128, 64);
+  else if (p.bmw == 64 && p.bnw == 128) LO_WG(64, 128);
   else LO_WG(64, 64);
 #undef LO_WG
   LO_LAUNCH_CHECK("wgrad_tn");
-  *direct = a.direct != 0;
+  return LO_OK;
+}
+
+// slab [nsplit][packed] -> canonical fp32 gradient (scaled)
+static int lo_wgrad_reduce_launch(const LoGeom& g, const LoWgradChoice& p, const float* slab, float* grad, float scale, hipStream_t st) {
+  auto* const kernel = p.reduce == LO_WR_ROWS ? lo_wgrad_reduce_rows_kernel : p.reduce == LO_WR_CONVT ? lo_wgrad_reduce_convt_kernel : lo_wgrad_reduce_kernel;
+  hipLaunchKernelGGL(kernel, p.rgrid, p.rblock, 0, st, slab, grad, g, lo_geom_packed_elems(g), p.nsplit, scale);
+  LO_LAUNCH_CHECK("wgrad_reduce");
   return LO_OK;
 }
 
@@ -424,20 +478,15 @@ static int wgrad_tn_launch(const LoGeom& g, const f16* x, const f16* dy, float* 
 // right behind its GEMM finds the slab in the Infinity Cache, the merged one re-reads up to 0.2 GB from HBM in front of the join)
 int lo_wgrad_run(const LoGeom& g, const f16* x, const f16* dy, float* slab, float* grad, float scale, hipStream_t st) {
   static const char* const scope[3] = {"lo_wgrad3x3_mt", "lo_wgrad_s2_mt", "lo_wgrad_tn"};   // indexed by LoWgradKernel
-  const LoWgradChoice c = lo_wgrad_choose(g);
-  const int total = lo_geom_packed_elems(g);
-  int nsplit = c.nsplit;
-  bool direct = false;
+  const LoWgradChoice p = lo_wgrad_choose(g);
   {
-    LoProfScope _p(lo_prof_geom_name(scope[c.kernel], g), lo_geom_flops(g), lo_geom_bytes(g), st);
-    int r = c.kernel == LO_WK_WGRAD3   ? lo_wgrad3_run(g, x, dy, slab, st, &nsplit)
-            : c.kernel == LO_WK_WGRAD2 ? lo_wgrad2_run(g, x, dy, slab, st, &nsplit)
-                                       : wgrad_tn_launch(g, x, dy, slab, grad, scale, c.nsplit, st, &direct);
+    LoProfScope _p(lo_prof_geom_name(scope[p.kernel], g), lo_geom_flops(g), lo_geom_bytes(g), st);
+    int r = p.kernel == LO_WK_WGRAD3   ? lo_wgrad3_run(g, p, x, dy, slab, st)
+            : p.kernel == LO_WK_WGRAD2 ? lo_wgrad2_run(g, p, x, dy, slab, st)
+                                       : wgrad_tn_run(g, p, x, dy, slab, grad, scale, st);
     if (r != LO_OK) return r;
   }
-  if (direct) return LO_OK;
-  LoProfScope _p2(lo_prof_geom_name("lo_wgrad_reduce", g), 0, 4.0 * total * (nsplit + 1), st);
-  return lo_wgrad_reduce_launch(slab, grad, g, total, nsplit, scale, st);
+  if (p.reduce == LO_WR_NONE) return LO_OK;
+  LoProfScope _p2(lo_prof_geom_name("lo_wgrad_reduce", g), 0, 4.0 * lo_geom_packed_elems(g) * (p.nsplit + 1), st);
+  return lo_wgrad_reduce_launch(g, p, slab, grad, scale, st);
 }
-
-size_t lo_wgrad_slab_bytes(const LoGeom& g) { return (size_t)lo_wgrad_choose(g).nsplit * lo_geom_packed_elems(g) * sizeof(float); }

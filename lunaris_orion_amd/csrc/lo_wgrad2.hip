@@ -15,12 +15,7 @@
 //   counted vmcnt (every wave issues exactly four 1-KB LDS-DMA instructions per chunk) + one barrier per chunk
 //   output: fp32 slab [split][packed weight layout of the forward geometry], summed by lo_wgrad_reduce_kernel (fixed order)
 #include "lo_conv.h"
-#include <stdlib.h>
-
-__device__ __attribute__((aligned(256))) unsigned int lo_zero_page_w2[64];
-// every padding lane reads the page's base: 1 address x 16 B per lane
-static_assert(sizeof(lo_zero_page_w2) >= 1 * 16, "LDS-DMA padding lanes read 16 B at offset 0 of the zero page");
-#define LO_VMCNT(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
+#include "lo_conv_dev.h"
 
 struct Wgrad2Args {
   const f16* a;       // coarse tensor [B, Hc, Wc, Ca]
@@ -32,13 +27,6 @@ struct Wgrad2Args {
   int Cin;            // forward Cin (the packed layout's K = taps * Cin)
   int wofs[4];        // CONVT: element offset of the four phases inside the packed weight
 };
-
-__device__ __forceinline__ int lo_xcd_remap_w2(int bid, int total) {
-  const int q = total >> 3, r = total & 7;
-  const int xcd = bid & 7, loc = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-}
-__device__ __forceinline__ int lo_w2_swz(int row) { return (row >> 1) & 3; }
 
 template <bool CONVT>
 __global__ __launch_bounds__(512) void lo_wgrad_s2_mt(Wgrad2Args a) {
@@ -58,7 +46,7 @@ __global__ __launch_bounds__(512) void lo_wgrad_s2_mt(Wgrad2Args a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wa = wave & 1, wf = (wave >> 1) & 1, wt = wave >> 2;
   const int tiles_f = (a.Cf + 63) >> 6, tiles = (a.Ca >> 6) * tiles_f;
-  const int wid = lo_xcd_remap_w2(blockIdx.x, gridDim.x);
+  const int wid = lo_xcd_remap(blockIdx.x, gridDim.x);
   const int tile = wid % tiles, split = wid / tiles;
   const int a0 = (tile / tiles_f) * 64, f0 = (tile % tiles_f) * 64;
   const int q_begin = split * a.chunks_per_split;
@@ -66,7 +54,7 @@ __global__ __launch_bounds__(512) void lo_wgrad_s2_mt(Wgrad2Args a) {
   const int nq = q_end - q_begin;
   const int chunks_x = a.Wc / TW, chunks_img = chunks_x * (a.Hc / TH);
   const int Hf = 2 * a.Hc, Wf = 2 * a.Wc;
-  const f16* zpage = reinterpret_cast<const f16*>(lo_zero_page_w2);
+  const f16* zpage = reinterpret_cast<const f16*>(lo_zero_page);
 
   // ---- per-lane constants of this wave's four DMA slots q = wave * 4 + j: q < 4 -> A rows 8q .. 8q+7, else patch rows 8 (q - 4) ..
   int s_kind[4], s_off[4], s_py[4], s_px[4];            // kind 0 = A, 1 = patch, 2 = unused
@@ -79,13 +67,13 @@ __global__ __launch_bounds__(512) void lo_wgrad_s2_mt(Wgrad2Args a) {
       const int arow = q * 8 + row8;                                             // coarse position of the chunk: (arow / TW, arow % TW)
       s_kind[j] = 0;
       s_py[j] = arow / TW; s_px[j] = arow % TW;
-      s_off[j] = (s_py[j] * a.Wc + s_px[j]) * a.Ca + a0 + ((((pos >> 1) ^ lo_w2_swz(arow)) << 1) | (pos & 1)) * 8;
+      s_off[j] = (s_py[j] * a.Wc + s_px[j]) * a.Ca + a0 + ((((pos >> 1) ^ lo_tr_swz<128>(arow)) << 1) | (pos & 1)) * 8;
       s_lds[j] = (unsigned int)(q * 1024);
     } else if (q - 4 < PQ) {
       const int prow = (q - 4) * 8 + row8;
       const int py = prow / (2 * PWH), rem = prow - py * (2 * PWH), par = rem / PWH, hx = rem - par * PWH;
       const int px = 2 * hx + par;
-      const int ch = f0 + ((((pos >> 1) ^ lo_w2_swz(prow)) << 1) | (pos & 1)) * 8;
+      const int ch = f0 + ((((pos >> 1) ^ lo_tr_swz<128>(prow)) << 1) | (pos & 1)) * 8;
       const bool ok = prow < PROWS && px < 2 * TW + R - 1 && ch < a.Cf;
       s_kind[j] = ok ? 1 : 2;
       s_py[j] = py - 1; s_px[j] = px - 1;                                          // relative to (2 y0, 2 x0)
@@ -135,7 +123,7 @@ __global__ __launch_bounds__(512) void lo_wgrad_s2_mt(Wgrad2Args a) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int Rr = trow + 16 * h, blk = wa * 2 + mi;
-      aoff[mi][h] = Rr * 128 + ((blk ^ lo_w2_swz(Rr)) * 32) + tsub;
+      aoff[mi][h] = Rr * 128 + ((blk ^ lo_tr_swz<128>(Rr)) * 32) + tsub;
     }
   // patch fragments of this wave's taps t = wt * NTW + tt: fine pixel of k index kk under tap (r, s) = (2 ky + r, 2 kx + s)
   int boff[NTW][2];
@@ -148,7 +136,7 @@ __global__ __launch_bounds__(512) void lo_wgrad_s2_mt(Wgrad2Args a) {
       const int r = tq / R, s = tq % R;
       const int kk = trow + 16 * h, ky = kk / TW, kx = kk % TW;
       const int prow = ((2 * ky + r) * 2 + (s & 1)) * PWH + kx + (s >> 1);
-      boff[tt][h] = A_BYTES + prow * 128 + (((wf * 2) ^ lo_w2_swz(prow)) * 32) + tsub;
+      boff[tt][h] = A_BYTES + prow * 128 + (((wf * 2) ^ lo_tr_swz<128>(prow)) * 32) + tsub;
     }
 
   f32x4 acc[NTW][2][2];
@@ -232,63 +220,20 @@ __global__ __launch_bounds__(512) void lo_wgrad_s2_mt(Wgrad2Args a) {
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// launcher side
-// ---------------------------------------------------------------------------------------------
-static inline bool wgrad2_applies(const LoGeom& g) {
-  const bool s2 = g.n_phase == 1 && g.T[0] == 9 && g.in_stride == 2 && g.out_stride == 1;                  // Conv2d k3 s2 p1 forward geometry
-  const bool ct = g.n_phase == 4 && g.in_stride == 1 && g.out_stride == 2 && g.T[0] == 4 && g.T[3] == 4;   // ConvTranspose2d k4 s2 p1
-  if (!s2 && !ct) return false;
-  const int Hc = s2 ? g.Hout : g.Hin, Wc = s2 ? g.Wout : g.Win;
-  const int Ca = s2 ? g.Cout : g.Cin, Cf = s2 ? g.Cin : g.Cout;
-  return Hc % 4 == 0 && Wc % 8 == 0 && Ca % 64 == 0 && (Cf % 64 == 0 || Cf == 32);
-}
-
-int lo_wgrad2_nsplit(const LoGeom& g) {
-  if (!wgrad2_applies(g)) return 0;
-  const bool s2 = g.n_phase == 1;
-  const int Hc = s2 ? g.Hout : g.Hin, Wc = s2 ? g.Wout : g.Win;
-  const int Ca = s2 ? g.Cout : g.Cin, Cf = s2 ? g.Cin : g.Cout;
-  const long tiles = (long)(Ca / 64) * ((Cf + 63) / 64);
-  const long nchunks = (long)g.B * Hc * Wc / 32;
-  // workgroups per launch: as in lo_wgrad3_nsplit (same table), few and long.  With the per-tap kernel's policy (>= 256 workgroups)
-  // this kernel LOST 1 % on the step against the kernel it replaces (21 014-21 067 against 21 215-21 251) although alone it is
-  // faster: a multi-tap tile has 9 / 16 times fewer tiles per layer, so filling 256 CUs took up to 32 position splits and 64 MB of
-  // slab per layer.  With a floor of 128: 22 262-22 317 against 21 955-22 019 for the per-tap kernel on the same box (+1.3 %)
-  constexpr int tgt = 256, flo = 128, capmb = 24;
-  long want = (tgt + tiles - 1) / tiles;
-  long packed = 0;
-  for (int p = 0; p < g.n_phase; ++p) packed += (long)g.Cout * g.T[p] * g.Cin;
-  const long slab_bytes = packed * 4;
-  long cap = ((long)capmb << 20) / slab_bytes;                      // slab traffic (written here, re-read by the reduce pass)
-  const long floor_wgs = (flo + tiles - 1) / tiles;         // but not below this many workgroups
-  if (cap < floor_wgs) cap = floor_wgs;
-  if (want > cap) want = cap;
-  if (want > nchunks / 4) want = nchunks / 4 > 0 ? nchunks / 4 : 1;   // at least 4 chunks per split
-  if (want < 1) want = 1;
-  const long cps = (nchunks + want - 1) / want;
-  return (int)((nchunks + cps - 1) / cps);                  // no empty splits: every slab is written
-}
-
-int lo_wgrad2_run(const LoGeom& g, const f16* x, const f16* dy, float* slab, hipStream_t st, int* nsplit_out) {
-  LO_REQUIRE(wgrad2_applies(g), "lo_wgrad2_run: geometry not supported by the stride-2 multi-tap weight-gradient kernel");
-  const bool s2 = g.n_phase == 1;
+// launcher: the arguments from (g, plan); lo_wgrad_choose decided everything else
+int lo_wgrad2_run(const LoGeom& g, const LoWgradChoice& p, const f16* x, const f16* dy, float* slab, hipStream_t st) {
+  LO_REQUIRE(p.kernel == LO_WK_WGRAD2, "lo_wgrad2_run: the plan names another weight-gradient kernel");
+  const bool s2 = !p.convt;
   Wgrad2Args a;
   a.a = s2 ? dy : x; a.f = s2 ? x : dy; a.slab = slab;
   a.B = g.B; a.Hc = s2 ? g.Hout : g.Hin; a.Wc = s2 ? g.Wout : g.Win;
   a.Ca = s2 ? g.Cout : g.Cin; a.Cf = s2 ? g.Cin : g.Cout;
-  a.nchunks = g.B * a.Hc * a.Wc / 32;
-  a.nsplit = lo_wgrad2_nsplit(g);
-  a.chunks_per_split = (a.nchunks + a.nsplit - 1) / a.nsplit;
-  a.packed_elems = 0;
-  for (int p = 0; p < g.n_phase; ++p) a.packed_elems += g.Cout * g.T[p] * g.Cin;
+  a.nchunks = p.units; a.nsplit = p.nsplit; a.chunks_per_split = p.units_per_split;
+  a.packed_elems = lo_geom_packed_elems(g);
   a.Cin = g.Cin;
-  for (int p = 0; p < 4; ++p) a.wofs[p] = p < g.n_phase ? g.wofs[p] : 0;
-  *nsplit_out = a.nsplit;
-  const int tiles = (a.Ca / 64) * ((a.Cf + 63) / 64);
-  dim3 grid(tiles * a.nsplit);
-  if (s2) hipLaunchKernelGGL((lo_wgrad_s2_mt<false>), grid, dim3(512), 0, st, a);
-  else hipLaunchKernelGGL((lo_wgrad_s2_mt<true>), grid, dim3(512), 0, st, a);
+  for (int q = 0; q < 4; ++q) a.wofs[q] = q < g.n_phase ? g.wofs[q] : 0;
+  if (s2) hipLaunchKernelGGL((lo_wgrad_s2_mt<false>), p.grid, p.block, 0, st, a);
+  else hipLaunchKernelGGL((lo_wgrad_s2_mt<true>), p.grid, p.block, 0, st, a);
   LO_LAUNCH_CHECK("wgrad_s2_mt");
   return LO_OK;
 }

@@ -14,12 +14,7 @@
 //   end: group 1 hands its accumulators to group 0 through LDS (fixed order), group 0 writes the fp32 slab
 //   output: fp32 slab [split][packed weight layout], summed in fixed order by lo_wgrad_reduce_kernel (reproducible)
 #include "lo_conv.h"
-#include <stdlib.h>
-
-__device__ __attribute__((aligned(256))) unsigned int lo_zero_page_w3[64];
-// every padding lane reads the page's base: 1 address x 16 B per lane
-static_assert(sizeof(lo_zero_page_w3) >= 1 * 16, "LDS-DMA padding lanes read 16 B at offset 0 of the zero page");
-#define LO_VMCNT(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
+#include "lo_conv_dev.h"
 
 struct Wgrad3Args {
   const f16* x;     // forward input  [B,H,W,Cin]
@@ -36,16 +31,6 @@ struct Wgrad3Args {
 unsigned long long* g_lo_wgrad3_stamps = nullptr;
 #define LO_T() __builtin_amdgcn_s_memtime()
 #endif
-
-__device__ __forceinline__ int lo_xcd_remap_w3(int bid, int total) {
-  const int q = total >> 3, r = total & 7;
-  const int xcd = bid & 7, loc = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-}
-
-// 128-byte rows, 32-byte blocks XOR-swizzled by (row >> 1) & 3: the 8 consecutive rows a 32-lane half of a transposed
-// read touches land on 8 distinct 32-byte slots of the 256-byte bank row whatever the first row is
-__device__ __forceinline__ int lo_w3_swz(int row) { return (row >> 1) & 3; }
 
 template <int TH, int TW>
 __global__ __launch_bounds__(512) void lo_wgrad3x3_mt(Wgrad3Args a) {
@@ -67,19 +52,19 @@ __global__ __launch_bounds__(512) void lo_wgrad3x3_mt(Wgrad3Args a) {
   unsigned char* const smem = smem_all + grp * (NSTAGE * STAGE);
   const int wco = wave & 1, wci = wave >> 1;
   const int tiles_ci = a.Cin >> 6, tiles = (a.Cout >> 6) * tiles_ci;
-  const int wid = lo_xcd_remap_w3(blockIdx.x, gridDim.x);
+  const int wid = lo_xcd_remap(blockIdx.x, gridDim.x);
   const int tile = wid % tiles, split = wid / tiles;       // tiles of one pixel range are adjacent: they share dy / x in L2
   const int co0 = (tile / tiles_ci) * 64, ci0 = (tile % tiles_ci) * 64;
   const int q_begin = split * a.chunks_per_split;
   const int q_end = min(a.nchunks, q_begin + a.chunks_per_split);
   const int nq = q_end - q_begin;
   const int chunks_x = a.W / TW, chunks_img = chunks_x * (a.H / TH);
-  const f16* zpage = reinterpret_cast<const f16*>(lo_zero_page_w3);
+  const f16* zpage = reinterpret_cast<const f16*>(lo_zero_page);
 
   // ---- per-lane DMA constants.  dy: one instruction per wave (rows wave*8 .. +7 of the 32); patch: q = j*4 + wave
   const int drow = wave * 8 + (lane >> 3), dpos = lane & 7;
   const int d_ty = drow / TW, d_tx = drow % TW;
-  const int d_lane = (d_ty * a.W + d_tx) * a.Cout + co0 + ((((dpos >> 1) ^ lo_w3_swz(drow)) << 1) | (dpos & 1)) * 8;
+  const int d_lane = (d_ty * a.W + d_tx) * a.Cout + co0 + ((((dpos >> 1) ^ lo_tr_swz<128>(drow)) << 1) | (dpos & 1)) * 8;
   int p_py[PJ], p_px[PJ], p_lane[PJ];
 #pragma unroll
   for (int j = 0; j < PJ; ++j) {
@@ -87,7 +72,7 @@ __global__ __launch_bounds__(512) void lo_wgrad3x3_mt(Wgrad3Args a) {
     const int py = prow / PWP, px = prow - py * PWP;
     p_py[j] = prow < PROWS ? py - 1 : -100000;             // rows past the patch read zeros
     p_px[j] = px - 1;
-    p_lane[j] = ((py - 1) * a.W + (px - 1)) * a.Cin + ci0 + ((((pos >> 1) ^ lo_w3_swz(prow)) << 1) | (pos & 1)) * 8;
+    p_lane[j] = ((py - 1) * a.W + (px - 1)) * a.Cin + ci0 + ((((pos >> 1) ^ lo_tr_swz<128>(prow)) << 1) | (pos & 1)) * 8;
   }
   // next chunk this group stages: (image, y0, x0), advanced by two chunks per call without divisions
   int nx_q = q_begin + grp;
@@ -139,7 +124,7 @@ __global__ __launch_bounds__(512) void lo_wgrad3x3_mt(Wgrad3Args a) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int R = trow + 16 * h, blk = wco * 2 + mi;
-      aoff[mi][h] = R * 128 + ((blk ^ lo_w3_swz(R)) * 32) + tsub;
+      aoff[mi][h] = R * 128 + ((blk ^ lo_tr_swz<128>(R)) * 32) + tsub;
     }
   // patch fragments: row of k index kk under tap (r, s) = (kk / TW + r) * PWP + kk % TW + s; [tap][first / second read],
   // input-channel fragment ni = 0; ni = 1 is the same address ^ 32
@@ -150,7 +135,7 @@ __global__ __launch_bounds__(512) void lo_wgrad3x3_mt(Wgrad3Args a) {
     for (int h = 0; h < 2; ++h) {
       const int kk = trow + 16 * h;
       const int R = (kk / TW + t / 3) * PWP + kk % TW + t % 3;
-      boff[t][h] = A_BYTES + R * 128 + (((wci * 2) ^ lo_w3_swz(R)) * 32) + tsub;
+      boff[t][h] = A_BYTES + R * 128 + (((wci * 2) ^ lo_tr_swz<128>(R)) * 32) + tsub;
     }
 
   f32x4 acc[9][2][2];
@@ -290,58 +275,19 @@ __global__ __launch_bounds__(512) void lo_wgrad3x3_mt(Wgrad3Args a) {
 #endif
 }
 
-// ---------------------------------------------------------------------------------------------
-// launcher side
-// ---------------------------------------------------------------------------------------------
-static inline bool wgrad3_applies(const LoGeom& g) {
-  if (g.n_phase != 1 || g.T[0] != 9 || g.in_stride != 1 || g.out_stride != 1) return false;
-  if (g.Cin % 64 || g.Cout % 64 || g.Hin != g.Hout || g.Win != g.Wout) return false;
-  if (g.Win % 16 == 0) return g.Hin % 2 == 0;
-  return g.Win == 8 && g.Hin % 4 == 0;
-}
-
-// pixel splits of the multi-tap kernel for this geometry, 0 when it does not apply
-int lo_wgrad3_nsplit(const LoGeom& g) {
-  if (!wgrad3_applies(g)) return 0;
-  const long tiles = (long)(g.Cout / 64) * (g.Cin / 64);
-  const long nchunks = (long)g.B * g.Hin * g.Win / 32;
-  // Workgroups per launch: these kernels run on the side stream BESIDE the dependent chain, and every CU one of their 512-thread
-  // workgroups holds is lost to the chain.  Round 3, sprites/s on the step (interleaved on one box) | serial time of the 8 launches:
-  //   target 256 / floor 256 (one workgroup per CU at least)   21 854-21 994 | 0.240 ms
-  //   192 / 192                                                22 375-22 499 | 0.269 ms
-  //   256 / 128                                                22 513-22 706 | 0.303 ms   <- shipped
-  //   128 / 64                                                 22 544-22 747 | 0.340 ms
-  // fewer, longer workgroups (and less slab traffic) win on the step although the launch alone takes longer
-  constexpr int target = 256, flo = 128;
-  long want = (target + tiles - 1) / tiles;
-  const long slab_bytes = (long)g.Cout * 9 * g.Cin * 4;
-  long cap = (24L << 20) / slab_bytes;                    // slab traffic (written here, re-read by the reduce pass)
-  const long floor_wgs = (flo + tiles - 1) / tiles;        // but not below this many workgroups
-  if (cap < floor_wgs) cap = floor_wgs;
-  if (want > cap) want = cap;
-  if (want > nchunks / 4) want = nchunks / 4 > 0 ? nchunks / 4 : 1;   // at least 4 chunks per split
-  if (want < 1) want = 1;
-  return (int)want;
-}
-
-int lo_wgrad3_run(const LoGeom& g, const f16* x, const f16* dy, float* slab, hipStream_t st, int* nsplit_out) {
-  LO_REQUIRE(wgrad3_applies(g), "lo_wgrad3_run: geometry not supported by the multi-tap weight-gradient kernel");
+// launcher: the arguments from (g, plan); lo_wgrad_choose decided everything else
+int lo_wgrad3_run(const LoGeom& g, const LoWgradChoice& p, const f16* x, const f16* dy, float* slab, hipStream_t st) {
+  LO_REQUIRE(p.kernel == LO_WK_WGRAD3, "lo_wgrad3_run: the plan names another weight-gradient kernel");
   Wgrad3Args a;
   a.x = x; a.dy = dy; a.slab = slab;
   a.B = g.B; a.H = g.Hin; a.W = g.Win; a.Cin = g.Cin; a.Cout = g.Cout;
-  a.nchunks = g.B * g.Hin * g.Win / 32;
-  a.nsplit = lo_wgrad3_nsplit(g);
-  a.chunks_per_split = (a.nchunks + a.nsplit - 1) / a.nsplit;
-  a.nsplit = (a.nchunks + a.chunks_per_split - 1) / a.chunks_per_split;   // no empty splits: every slab is written
-  a.packed_elems = g.Cout * 9 * g.Cin;
-  *nsplit_out = a.nsplit;
+  a.nchunks = p.units; a.nsplit = p.nsplit; a.chunks_per_split = p.units_per_split;
+  a.packed_elems = lo_geom_packed_elems(g);
 #ifdef LO_STAMPS
   a.stamps = g_lo_wgrad3_stamps;
 #endif
-  const int tiles = (g.Cout / 64) * (g.Cin / 64);
-  dim3 grid(tiles * a.nsplit);
-  if (g.Win % 16 == 0) hipLaunchKernelGGL((lo_wgrad3x3_mt<2, 16>), grid, dim3(512), 0, st, a);
-  else hipLaunchKernelGGL((lo_wgrad3x3_mt<4, 8>), grid, dim3(512), 0, st, a);
+  if (p.tw == 16) hipLaunchKernelGGL((lo_wgrad3x3_mt<2, 16>), p.grid, p.block, 0, st, a);
+  else hipLaunchKernelGGL((lo_wgrad3x3_mt<4, 8>), p.grid, p.block, 0, st, a);
   LO_LAUNCH_CHECK("wgrad3x3_mt");
   return LO_OK;
 }

@@ -124,6 +124,7 @@ WGRAD_CASES = [
     (KIND_T4, 3, 256, 128, 16),
     (KIND_T4, 1, 64, 32, 8),             # ... 32 output channels: half of the F tile is padding
     (KIND_T4, 5, 64, 64, 8),
+    (KIND_S1, 7, 128, 128, 32),          # multi-tap kernel: the slab is sized for 42 splits, 38 are launched and written
 ]
 
 
@@ -170,7 +171,8 @@ def _linear_splitk(M, K, N, nsplit, skew=0, slab_short=0):
     check_guards(xd, wd, slab, out, bdev)
 
 
-@pytest.mark.parametrize("kind,M,K,N", [(KIND_LIN, 64, 32768, 512), (KIND_LIN, 2, 256, 32768), (KIND_LIN, 5, 32768, 1024)])
+@pytest.mark.parametrize("kind,M,K,N", [(KIND_LIN, 64, 32768, 512), (KIND_LIN, 2, 256, 32768), (KIND_LIN, 5, 32768, 1024),
+                                          (KIND_LIN, 20480, 512, 512)])   # per-tap kernel: 24 splits wanted, 23 non-empty ones launched
 def test_linear_wgrad(kind, M, K, N):
     x = _rand(M, K, seed=1)
     dy = _rand(M, N, seed=2, scale=0.1)

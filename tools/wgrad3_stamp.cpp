@@ -18,23 +18,23 @@ int main(int argc, char** argv) {
   for (auto& v : hx) v = (_Float16)rnd();
   for (auto& v : hd) v = (_Float16)(0.1f * rnd());
   f16 *x, *dy; float *slab, *grad; unsigned long long* st;
-  int ns = lo_wgrad3_nsplit(g);
+  const LoWgradChoice plan = lo_wgrad_choose(g);
+  if (plan.kernel != LO_WK_WGRAD3) { printf("B=%d H=%d C=%d is not a shape of the multi-tap 3x3 kernel\n", B, H, C); return 1; }
   size_t welems = (size_t)C * 9 * C;
-  hipMalloc(&x, nx * 2); hipMalloc(&dy, nx * 2); hipMalloc(&slab, (size_t)(ns + 1) * welems * 4); hipMalloc(&grad, welems * 4);
+  hipMalloc(&x, nx * 2); hipMalloc(&dy, nx * 2); hipMalloc(&slab, lo_wgrad_slab_bytes(g)); hipMalloc(&grad, welems * 4);
   hipMemcpy(x, hx.data(), nx * 2, hipMemcpyHostToDevice); hipMemcpy(dy, hd.data(), nx * 2, hipMemcpyHostToDevice);
-  int wgs = (C / 64) * (C / 64) * ns;
+  const int wgs = (int)plan.grid.x;
   hipMalloc(&st, (size_t)wgs * 8 * 16 * 8); hipMemset(st, 0, (size_t)wgs * 8 * 16 * 8);
   g_lo_wgrad3_stamps = st;
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-  int nsplit = 0;
-  for (int i = 0; i < 3; ++i) lo_wgrad3_run(g, x, dy, slab, 0, &nsplit);
+  for (int i = 0; i < 3; ++i) lo_wgrad3_run(g, plan, x, dy, slab, 0);
   hipDeviceSynchronize();
   hipEventRecord(e0, 0);
   const int it = 10;
-  for (int i = 0; i < it; ++i) lo_wgrad3_run(g, x, dy, slab, 0, &nsplit);
+  for (int i = 0; i < it; ++i) lo_wgrad3_run(g, plan, x, dy, slab, 0);
   hipEventRecord(e1, 0); hipDeviceSynchronize();
   float ms; hipEventElapsedTime(&ms, e0, e1); ms /= it;
-  printf("B=%d H=%d C=%d: %.1f us (kernel only) %.1f TFLOP/s  workgroups=%d nsplit=%d\n", B, H, C, ms * 1e3, 2.0 * nx * 9 * C / ms / 1e9, wgs, nsplit);
+  printf("B=%d H=%d C=%d: %.1f us (kernel only) %.1f TFLOP/s  workgroups=%d nsplit=%d\n", B, H, C, ms * 1e3, 2.0 * nx * 9 * C / ms / 1e9, wgs, plan.nsplit);
   std::vector<unsigned long long> hs((size_t)wgs * 8 * 16);
   hipMemcpy(hs.data(), st, hs.size() * 8, hipMemcpyDeviceToHost);
   const char* nm[7] = {"prologue", "loop", "exchange", "store(g0)", "sum wait", "sum issue", "sum compute"};
