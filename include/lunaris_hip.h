@@ -159,6 +159,17 @@ int lo_clip_adamw_step_presummed(float* p, const float* g, float* m, float* v, s
                                  float lr, float beta1, float beta2, float eps, float weight_decay, int step, float* scratch,
                                  void* stream);
 
+/* Tool level: two passes of the optimizer step as single calls, exported for measurement only (tools/op_bench.py); the training
+ * path never calls them and a binding may leave them out.
+ * The AdamW pass alone (train_hybrid.py:921) on one flat range of n elements -- p, g, m, v: n floats -- as lo_clip_adamw_step and
+ * lo_vae_optimizer_step launch it.  norm: NULL, or 3 floats as scratch[1024..1026] ([1] multiplies the gradient, [2] == 0 skips the
+ * update); cast: NULL, or n halves = fp16(p) after the update, written by the same pass.
+ * lo_transpose_f16: dst [cols][rows] = src [rows][cols]^T, fp16, rows and cols multiples of 64: the transposed operand copies of the
+ * two Linear weights.  Both exist at this level for tools/op_bench.py --op lowrank_gathered (the materialised path, pass by pass). */
+int lo_adamw_range(float* p, const float* g, float* m, float* v, size_t n, const float* norm, float lr, float beta1, float beta2,
+                   float eps, float weight_decay, int step, void* cast, void* stream);
+int lo_transpose_f16(const void* src, void* dst, int rows, int cols, void* stream);
+
 /* ---- the VAE step executor (LunarisCoreVAE.forward / backward, lunar_generate.py:263-276) -------------------- */
 typedef struct LoVae LoVae;
 int lo_vae_create(int batch, int latent_dim, LoVae** out);
@@ -219,7 +230,7 @@ int lo_vae_join(LoVae* h, void* stream);   /* `stream` waits for the side-stream
  * inside its AdamW pass (train_hybrid.py:921).  Same update to fp32 rounding; 12 of 38 bytes of HBM traffic per parameter less.
  * Explicit-gradient backwards (the autograd path) and lo_vae_backward_phase always write every gradient.
  * lo_vae_materialize_linear_grads: writes the two gradients of the last fused backward into flat_grads after all (tests, tools). */
-int lo_vae_set_linear_factored(LoVae* h, int mode);   /* 0 off, 1 single process (above), 2 data parallel (below) */
+int lo_vae_set_linear_factored(LoVae* h, int mode);   /* 0 off, 1 single process (above), 2 / 3 data parallel (below) */
 /* Data parallel (mode 2; no reference counterpart: the reference has no distributed code).  lo_vae_backward_phase(1) then leaves the
  * two Linear layers' factors instead of their weight gradients: one contiguous block of the workspace (lo_vae_factor_block:
  * dml^T | xflat^T | Gfc^T | z^T, transposed, batch-padded fp16; 8.6 MB at batch 64 / latent 512).  The ranks all-gather the blocks
@@ -228,8 +239,43 @@ int lo_vae_set_linear_factored(LoVae* h, int mode);   /* 0 off, 1 single process
  * scale -- the all-reduce(AVG) of the per-rank gradients to fp32 rounding.  Everything else of the range is exchanged as before. */
 int lo_vae_factor_block(const LoVae* h, size_t* byte_offset, size_t* bytes);
 int lo_vae_materialize_gathered_linear_grads(LoVae* h, const void* gathered, int world, float* flat_grads, void* stream);
+/* Mode 3: as mode 2 up to the all-gather, but the averaged matrices are never written either.  Behind the all-gather and the exchange
+ * of the rest of the phase-1 range, on the stream that ran them, the caller enqueues lo_vae_gathered_early_norm: it fills
+ * scratch[512..1024) of the 1028-float optimizer scratch -- everything behind decoder.fc.weight and the two head biases from the
+ * averaged flat_grads, the two matrices as ||sum_r dY_r^T X_r||_F^2 / (loss scale * world)^2 from Gram matrices over the combined
+ * batch axis of world * Bp samples (Bp = batch rounded up to 32), cross-rank terms included -- and remembers `gathered` and `world`.
+ * lo_vae_optimizer_step (LO_OPT_PRESUMMED required, serial or pipelined) then forms every gradient tile inside its AdamW pass with
+ * the contraction running over all ranks' blocks in rank order (no atomics: every rank gets the same bits from the same buffer),
+ * and writes the fp16 operand copies like mode 1.  Limits: world * Bp <= 512 (8 ranks at batch 64); above that the norm call
+ * returns -1 and the caller stays in mode 2.
+ *   gathered      world * lo_vae_factor_block bytes, block r at r * bytes; it must stay unchanged until the work
+ *                 lo_vae_optimizer_step enqueues has read it.  The next step's lo_vae_backward_phase(1) waits for that work, so a
+ *                 stream ordered behind that call may overwrite the buffer.
+ *   gram_scratch  lo_vae_gathered_scratch_bytes(h, world) bytes = 2 * (world * Bp)^2 floats, contents unspecified
+ * lo_vae_linear_factored returns the mode (1 or 3) while flat_grads does not hold the two matrices, 0 otherwise (mode 2 included);
+ * lo_vae_materialize_linear_grads writes them out after all: in mode 3 the averaged ones, from the remembered gathered buffer. */
+size_t lo_vae_gathered_scratch_bytes(const LoVae* h, int world);   /* 0: world * Bp is above 512 */
+int lo_vae_gathered_early_norm(LoVae* h, const void* gathered, int world, float* gram_scratch, const float* flat_grads, float* scratch,
+                               void* stream);
 int lo_vae_linear_factored(const LoVae* h);
 int lo_vae_materialize_linear_grads(LoVae* h, void* ws, float* flat_grads, void* stream);
+/* The two passes of mode 3 on plain pointers.  W is [N][K] fp32 (N % 64 == 0, K % 64 == 0); its averaged gradient is
+ * gscale * sum_r dY_r^T X_r with the factors TRANSPOSED and batch-padded, fp16: xt [K][Bp], yt [N][Bp] per rank, columns
+ * batch .. Bp - 1 zero (Bp = batch rounded up to 32, batch <= 128), rank r's copy rank_stride_elems * r elements behind rank 0's
+ * (a multiple of 8).  world * Bp <= 512, else -1.
+ * lo_lowrank_gathered_adamw: AdamW (train_hybrid.py:921) of W in place.  p, m, v: N * K floats; cast: N * K halves = fp16(p) after
+ * the update; cast_t: K * N halves = its transpose (either may be NULL); xt: (world - 1) * rank_stride_elems + K * Bp halves, yt:
+ * (world - 1) * rank_stride_elems + N * Bp; norm: NULL, or 3 floats as scratch[1024..1026] of lo_clip_adamw_step -- [1] multiplies
+ * the gradient, [2] == 0 skips the update.
+ * lo_lowrank_gathered_sumsq: partial[0..127] = 128 partial sums (every one written) of scale^2 * ||sum_r dY_r^T X_r||_F^2.  fshort_t /
+ * flong_t: the two factors ([n_short][Bp], [n_long][Bp]; row lengths multiples of 32; which of X, dY is which does not matter), sizes
+ * as xt / yt; gram_scratch: lo_lowrank_gathered_scratch_bytes(world, batch) bytes = (world * Bp)^2 floats, contents unspecified. */
+size_t lo_lowrank_gathered_scratch_bytes(int world, int batch);   /* 0: unsupported */
+int lo_lowrank_gathered_sumsq(const void* fshort_t, int n_short, const void* flong_t, int n_long, size_t rank_stride_elems, int world,
+                              int batch, float scale, float* gram_scratch, float* partial, void* stream);
+int lo_lowrank_gathered_adamw(float* p, float* m, float* v, void* cast, void* cast_t, const void* xt, const void* yt,
+                              size_t rank_stride_elems, int world, int N, int K, int batch, float gscale, const float* norm, float lr,
+                              float beta1, float beta2, float eps, float weight_decay, int step, void* stream);
 /* forward.  eps: explicit N(0,1) noise [B,L] or NULL (on-device counter RNG with `seed`).  target: images for the fused
  * MSE partial sums or NULL.  Outputs recon [B,3,128,128], mu, logvar [B,L] (fp32). */
 int lo_vae_forward(LoVae* h, const float* x, const float* eps, uint64_t seed, const float* flat_params, void* ws,

@@ -94,6 +94,13 @@ SIGNATURES = {
     "lo_vae_factor_block": (i32, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "lo_vae_materialize_gathered_linear_grads": (i32, [vp, vp, i32, f32p, vp]),
     "lo_vae_materialize_linear_grads": (i32, [vp, vp, f32p, vp]),
+    "lo_adamw_range": (i32, [f32p, f32p, f32p, f32p, sz, f32p] + [flt] * 5 + [i32, vp, vp]),
+    "lo_transpose_f16": (i32, [vp, vp, i32, i32, vp]),
+    "lo_vae_gathered_scratch_bytes": (sz, [vp, i32]),
+    "lo_vae_gathered_early_norm": (i32, [vp, vp, i32, f32p, f32p, f32p, vp]),
+    "lo_lowrank_gathered_scratch_bytes": (sz, [i32, i32]),
+    "lo_lowrank_gathered_sumsq": (i32, [vp, i32, vp, i32, sz, i32, i32, flt, f32p, f32p, vp]),
+    "lo_lowrank_gathered_adamw": (i32, [f32p, f32p, f32p, vp, vp, vp, vp, sz, i32, i32, i32, i32, flt, f32p] + [flt] * 5 + [i32, vp]),
     "lo_vae_gradnorm_presummed": (i32, [vp]),
     "lo_clip_adamw_step_presummed": (i32, [f32p, f32p, f32p, f32p, sz, sz, flt, flt, flt, flt, flt, flt, i32, f32p, vp]),
     "lo_vae_destroy": (None, [vp]),

@@ -77,4 +77,11 @@ int lo_adamw_lowrank(const LoLowrankMat* mats, int nmat, int B, float gscale, co
 int lo_lowrank_materialize(float* gout, const f16* xt, const f16* yt, int N, int K, int B, float gscale, hipStream_t st);
 int lo_lowrank_materialize_gathered(float* gout, const f16* xt, const f16* yt, size_t rank_stride_elems, int world, int N, int K, int B,
                                     float gscale, hipStream_t st);
+// data parallel, mode 3: the same two from `world` gathered factor blocks (rank r's copy of a factor rank_stride_elems * r further on);
+// world * lo_lowrank_bp(B) <= 512.  LoLowrankNorm's factors are then the TRANSPOSED ones ([n][Bp]); gram: [KT][KT] per layer
+bool lo_lowrank_gathered_applies(int world, int B);
+size_t lo_lowrank_gathered_gram_elems(int world, int B);   // fp32 elements of Gram scratch for two layers: 2 (world Bp)^2
+int lo_adamw_lowrank_gathered(const LoLowrankMat* mats, int nmat, size_t rank_stride_elems, int world, int B, float gscale, const float* norm,
+                              float lr, float beta1, float beta2, float eps, float wd, int step, hipStream_t st);
+int lo_lowrank_sumsq_gathered(const LoLowrankNorm* layers, int nlayers, size_t rank_stride_elems, int world, int B, float scale, hipStream_t st);
 int lo_sumsq_blocks(const float* g, size_t n, float* partial, int nblocks, hipStream_t st);   // lo_train.hip: partial[0 .. nblocks)

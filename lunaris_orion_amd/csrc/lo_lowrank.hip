@@ -18,6 +18,7 @@
 // lo_vae_materialize_linear_grads.  No reference counterpart below aten::linear_backward / torch.optim.AdamW.
 #include "lo_common.h"
 #include "lo_internal.h"
+#include "lo_conv_dev.h"
 #include <math.h>
 #include <string.h>
 #include <stdlib.h>
@@ -359,6 +360,267 @@ __global__ __launch_bounds__(256) void lo_lowrank_materialize_gathered_kernel(Lo
 }
 
 // ---------------------------------------------------------------------------------------------
+// Data parallel, mode 3: the factored AdamW and the Gram norm straight from the gathered blocks -- the averaged matrices are never
+// written.  KT = world * Bp <= 512 is the combined batch axis (rank-major: rank r's Bp columns at 32-sample steps r Bp / 32 ..).
+//
+// AdamW.  lo_adamw_lowrank keeps a band's X^T fragments in registers (4 x Bp / 32 x 4 VGPRs); at KT = 512 that alone would be 256.
+// Here a workgroup of NW waves owns ONE 64-column band and NW x TPW row tiles of 64 rows: it stages the band's X^T rows of all ranks
+// in LDS once (64 rows x KT halves, 64 KB at 512; rows 16 bytes apart from a multiple of 64 bytes.  By the bank rule, not by a
+// counter: the 16-lane groups of a ds_read_b128 fragment read are then 2-way at worst, which at KT = 512 is about a quarter of
+// the LDS time that the HBM traffic of the same group leaves room for), and
+// every wave walks its row tiles (w, w + NW of the chunk) in 16-row groups like the single-process kernel: the dY^T fragments of group
+// g + 1 (L2 / Infinity-Cache resident) and its p / m / v are loaded behind the MFMAs of group g, before g's element update; a wave's
+// first loads are issued ahead of the staging.  NW = 4, one tile per wave up to KT = 256 (53 / 70 KB of LDS: two workgroups per
+// CU); NW = 8, two tiles per wave above (137 KB: one workgroup per CU, the same 8 waves, the 64 KB of staging shared by 16 tiles).
+// Neighbouring workgroups own neighbouring bands, as neighbouring waves do in lo_adamw_lowrank: what is resident on the chip covers
+// whole rows of the matrix.  (lo_xcd_remap -- every XCD on its own contiguous range of bands, so that the 8 bands of decoder.fc
+// that share 1 MB of Gfc^T meet in one L2 -- is NOT used: with it all XCDs start in the same two 16 KB column windows of
+// fc_mu | fc_logvar's 128 KB rows, and the pass was 9 % slower at KT = 64.)  Measured: profiles/dp_factored_adamw_ab.md; still
+// 1.5 x the single-process kernel, whose four waves per workgroup cover 1 KB of every row where this one covers 256 bytes.
+// The contraction runs rank by rank, 32 samples at a time, in ONE accumulator per tile: a fixed order, no atomics -- every rank
+// forms the same bits from the same gathered buffer.
+// ---------------------------------------------------------------------------------------------
+struct LoGatherPair { LoLowrankArgs l[2]; int nwg0, world; size_t rstride; };
+template <int KSMAX, int NW, int TPW>
+__global__ __launch_bounds__(64 * NW) void lo_adamw_lowrank_gathered_kernel(LoGatherPair A) {
+  constexpr int XP = KSMAX * 32 + 8;                     // LDS pitch of a staged X^T row in halves
+  __shared__ __attribute__((aligned(16))) f16 xs[64 * XP];
+  __shared__ __attribute__((aligned(16))) f16 tbuf[NW][64 * LR_TP];
+  const bool second = (int)blockIdx.x >= A.nwg0;
+  const LoLowrankArgs& a = second ? A.l[1] : A.l[0];
+  const float coef = a.norm ? a.norm[1] : 1.0f;
+  if (a.norm && a.norm[2] == 0.f) return;                // non-finite norm / lost launch: the update is skipped
+  const int bid = second ? (int)blockIdx.x - A.nwg0 : (int)blockIdx.x;
+  // neighbouring workgroups own neighbouring bands: what is resident on the chip at any moment covers whole rows of the matrix
+  const int bands = a.K / 64, tiles_n = a.N / 64;
+  const int band = bid % bands, chunk = bid / bands, k0 = band * 64;
+  const int Bp = a.Bp, KT = A.world * Bp, KS = KT / 32, c8n = KT / 8;
+  const int lane = threadIdx.x & 63, l15 = lane & 15, lq = lane >> 4, wave = threadIdx.x >> 6;
+  const int tile0 = chunk * (TPW * NW) + wave;
+  const bool live = tile0 < tiles_n;                     // a wave without a row tile only helps staging
+  const int ngroups = TPW == 2 && tile0 + NW < tiles_n ? 8 : 4;
+  const float step_size = a.lr / a.bc1, decay = 1.0f - a.lr * a.wd, omb1 = 1.0f - a.beta1, omb2 = 1.0f - a.beta2;
+  size_t yoff[KSMAX];                                    // where 32-sample step ks starts inside a dY^T row: rank block + column (wave-uniform)
+#pragma unroll
+  for (int ks = 0; ks < KSMAX; ++ks) {
+    const int col = 32 * ks, r = col / Bp;
+    yoff[ks] = (size_t)r * A.rstride + (col - r * Bp);
+  }
+  f32x4 pv[2][4], mv[2][4], vv[2][4], acc[4];
+  f16x8 yf[KSMAX];
+  auto row_of = [&](int g) { return (size_t)((tile0 + NW * (g >> 2)) * 64 + 16 * (g & 3) + l15); };
+  auto load_y = [&](int g) {
+    const f16* yr = a.yt + row_of(g) * Bp + 8 * lq;
+#pragma unroll
+    for (int ks = 0; ks < KSMAX; ++ks)
+      if (ks < KS) yf[ks] = *reinterpret_cast<const f16x8*>(yr + yoff[ks]);
+  };
+  auto load_pmv = [&](int g, int buf) {
+    const size_t base = row_of(g) * a.K + k0 + 4 * lq;
+#pragma unroll
+    for (int ik = 0; ik < 4; ++ik) {
+      pv[buf][ik] = *reinterpret_cast<const f32x4*>(a.p + base + 16 * ik);
+      mv[buf][ik] = *reinterpret_cast<const f32x4*>(a.m + base + 16 * ik);
+      vv[buf][ik] = *reinterpret_cast<const f32x4*>(a.v + base + 16 * ik);
+    }
+  };
+  auto tiles = [&]() {
+#pragma unroll
+    for (int ik = 0; ik < 4; ++ik) acc[ik] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < KSMAX; ++ks)
+      if (ks < KS) {
+#pragma unroll
+        for (int ik = 0; ik < 4; ++ik) {
+          const f16x8 xf = *reinterpret_cast<const f16x8*>(&xs[(16 * ik + l15) * XP + 32 * ks + 8 * lq]);
+          acc[ik] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xf, yf[ks], acc[ik], 0, 0, 0);
+        }
+      }
+  };
+  auto update = [&](int g, int buf) {
+    const size_t base = row_of(g) * a.K + k0 + 4 * lq;
+#pragma unroll
+    for (int ik = 0; ik < 4; ++ik) {
+      f32x4 pe = pv[buf][ik], me = mv[buf][ik], ve = vv[buf][ik];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float pr = pe[r], mr = me[r], vr = ve[r];
+        lo_adamw_elem_lr(pr, acc[ik][r] * a.gscale, mr, vr, coef, decay, omb1, a.beta2, omb2, a.bc2_sqrt, a.eps, step_size);
+        pe[r] = pr; me[r] = mr; ve[r] = vr;
+      }
+      *reinterpret_cast<f32x4*>(a.p + base + 16 * ik) = pe;
+      *reinterpret_cast<f32x4*>(a.m + base + 16 * ik) = me;
+      *reinterpret_cast<f32x4*>(a.v + base + 16 * ik) = ve;
+      if (a.cast) *reinterpret_cast<f16x4*>(a.cast + base + 16 * ik) = (f16x4){(f16)pe[0], (f16)pe[1], (f16)pe[2], (f16)pe[3]};
+      if (a.cast_t) {
+        f16* tb = &tbuf[wave][0];
+        const int nloc = 16 * (g & 3) + l15;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) tb[(16 * ik + 4 * lq + r) * LR_TP + nloc] = (f16)pe[r];
+      }
+    }
+    if (a.cast_t && (g & 3) == 3) {
+      // the tile's four groups are in (see lo_adamw_lowrank_kernel): 64 rows (k) x 64 columns (n), 128 contiguous bytes per row
+      __builtin_amdgcn_wave_barrier();
+      const f16* tb = &tbuf[wave][0];
+      const size_t n_first = (size_t)(tile0 + NW * (g >> 2)) * 64;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int kk = 8 * j + (lane >> 3), ch = lane & 7;
+        *reinterpret_cast<f16x8*>(a.cast_t + (size_t)(k0 + kk) * a.N + n_first + 8 * ch) = *reinterpret_cast<const f16x8*>(tb + kk * LR_TP + 8 * ch);
+      }
+      __builtin_amdgcn_wave_barrier();
+    }
+  };
+  if (live) { load_y(0); load_pmv(0, 0); }
+  for (int i = threadIdx.x; i < 64 * c8n; i += 64 * NW) {
+    const int row = i / c8n, col = (i - row * c8n) * 8, r = col / Bp, b = col - r * Bp;
+    *reinterpret_cast<f16x8*>(&xs[row * XP + col]) = *reinterpret_cast<const f16x8*>(a.xt + (size_t)r * A.rstride + (size_t)(k0 + row) * Bp + b);
+  }
+  __syncthreads();
+  if (!live) return;                                     // (no workgroup barrier below)
+  for (int g = 0; g < ngroups; g += 2) {                 // ngroups is 4 or 8
+    tiles();
+    load_y(g + 1);
+    load_pmv(g + 1, 1);
+    update(g, 0);
+    tiles();
+    if (g + 2 < ngroups) { load_y(g + 2); load_pmv(g + 2, 0); }
+    update(g + 1, 1);
+  }
+}
+
+// The norm.  ||sum_r dY_r^T X_r||_F^2 = sum_{b,b'} (dY dY^T)[b,b'] (X X^T)[b,b'] over the combined batch axis, cross-rank terms
+// included.  The gathered factors are TRANSPOSED ([n][Bp] per rank): the Gram contraction runs over their slow axis, so tiles of
+// [64 c][128 b] are staged in LDS (the next tile's loads in flight behind the barrier; rows c >= n are zero) and the MFMA
+// fragments come from transposed LDS reads, with the image and block swizzle of the
+// weight-gradient kernels (lo_tr_swz<256>, lo_conv_dev.h).  (Transposing the blocks back first would write and re-read world x 8.6 MB
+// per step for a layout only this norm wants; the staged form reads each factor once per 128-sample block row or column.)
+// A workgroup owns one pair (I <= J) of 128-sample blocks, its four waves a 64 x 64 quarter each (16 accumulator tiles); the Gram
+// matrix is symmetric, so off-diagonal pairs count twice and pairs I > J are neither computed nor stored.
+//   DOT = false  the factor with the short rows: the pair's block of its Gram matrix [KT][KT] (all c steps in one workgroup)
+//   DOT = true   the factor with the long rows, one c chunk per workgroup: partial[slot] = weight * scale^2 * sum over the block of
+//                small[b][b'] * (sum_{c in chunk} src[c][b] src[c][b'])  -- one slot per workgroup, added in wave order through LDS;
+//                slots beyond pairs x chunks are zeroed.  (A slot of an off-diagonal pair can be negative; their sum is the norm.)
+struct LoGramTLayer { const f16* fshort; const f16* flong; float* gram; float* partial; int n_short, n_long, chunks, per, nslots; };
+struct LoGramTJobs { LoGramTLayer l[2]; size_t rstride; int Bp, KT, nb; float scale2; };
+template <bool DOT>
+__global__ __launch_bounds__(256) void lo_gram_gathered_kernel(LoGramTJobs J) {
+  __shared__ __attribute__((aligned(1024))) unsigned char smem[2][2][64 * 256];      // [buffer][side][64 c rows][128 b]
+  __shared__ float wsum[4];
+  const LoGramTLayer L = J.l[blockIdx.y];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave & 1, wn = wave >> 1;
+  const int nb = J.nb, npairs = nb * (nb + 1) / 2, KT = J.KT, Bp = J.Bp;
+  const int slot = blockIdx.x, chunks = DOT ? L.chunks : 1;
+  const int pair = slot / chunks, chunk = slot - pair * chunks;
+  if (pair >= npairs) {
+    if (DOT && tid == 0 && slot < L.nslots) L.partial[slot] = 0.f;
+    return;
+  }
+  int bI = 0, rem = pair;
+  while (rem >= nb - bI) { rem -= nb - bI; ++bI; }
+  const int bJ = bI + rem;
+  const f16* src = DOT ? L.flong : L.fshort;
+  const int n = DOT ? L.n_long : L.n_short, steps = (n + 63) / 64;
+  const int s0 = DOT ? chunk * L.per : 0, s1 = DOT ? (s0 + L.per < steps ? s0 + L.per : steps) : steps;
+  // staging: thread -> four 16-byte chunks per side (row = c inside the step, pos = chunk of the 128 samples); samples >= KT are zero
+  size_t goff[2][4];
+  bool gok[2][4];
+  int grow[4], soff[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int q = tid + 256 * j, row = q >> 4, pos = q & 15;
+    grow[j] = row;
+    soff[j] = row * 256 + ((((pos >> 1) ^ lo_tr_swz<256>(row)) << 1) | (pos & 1)) * 16;
+#pragma unroll
+    for (int side = 0; side < 2; ++side) {
+      const int b = (side ? bJ : bI) * 128 + pos * 8, r = b / Bp;
+      gok[side][j] = b < KT;
+      goff[side][j] = (size_t)r * J.rstride + (size_t)row * Bp + (b - r * Bp);
+    }
+  }
+  f16x8 reg[2][4];
+  auto gload = [&](int s) {
+#pragma unroll
+    for (int side = 0; side < 2; ++side)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (gok[side][j] && s * 64 + grow[j] < n) z = *reinterpret_cast<const f16x8*>(src + goff[side][j] + (size_t)s * 64 * Bp);
+        reg[side][j] = z;
+      }
+  };
+  // transposed fragment reads as in lo_wgrad_tn: per 32 rows, lane group q reads rows 4q .. 4q + 3 and 16 + 4q .. 16 + 4q + 3 --
+  // the same k permutation for both operands
+  const int q16 = lane >> 4, i16 = lane & 15;
+  const int trow = 4 * q16 + (i16 >> 2), tsub = (i16 & 3) * 8;
+  int aoff[4][4], boff[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+      const int R = trow + 16 * h;
+      aoff[i][h] = R * 256 + (((wm * 4 + i) ^ lo_tr_swz<256>(R)) * 32) + tsub;
+      boff[i][h] = 64 * 256 + R * 256 + (((wn * 4 + i) ^ lo_tr_swz<256>(R)) * 32) + tsub;
+    }
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  gload(s0);
+  int buf = 0;
+  for (int s = s0; s < s1; ++s) {
+    unsigned char* sb = &smem[buf][0][0];
+#pragma unroll
+    for (int side = 0; side < 2; ++side)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) *reinterpret_cast<f16x8*>(sb + side * 64 * 256 + soff[j]) = reg[side][j];
+    __syncthreads();               // one barrier per step: the other buffer is rewritten only after every wave has passed this one
+    if (s + 1 < s1) gload(s + 1);
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      f16x8 af[4], bf[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        h16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16((h16x4 __attribute__((address_space(3)))*)(sb + aoff[i][2 * kk]));
+        h16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4f16((h16x4 __attribute__((address_space(3)))*)(sb + aoff[i][2 * kk + 1]));
+        af[i] = (f16x8){(f16)lo[0], (f16)lo[1], (f16)lo[2], (f16)lo[3], (f16)hi[0], (f16)hi[1], (f16)hi[2], (f16)hi[3]};
+        lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16((h16x4 __attribute__((address_space(3)))*)(sb + boff[i][2 * kk]));
+        hi = __builtin_amdgcn_ds_read_tr16_b64_v4f16((h16x4 __attribute__((address_space(3)))*)(sb + boff[i][2 * kk + 1]));
+        bf[i] = (f16x8){(f16)lo[0], (f16)lo[1], (f16)lo[2], (f16)lo[3], (f16)hi[0], (f16)hi[1], (f16)hi[2], (f16)hi[3]};
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i], bf[j], acc[i][j], 0, 0, 0);
+    }
+    buf ^= 1;
+  }
+  // acc[i][j][r]: b = 128 I + 64 wm + 16 i + 4 (lane >> 4) + r,  b' = 128 J + 64 wn + 16 j + (lane & 15)
+  float sum = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int bc = bJ * 128 + wn * 64 + 16 * j + i16;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int br = bI * 128 + wm * 64 + 16 * i + 4 * q16 + r;
+        if (br < KT && bc < KT) {
+          if (DOT) sum += acc[i][j][r] * L.gram[(size_t)br * KT + bc];
+          else L.gram[(size_t)br * KT + bc] = acc[i][j][r];
+        }
+      }
+    }
+  if (!DOT) return;
+  sum = lo_wave_sum(sum);
+  if (lane == 0) wsum[wave] = sum;
+  __syncthreads();
+  if (tid == 0) L.partial[slot] = ((wsum[0] + wsum[1]) + (wsum[2] + wsum[3])) * (bI == bJ ? 1.f : 2.f) * J.scale2;
+}
+
+// ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
 int lo_lowrank_bp(int B) { return (B + 31) / 32 * 32; }
@@ -493,5 +755,91 @@ int lo_lowrank_materialize_gathered(float* gout, const f16* xt, const f16* yt, s
   LoProfScope _p("lo_lowrank_materialize_gathered", 2.0 * a.Bp * world * (double)N * K, 4.0 * (double)N * K, st);
   hipLaunchKernelGGL(lo_lowrank_materialize_gathered_kernel, dim3(nblk), dim3(256), 0, st, a);
   LO_LAUNCH_CHECK("lowrank_materialize_gathered");
+  return LO_OK;
+}
+
+// ---- data parallel, mode 3: straight from the gathered blocks ---------------------------------------------------------------------
+template <typename... P>
+static bool lo_aligned16(const P*... p) { return ((0 | ... | reinterpret_cast<uintptr_t>(p)) & 15) == 0; }   // null pointers pass
+bool lo_lowrank_gathered_applies(int world, int B) { return world >= 1 && B >= 1 && B <= 128 && (long long)world * lo_lowrank_bp(B) <= 512; }
+size_t lo_lowrank_gathered_gram_elems(int world, int B) { const size_t kt = (size_t)world * lo_lowrank_bp(B); return 2 * kt * kt; }
+
+// AdamW of up to two weight matrices whose AVERAGED gradient is gscale * sum_r dY_r^T X_r: xt / yt point at the factor inside rank 0's
+// block, rank r's copy sits rank_stride_elems further on per rank.  gscale carries 1 / (loss scale * world).
+int lo_adamw_lowrank_gathered(const LoLowrankMat* mats, int nmat, size_t rank_stride_elems, int world, int B, float gscale, const float* norm,
+                              float lr, float beta1, float beta2, float eps, float wd, int step, hipStream_t st) {
+  LO_REQUIRE(nmat >= 1 && nmat <= 2, "lo_adamw_lowrank_gathered: one or two matrices");
+  const int Bp = lo_lowrank_bp(B);
+  LO_REQUIRE(lo_lowrank_gathered_applies(world, B), "lo_adamw_lowrank_gathered: world %d x padded batch %d is outside the combined rank the "
+             "gathered update is built for (1 .. 512)", world, Bp);
+  LO_REQUIRE(rank_stride_elems % 8 == 0, "lo_adamw_lowrank_gathered: rank stride %zu must be a multiple of 8 elements (16-byte loads)", rank_stride_elems);
+  LoGatherPair A;
+  memset(&A, 0, sizeof(A));
+  A.world = world; A.rstride = rank_stride_elems;
+  const int KS = world * Bp / 32, nw = KS <= 8 ? 4 : 8, tpw = KS <= 8 ? 1 : 2;   // waves per workgroup, row tiles per wave
+  double bytes = 0, flops = 0;
+  int nwg[2] = {0, 0};
+  for (int i = 0; i < nmat; ++i) {
+    const LoLowrankMat& mt = mats[i];
+    LO_REQUIRE(lo_lowrank_applies(B, mt.N, mt.K), "lo_adamw_lowrank_gathered: shape B=%d N=%d K=%d not supported", B, mt.N, mt.K);
+    LO_REQUIRE(lo_aligned16(mt.p, mt.m, mt.v, mt.cast, mt.cast_t, mt.xt, mt.yt), "lo_adamw_lowrank_gathered: every tensor pointer must be 16-byte aligned");
+    LoLowrankArgs& a = A.l[i];
+    a.p = mt.p; a.m = mt.m; a.v = mt.v; a.cast = mt.cast; a.cast_t = mt.cast_t; a.gout = nullptr; a.xt = mt.xt; a.yt = mt.yt; a.N = mt.N; a.K = mt.K; a.Bp = Bp;
+    a.gscale = gscale; a.norm = norm; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = wd;
+    a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+    a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+    const double elems = (double)mt.N * mt.K;
+    bytes += (24.0 + (mt.cast ? 2.0 : 0.0) + (mt.cast_t ? 2.0 : 0.0)) * elems;
+    flops += 2.0 * world * Bp * elems;
+    nwg[i] = (mt.K / 64) * ((mt.N / 64 + tpw * nw - 1) / (tpw * nw));
+  }
+  A.nwg0 = nwg[0];
+  LoProfScope _p("lo_adamw_lowrank_gathered", flops, bytes, st);
+#define LO_LG(KSV, NWV, TPWV) LO_LAUNCH_STOP((lo_adamw_lowrank_gathered_kernel<KSV, NWV, TPWV>), dim3(nwg[0] + nwg[1]), dim3(64 * NWV), 0, st, A)
+  if (KS <= 4) LO_LG(4, 4, 1);
+  else if (KS <= 8) LO_LG(8, 4, 1);
+  else LO_LG(16, 8, 2);
+#undef LO_LG
+  LO_LAUNCH_CHECK("adamw_lowrank_gathered");
+  return LO_OK;
+}
+
+// ||sum_r dY_r^T X_r||_F^2 * scale^2 of up to two Linear layers into their partial-sum slots (every slot is written).  fshort / flong:
+// the layer's two factors, TRANSPOSED ([n_short][Bp], [n_long][Bp] fp16, padding columns zero), inside rank 0's block; gram: [KT][KT]
+// fp32 scratch per layer (KT = world * Bp; lo_lowrank_gathered_gram_elems for two layers).
+int lo_lowrank_sumsq_gathered(const LoLowrankNorm* layers, int nlayers, size_t rank_stride_elems, int world, int B, float scale, hipStream_t st) {
+  const int Bp = lo_lowrank_bp(B);
+  LO_REQUIRE(nlayers >= 1 && nlayers <= 2, "lo_lowrank_sumsq_gathered: one or two layers");
+  LO_REQUIRE(lo_lowrank_gathered_applies(world, B), "lo_lowrank_sumsq_gathered: world %d x padded batch %d is outside the combined rank the "
+             "gathered norm is built for (1 .. 512)", world, Bp);
+  LO_REQUIRE(rank_stride_elems % 8 == 0, "lo_lowrank_sumsq_gathered: rank stride %zu must be a multiple of 8 elements (16-byte loads)", rank_stride_elems);
+  LoGramTJobs J;
+  memset(&J, 0, sizeof(J));
+  J.rstride = rank_stride_elems; J.Bp = Bp; J.KT = world * Bp; J.nb = (J.KT + 127) / 128; J.scale2 = scale * scale;
+  const int npairs = J.nb * (J.nb + 1) / 2;
+  int maxslots = 0;
+  double bytes = 0, flops = 0;
+  for (int i = 0; i < nlayers; ++i) {
+    const LoLowrankNorm& in = layers[i];
+    LO_REQUIRE(in.n_short >= 32 && in.n_long >= 32 && in.n_short % 32 == 0 && in.n_long % 32 == 0, "lo_lowrank_sumsq_gathered: row lengths must be multiples of 32");
+    LO_REQUIRE(lo_aligned16(in.fshort, in.flong), "lo_lowrank_sumsq_gathered: the factor pointers must be 16-byte aligned");
+    int chunks = in.nslots / npairs;
+    LO_REQUIRE(chunks >= 1, "lo_lowrank_sumsq_gathered: %d partial slots are too few", in.nslots);
+    const int steps = (in.n_long + 63) / 64;     // 64 rows of the long factor per step
+    if (chunks > steps) chunks = steps;
+    const int per = (steps + chunks - 1) / chunks;
+    chunks = (steps + per - 1) / per;
+    LoGramTLayer& l = J.l[i];
+    l.fshort = in.fshort; l.flong = in.flong; l.gram = in.gram; l.partial = in.partial;
+    l.n_short = in.n_short; l.n_long = in.n_long; l.chunks = chunks; l.per = per; l.nslots = in.nslots;
+    maxslots = in.nslots > maxslots ? in.nslots : maxslots;
+    bytes += 2.0 * J.KT * ((double)in.n_short + in.n_long);
+    flops += 2.0 * 128 * 128 * npairs * ((double)in.n_short + in.n_long);
+  }
+  LoProfScope _p("lo_lowrank_sumsq_gathered", flops, bytes, st);
+  hipLaunchKernelGGL((lo_gram_gathered_kernel<false>), dim3(npairs, nlayers), dim3(256), 0, st, J);
+  LO_LAUNCH_CHECK("gram_gathered_small");
+  hipLaunchKernelGGL((lo_gram_gathered_kernel<true>), dim3(maxslots, nlayers), dim3(256), 0, st, J);
+  LO_LAUNCH_CHECK("gram_gathered_dot");
   return LO_OK;
 }

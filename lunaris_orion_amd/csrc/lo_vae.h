@@ -113,6 +113,11 @@ struct LoVae {
   // backward has left this step's factors and the Gram part of the gradient norm; fac_scale: 1 / loss scale of that backward
   bool lin_factored = false, fac_ready = false;
   bool lin_factored_dp = false;   // data parallel: phase 1 leaves the factors (no Linear weight gradients); the ranks all-gather them
+  // ... and mode 3 on top of it: norm and AdamW read the gathered blocks (lo_vae_gathered_early_norm remembers where they are; the
+  // caller keeps the buffer alive and unchanged until the step that follows has read it -- see lo_vae_gathered_early_norm)
+  bool lin_gathered = false;
+  const f16* fac_gathered = nullptr;
+  int fac_world = 0;
   int Bp = 0;
   size_t o_fac_dmlT = 0, o_fac_xT = 0, o_fac_gfcT = 0, o_fac_zT = 0, o_gram = 0;
   float fac_scale = 1.f;
@@ -194,6 +199,13 @@ struct LoProfTag {
   void end() { g_lo_prof_tag = nullptr; }     // ahead of the scope's end: what is launched next keeps its own name
   ~LoProfTag() { end(); }
 };
+
+// the optimizer step forms the two Linear weight gradients from factors (this rank's: mode 1; the gathered blocks: mode 3)
+static inline bool vae_fac_opt(const LoVae* h) { return h->lin_factored || h->lin_gathered; }
+// Gathered factor blocks (data parallel): every rank's block keeps the workspace's layout dml^T | xflat^T | Gfc^T | z^T.  Elements from
+// one rank's block to the next, and where the factor at workspace offset o_fac sits inside rank 0's block of `gathered`:
+static inline size_t vae_fac_block_elems(const LoVae* h) { return (h->o_gram - h->o_fac_dmlT) / 2; }
+static inline const f16* vae_fac_in_block(const LoVae* h, const f16* gathered, size_t o_fac) { return gathered + (o_fac - h->o_fac_dmlT) / 2; }
 
 // ---- across the units ------------------------------------------------------------------------------------------------------------
 int vae_flush_deferred(LoVae* h, hipStream_t after_main);    // lo_vae_opt.hip: enqueue a pipelined optimizer step's tail

@@ -330,12 +330,52 @@ extern "C" int lo_vae_gradnorm_presummed(const LoVae* h) { return h && h->norm_s
 // its AdamW pass.  Batch <= 128.  Explicit-gradient (autograd) backwards and the phased data-parallel backward are not affected.
 extern "C" int lo_vae_set_linear_factored(LoVae* h, int on) {
   LO_REQUIRE(h, "lo_vae_set_linear_factored: null handle");
-  LO_REQUIRE(on >= 0 && on <= 2, "lo_vae_set_linear_factored: mode must be 0 (off), 1 (single process) or 2 (data parallel: factors only)");
+  LO_REQUIRE(on >= 0 && on <= 3, "lo_vae_set_linear_factored: mode must be 0 (off), 1 (single process), 2 (data parallel: factors only) "
+             "or 3 (data parallel: factored AdamW and norm from the gathered factors)");
   if (on) LO_REQUIRE(lo_lowrank_applies(h->B, 2 * h->L, 32768) && lo_lowrank_applies(h->B, 32768, h->L),
                      "lo_vae_set_linear_factored: batch %d is above the rank the factored update is built for (128)", h->B);
   h->lin_factored = on == 1;
-  h->lin_factored_dp = on == 2;
+  h->lin_factored_dp = on == 2 || on == 3;
+  h->lin_gathered = on == 3;
   h->fac_ready = false;
+  h->fac_gathered = nullptr;
+  h->fac_world = 0;
+  return LO_OK;
+}
+// Mode 3: the gathered blocks stay the only form of the two Linear weight gradients (block addressing: lo_vae.h)
+extern "C" size_t lo_vae_gathered_scratch_bytes(const LoVae* h, int world) {
+  if (!h || !lo_lowrank_gathered_applies(world, h->B)) return 0;
+  return lo_lowrank_gathered_gram_elems(world, h->B) * sizeof(float);
+}
+// Called behind the all-gather of the factor blocks AND the exchange of the rest of the phase-1 range, on the stream that ran them:
+// fills scratch[512..1024) the way the single-process backward's early norm does (VaeBackward::early_norm) -- [512, 767) everything
+// behind decoder.fc.weight and [767] the two head biases from the AVERAGED flat buffer, [768, 896) and [896, 1024) the two matrices
+// from the Gram matrices of the gathered factors, cross-rank terms included -- and remembers the buffer for the optimizer step.
+// Lifetime of `gathered`: the pipelined step's factored AdamW reads it on the side stream; the caller overwrites it with the next
+// step's all-gather on its communication stream.  That stream is ordered behind a point of the compute stream that follows
+// lo_vae_backward_phase(1) of the next step, that backward begins with a wait for operand-refresh level 5 (VaeBackward::begin), and
+// level 5 is recorded on the side stream behind the factored AdamW (level 3, vae_flush_deferred): the all-gather cannot start
+// before the AdamW has read the buffer.  No further event is needed.
+extern "C" int lo_vae_gathered_early_norm(LoVae* h, const void* gathered, int world, float* gram_scratch, const float* G, float* scratch,
+                                          void* stream) {
+  LO_REQUIRE(h && gathered && gram_scratch && G && scratch, "lo_vae_gathered_early_norm: null argument");
+  if (!h->lin_gathered) { lo_set_error("lo_vae_gathered_early_norm: needs mode 3 of lo_vae_set_linear_factored"); return LO_ERR_STATE; }
+  LO_REQUIRE(lo_lowrank_gathered_applies(world, h->B), "lo_vae_gathered_early_norm: world %d x padded batch %d is above the combined rank "
+             "the gathered update is built for (512): use mode 2", world, h->Bp);
+  hipStream_t st = S(stream);
+  const int L = h->L;
+  const size_t bh = h->p_off[h->idx_fc_mu_w], nh = (size_t)2 * L * 32768, bd = h->p_off[h->idx_dfc_w], nd = (size_t)32768 * L;
+  const f16* base = reinterpret_cast<const f16*>(gathered);
+  LO_TRY(lo_sumsq_blocks(G + bd + nd, h->flat_elems - (bd + nd), scratch + 512, 255, st));
+  LO_TRY(lo_sumsq_blocks(G + bh + nh, bd - (bh + nh), scratch + 767, 1, st));
+  const size_t kt = (size_t)world * h->Bp;
+  const LoLowrankNorm nl[2] = {
+      {vae_fac_in_block(h, base, h->o_fac_dmlT), 2 * L, vae_fac_in_block(h, base, h->o_fac_xT), 32768, gram_scratch, scratch + 768, 128},
+      {vae_fac_in_block(h, base, h->o_fac_zT), L, vae_fac_in_block(h, base, h->o_fac_gfcT), 32768, gram_scratch + kt * kt, scratch + 896, 128}};
+  LO_TRY(lo_lowrank_sumsq_gathered(nl, 2, vae_fac_block_elems(h), world, h->B, h->fac_scale / (float)world, st));
+  h->fac_gathered = base;
+  h->fac_world = world;
+  h->fac_ready = true;
   return LO_OK;
 }
 // data parallel (mode 2): where the factor block -- dml^T | xflat^T | Gfc^T | z^T, transposed and batch-padded fp16, one contiguous
@@ -352,14 +392,17 @@ extern "C" int lo_vae_materialize_gathered_linear_grads(LoVae* h, const void* ga
   LO_REQUIRE(h && gathered && G && world >= 1, "lo_vae_materialize_gathered_linear_grads: bad argument");
   hipStream_t st = S(stream);
   const int L = h->L;
-  const size_t blk = (h->o_gram - h->o_fac_dmlT) / 2;     // elements per rank block
+  const size_t blk = vae_fac_block_elems(h);
   const f16* base = reinterpret_cast<const f16*>(gathered);
   const float sc = h->fac_scale / (float)world;
-  LO_TRY(lo_lowrank_materialize_gathered(G + h->p_off[h->idx_fc_mu_w], base + (h->o_fac_xT - h->o_fac_dmlT) / 2, base, blk, world, 2 * L, 32768, h->B, sc, st));
-  return lo_lowrank_materialize_gathered(G + h->p_off[h->idx_dfc_w], base + (h->o_fac_zT - h->o_fac_dmlT) / 2, base + (h->o_fac_gfcT - h->o_fac_dmlT) / 2,
+  LO_TRY(lo_lowrank_materialize_gathered(G + h->p_off[h->idx_fc_mu_w], vae_fac_in_block(h, base, h->o_fac_xT), vae_fac_in_block(h, base, h->o_fac_dmlT),
+                                         blk, world, 2 * L, 32768, h->B, sc, st));
+  return lo_lowrank_materialize_gathered(G + h->p_off[h->idx_dfc_w], vae_fac_in_block(h, base, h->o_fac_zT), vae_fac_in_block(h, base, h->o_fac_gfcT),
                                          blk, world, 32768, L, h->B, sc, st);
 }
-extern "C" int lo_vae_linear_factored(const LoVae* h) { return h && h->lin_factored ? 1 : 0; }
+// non-zero: the flat gradient buffer does not hold the two matrices after a step (1 or 3 = the mode; lo_vae_materialize_linear_grads
+// writes them out).  Mode 2 materialises them itself: 0
+extern "C" int lo_vae_linear_factored(const LoVae* h) { return !h ? 0 : (h->lin_factored ? 1 : (h->lin_gathered ? 3 : 0)); }
 extern "C" int lo_vae_num_params(const LoVae* h) { return h->nparam; }
 extern "C" size_t lo_vae_param_offset(const LoVae* h, int i) { return (i >= 0 && i < h->nparam) ? h->p_off[i] : (size_t)-1; }
 extern "C" size_t lo_vae_param_numel(const LoVae* h, int i) { return (i >= 0 && i < h->nparam) ? h->p_numel[i] : 0; }
@@ -407,6 +450,36 @@ extern "C" int lo_vae_wait_handover(LoVae* h, void* stream) {
 extern "C" int lo_gradnorm_early_range(const float* flat_grads, size_t begin, size_t end, float* scratch, void* stream) {
   LO_REQUIRE(flat_grads && scratch && end > begin, "lo_gradnorm_early_range: bad argument");
   return lo_sumsq_range(flat_grads, begin, end, scratch, S(stream));
+}
+
+// op level: the two gathered-factor passes on plain pointers (tests, tools/op_bench.py)
+extern "C" size_t lo_lowrank_gathered_scratch_bytes(int world, int batch) {
+  return lo_lowrank_gathered_applies(world, batch) ? lo_lowrank_gathered_gram_elems(world, batch) / 2 * sizeof(float) : 0;   // one layer
+}
+extern "C" int lo_lowrank_gathered_sumsq(const void* fshort_t, int n_short, const void* flong_t, int n_long, size_t rank_stride_elems, int world,
+                                         int batch, float scale, float* gram_scratch, float* partial, void* stream) {
+  LO_REQUIRE(fshort_t && flong_t && gram_scratch && partial, "lo_lowrank_gathered_sumsq: null argument");
+  const LoLowrankNorm nl = {reinterpret_cast<const f16*>(fshort_t), n_short, reinterpret_cast<const f16*>(flong_t), n_long, gram_scratch, partial, 128};
+  return lo_lowrank_sumsq_gathered(&nl, 1, rank_stride_elems, world, batch, scale, S(stream));
+}
+extern "C" int lo_lowrank_gathered_adamw(float* p, float* m, float* v, void* cast, void* cast_t, const void* xt, const void* yt,
+                                         size_t rank_stride_elems, int world, int N, int K, int batch, float gscale, const float* norm, float lr,
+                                         float beta1, float beta2, float eps, float weight_decay, int step, void* stream) {
+  LO_REQUIRE(p && m && v && xt && yt && step >= 1, "lo_lowrank_gathered_adamw: bad argument");
+  const LoLowrankMat mt = {p, m, v, reinterpret_cast<f16*>(cast), reinterpret_cast<f16*>(cast_t), reinterpret_cast<const f16*>(xt),
+                           reinterpret_cast<const f16*>(yt), N, K};
+  return lo_adamw_lowrank_gathered(&mt, 1, rank_stride_elems, world, batch, gscale, norm, lr, beta1, beta2, eps, weight_decay, step, S(stream));
+}
+
+// ... and the two passes of the optimizer's materialised path they are measured against (tools/op_bench.py --op lowrank_gathered)
+extern "C" int lo_adamw_range(float* p, const float* g, float* m, float* v, size_t n, const float* norm, float lr, float beta1, float beta2,
+                              float eps, float weight_decay, int step, void* cast, void* stream) {
+  LO_REQUIRE(p && g && m && v && n > 0 && step >= 1, "lo_adamw_range: bad argument");
+  return lo_adamw(p, g, m, v, n, norm, lr, beta1, beta2, eps, weight_decay, step, S(stream), reinterpret_cast<f16*>(cast));
+}
+extern "C" int lo_transpose_f16(const void* src, void* dst, int rows, int cols, void* stream) {
+  LO_REQUIRE(src && dst && rows > 0 && cols > 0 && rows % 64 == 0 && cols % 64 == 0, "lo_transpose_f16: rows=%d, cols=%d must be positive multiples of 64", rows, cols);
+  return lo_nhwc_to_nchw_f16(reinterpret_cast<const f16*>(src), reinterpret_cast<f16*>(dst), 1, rows, cols, S(stream));
 }
 
 extern "C" int lo_vae_fp8_layers(const LoVae* h, int* layers) {

@@ -75,7 +75,8 @@ class VAEStepper:
     def __init__(self, vae: LunarisCoreVAE, lr: float = 1e-4, min_lr: float = 1e-6, scheduler_t0: int = 10,
                  weight_decay: float = 0.01, max_grad_norm: float = 1.0, recon_weight: float = 1.0, kl_weight: float = 0.1,
                  gradient_accumulation_steps: int = 1, betas=(0.9, 0.999), eps: float = 1e-8,
-                 grad_sync: Optional[Callable[[torch.Tensor], None]] = None, pipeline_optimizer: bool = False):
+                 grad_sync: Optional[Callable[[torch.Tensor], None]] = None, pipeline_optimizer: bool = False,
+                 dp_factored_adamw: Optional[bool] = None):
         _lib.require_gpu()
         self.vae = vae
         # pipeline_optimizer: the update of the Linear / decoder parameters (87 % of AdamW's 1.7 GB) and their operand refresh run
@@ -98,6 +99,10 @@ class VAEStepper:
         # data parallel: the ranks all-gather the FACTORS (8.6 MB of fp16 per rank, exact) instead of exchanging the 201 MB of Linear
         # weight gradients, and each forms the averaged gradient from the gathered blocks (FlatGradSync.begin_factored)
         self.dp_factored = hasattr(grad_sync, "begin_factored") and os.environ.get("LO_LINEAR_FACTORED", "1") != "0"
+        # ... and, opt-in (LO_LINEAR_FACTORED=2, or dp_factored_adamw=True), never writes the averaged matrices either: norm and AdamW
+        # read the gathered blocks (mode 3 of lo_vae_set_linear_factored; world * padded batch <= 512, else mode 2 as above)
+        self.dp_factored_adamw = (os.environ.get("LO_LINEAR_FACTORED", "1") == "2") if dp_factored_adamw is None else bool(dp_factored_adamw)
+        self._gram_scratch = {}         # (world, batch) -> Gram scratch of lo_vae_gathered_early_norm
         self.dp_three_phase = True      # hand the encoder's last stage over before stages 3..1 run (False: one encoder range)
         flat = vae.flat_parameters()
         self.grads = torch.zeros_like(flat)
@@ -189,11 +194,13 @@ class VAEStepper:
             # FlatGradSync runs the exchange on its own stream: the phases then hand their range over as an event for THAT stream
             # (lo_vae_set_async_handover) instead of holding this one up until the side stream's weight gradients have finished
             active = getattr(self.grad_sync, "world", 1) > 1 or getattr(self.grad_sync, "force", False)
-            dpf = self.dp_factored and active and eng.batch <= 128
-            if eng.fac_mode != (2 if dpf else 0):
-                _lib.check(_lib.lib.lo_vae_set_linear_factored(eng.handle, 2 if dpf else 0), "lo_vae_set_linear_factored")
-                eng.fac_mode = 2 if dpf else 0
             hooks = getattr(self.grad_sync, "supports_then", False)
+            early = os.environ.get("LO_EARLY_NORM", "1") != "0" and hooks
+            mode = self._dp_linear_mode(eng, active, early)
+            dpf = mode != 0
+            if eng.fac_mode != mode:
+                _lib.check(_lib.lib.lo_vae_set_linear_factored(eng.handle, mode), "lo_vae_set_linear_factored")
+                eng.fac_mode = mode
             _lib.check(_lib.lib.lo_vae_set_async_handover(eng.handle, 1 if hooks else 0), "lo_vae_set_async_handover")
             def wait_range():
                 _lib.check(_lib.lib.lo_vae_wait_handover(eng.handle, _lib.stream_ptr()), "lo_vae_wait_handover")
@@ -201,7 +208,6 @@ class VAEStepper:
             _lib.check(_lib.lib.lo_vae_backward_phase(eng.handle, 1, *bargs), "lo_vae_backward_phase(1)")
             # ... and so is the sum of squares of that range for clip_grad_norm_ (of the AVERAGED gradients): taken right behind the
             # exchange on the communication stream, beside the encoder backward; the tail of the step reads only the encoder range
-            early = os.environ.get("LO_EARLY_NORM", "1") != "0" and hooks
             if dpf:
                 # the Linear weight gradients of this range travel as factors: gather, form the averaged matrices locally, average the
                 # rest of the range (head biases; decoder.fc.bias, decoder and final convs), then the range's share of the norm
@@ -216,15 +222,38 @@ class VAEStepper:
                 d_beg = d_end - 32768 * L
                 pieces = [self.grads[h_end:d_beg], self.grads[d_end:e.value]]
 
-                def materialize(gathered, world, eng=eng):
-                    _lib.check(_lib.lib.lo_vae_materialize_gathered_linear_grads(eng.handle, gathered.data_ptr(), world, self.grads.data_ptr(),
-                                                                                 _lib.stream_ptr()), "lo_vae_materialize_gathered_linear_grads")
+                if mode == 3:
+                    # nothing is materialised: the callback only notes what the all-gather delivered, and the hook behind the exchange
+                    # of `pieces` takes the range's share of the norm -- the rest of the range from the averaged flat buffer, the two
+                    # matrices from the Gram matrices of the gathered factors -- and leaves the buffer to the optimizer step
+                    seen = []
 
-                def norm_of_range():
-                    _lib.check(_lib.lib.lo_gradnorm_early_range(self.grads.data_ptr(), b.value, e.value, self.scratch.data_ptr(), _lib.stream_ptr()),
-                               "lo_gradnorm_early_range")
-                if self.grad_sync.begin_factored(pieces, factors, materialize, then=norm_of_range if early else None, **kw) and early:
+                    def keep_gathered(gathered, world):
+                        seen.append((gathered, world))
+
+                    def norm_of_gathered(eng=eng):
+                        gathered, world = seen[-1]
+                        key = (world, eng.batch)
+                        if key not in self._gram_scratch:
+                            self._gram_scratch[key] = _alloc_scratch(_lib.lib.lo_vae_gathered_scratch_bytes(eng.handle, world), gathered.device)
+                        _lib.check(_lib.lib.lo_vae_gathered_early_norm(eng.handle, gathered.data_ptr(), world, self._gram_scratch[key].data_ptr(),
+                                                                       self.grads.data_ptr(), self.scratch.data_ptr(), _lib.stream_ptr()),
+                                   "lo_vae_gathered_early_norm")
+
+                    if not self.grad_sync.begin_factored(pieces, factors, keep_gathered, then=norm_of_gathered, **kw):
+                        raise RuntimeError("dp_factored_adamw: the gradient exchange did not run its hooks (begin_factored returned False)")
                     self._presummed_begin = b.value
+                else:
+                    def materialize(gathered, world, eng=eng):
+                        _lib.check(_lib.lib.lo_vae_materialize_gathered_linear_grads(eng.handle, gathered.data_ptr(), world, self.grads.data_ptr(),
+                                                                                     _lib.stream_ptr()), "lo_vae_materialize_gathered_linear_grads")
+
+                    def norm_of_range():
+                        _lib.check(_lib.lib.lo_gradnorm_early_range(self.grads.data_ptr(), b.value, e.value, self.scratch.data_ptr(), _lib.stream_ptr()),
+                                   "lo_gradnorm_early_range")
+
+                    if self.grad_sync.begin_factored(pieces, factors, materialize, then=norm_of_range if early else None, **kw) and early:
+                        self._presummed_begin = b.value
             elif early:
                 if self.grad_sync.begin(self.grads[b.value:e.value], sumsq_scratch=self.scratch.data_ptr(), **kw):
                     self._presummed_begin = b.value
@@ -257,6 +286,19 @@ class VAEStepper:
                 b, e = C.c_size_t(), C.c_size_t()
                 _lib.check(_lib.lib.lo_vae_phase1_grad_range(eng.handle, C.byref(b), C.byref(e)), "lo_vae_phase1_grad_range")
                 self._presummed_begin = b.value
+
+    def _dp_linear_mode(self, eng, active: bool, early: bool) -> int:
+        """Mode of lo_vae_set_linear_factored for a data-parallel step: 0 the Linear weight gradients are exchanged like the rest,
+        2 their factors are all-gathered and the averaged matrices materialised, 3 (opt-in) norm and AdamW read the gathered
+        factors.  Mode 3 needs the exchange's `then` hook on a GPU communication stream and world * padded batch <= 512
+        (lo_vae_gathered_scratch_bytes says so); otherwise mode 2, silently."""
+        if not (self.dp_factored and active and eng.batch <= 128):
+            return 0
+        world = int(getattr(self.grad_sync, "world", 1))
+        if (self.dp_factored_adamw and early and getattr(self.grad_sync, "backend", "nccl") != "gloo"
+                and _lib.lib.lo_vae_gathered_scratch_bytes(eng.handle, world) > 0):
+            return 3
+        return 2
 
     def synchronize_parameters(self) -> None:
         """Make the current stream wait for a pipelined optimizer step's side-stream work (no-op otherwise)."""

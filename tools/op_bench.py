@@ -5,6 +5,7 @@
   python tools/op_bench.py --op attn --B 64 --H 8 --Cin 512        (SelfAttention2d forward on a [B, Cin, H, H] map)
   python tools/op_bench.py --op imgdgrad --stride 2|1 --B 64       (images' data gradient: VAE encoder.down1.0 | teacher conv1)
   python tools/op_bench.py --op tconv --B 8 --pairs 3              (wide teacher 3x3 convs at 128x128, e4m3 against fp16, interleaved; markdown table)
+  python tools/op_bench.py --op lowrank_gathered --B 64 --pairs 3  (data parallel: norm + AdamW of the two Linear matrices from gathered factors, mode 3 against mode 2, world 1 / 2 / 4 / 8)
 """
 import argparse
 import ctypes as C
@@ -67,6 +68,111 @@ def tconv(a):
               f"{'yes' if all(p8 < p16 for p8, p16 in zip(t8, t16)) else 'NO'} |", flush=True)
 
 
+def lowrank_gathered(a):
+    """Data parallel, the two Linear weight matrices at batch `--B` / latent 512 from `world` synthetic gathered factor blocks on one GPU:
+    mode 3 (Gram norm + factored AdamW straight from the blocks) against the passes mode 2 runs for the same result (materialise the
+    averaged matrices, sum their squares, AdamW with the fp16 copy, the two transposes), each matrix by its own launches on both sides
+    (the step puts both matrices of mode 3 into one launch per pass).  Two buffer sets alternate; one call moves 1.2 - 2 GB, several
+    times the 256 MB last-level cache, so every call streams from HBM.  `--pairs` interleaved pairs of `--iters` calls; markdown rows."""
+    lib, st, B, L = _lib.lib, _lib.stream_ptr(), a.B, 512
+    Bp = (B + 31) // 32 * 32
+    h = C.c_void_p()
+    _lib.check(lib.lo_vae_create(B, L, C.byref(h)))
+    fo, fb, pb, pe, lb, le = (C.c_size_t() for _ in range(6))
+    _lib.check(lib.lo_vae_factor_block(h, C.byref(fo), C.byref(fb)))
+    _lib.check(lib.lo_vae_phase1_grad_range(h, C.byref(pb), C.byref(pe)))
+    _lib.check(lib.lo_vae_linear_grad_range(h, C.byref(lb), C.byref(le)))
+    o_dml, o_x = 0, 2 * L * Bp
+    o_gfc = o_x + 32768 * Bp
+    o_z = o_gfc + 32768 * Bp
+    blk = o_z + L * Bp                                   # elements per rank block: dml^T | xflat^T | Gfc^T | z^T
+    assert blk * 2 == fb.value, (blk * 2, fb.value)
+    nflat = lib.lo_vae_flat_elems(h)
+    bh, nh = pb.value, 2 * L * 32768
+    bd, nd = le.value - 32768 - 32768 * L, 32768 * L
+    mats = ((bh, 2 * L, 32768, o_x, o_dml), (bd, 32768, L, o_z, o_gfc))       # offset, N, K, xt, yt
+    hyp = (1e-4, 0.9, 0.999, 1e-8, 0.01, 3)
+    print(f"| world | K = world x Bp | mode 3: norm us | mode 3: AdamW us | mode 3 total us (pairs) | mode 2: materialise us | mode 2: norm us | mode 2: AdamW + cast us | "
+          f"mode 2: transposes us | mode 2 total us (pairs) | mode 2 / mode 3 |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|")
+    sets = []
+    for _ in range(2):
+        P = torch.randn(nflat, device="cuda") * 0.02
+        sets.append(dict(P=P, M=torch.zeros_like(P), V=torch.zeros_like(P), G=torch.empty_like(P), c=[torch.empty(nh, dtype=torch.float16, device="cuda"),
+                    torch.empty(nd, dtype=torch.float16, device="cuda")], ct=[torch.empty(nh, dtype=torch.float16, device="cuda"),
+                    torch.empty(nd, dtype=torch.float16, device="cuda")], scratch=torch.zeros(1028, device="cuda")))
+    norm = torch.tensor([1.0, 1.0, 1.0], device="cuda")
+    for world in (1, 2, 4, 8):
+        gram = torch.empty(lib.lo_vae_gathered_scratch_bytes(h, world) // 4, device="cuda")
+        gath = []
+        for _ in range(2):
+            g = torch.zeros(world, blk, dtype=torch.float16, device="cuda")
+            for off, rows in ((o_dml, 2 * L), (o_x, 32768), (o_gfc, 32768), (o_z, L)):
+                g[:, off:off + rows * Bp].view(world, rows, Bp)[:, :, :B] = (torch.randn(world, rows, B, device="cuda") * 0.05).half()
+            gath.append(g)
+        kt = world * Bp
+        it = [0]
+
+        def new_norm():
+            s, g = sets[it[0] % 2], gath[it[0] % 2]
+            for i, (off, N, K, xo, yo) in enumerate(mats):
+                short, ns, long_, nl = (yo, N, xo, K) if N < K else (xo, K, yo, N)
+                _lib.check(lib.lo_lowrank_gathered_sumsq(g.data_ptr() + 2 * short, ns, g.data_ptr() + 2 * long_, nl, blk, world, B, 1.0 / world,
+                                                         gram.data_ptr() + 4 * i * kt * kt, s["scratch"].data_ptr() + 4 * (768 + 128 * i), st))
+
+        def new_adamw():
+            s, g = sets[it[0] % 2], gath[it[0] % 2]
+            for i, (off, N, K, xo, yo) in enumerate(mats):
+                _lib.check(lib.lo_lowrank_gathered_adamw(s["P"].data_ptr() + 4 * off, s["M"].data_ptr() + 4 * off, s["V"].data_ptr() + 4 * off, s["c"][i].data_ptr(),
+                                                         s["ct"][i].data_ptr(), g.data_ptr() + 2 * xo, g.data_ptr() + 2 * yo, blk, world, N, K, B, 1.0 / world,
+                                                         norm.data_ptr(), *hyp, st))
+
+        def old_mat():
+            s, g = sets[it[0] % 2], gath[it[0] % 2]
+            _lib.check(lib.lo_vae_materialize_gathered_linear_grads(h, g.data_ptr(), world, s["G"].data_ptr(), st))
+
+        def old_norm():
+            s = sets[it[0] % 2]
+            for off, N, K, _, _ in mats:
+                _lib.check(lib.lo_gradnorm_early_range(s["G"].data_ptr(), off, off + N * K, s["scratch"].data_ptr(), st))
+
+        def old_adamw():
+            s = sets[it[0] % 2]
+            for i, (off, N, K, _, _) in enumerate(mats):
+                _lib.check(lib.lo_adamw_range(s["P"].data_ptr() + 4 * off, s["G"].data_ptr() + 4 * off, s["M"].data_ptr() + 4 * off, s["V"].data_ptr() + 4 * off,
+                                              N * K, norm.data_ptr(), *hyp, s["c"][i].data_ptr(), st))
+
+        def old_tr():
+            s = sets[it[0] % 2]
+            for i, (off, N, K, _, _) in enumerate(mats):
+                _lib.check(lib.lo_transpose_f16(s["c"][i].data_ptr(), s["ct"][i].data_ptr(), N, K, st))
+
+        def timed(parts):
+            """mean us per call of each part and of their sum, the parts of one call back to back in stream order"""
+            ev = [[torch.cuda.Event(enable_timing=True) for _ in range(len(parts) + 1)] for _ in range(a.iters)]
+            for k in range(a.iters):
+                ev[k][0].record()
+                for j, fn in enumerate(parts):
+                    fn()
+                    ev[k][j + 1].record()
+                it[0] += 1
+            torch.cuda.synchronize()
+            per = [sum(e[j].elapsed_time(e[j + 1]) for e in ev) / a.iters * 1e3 for j in range(len(parts))]
+            return per, sum(e[0].elapsed_time(e[-1]) for e in ev) / a.iters * 1e3
+        new, old = (new_norm, new_adamw), (old_mat, old_norm, old_adamw, old_tr)
+        for _ in range(3):
+            timed(new)
+            timed(old)
+        tn, to = [], []
+        for _ in range(a.pairs):
+            tn.append(timed(new))
+            to.append(timed(old))
+        bn, bo = min(tn, key=lambda t: t[1]), min(to, key=lambda t: t[1])
+        print(f"| {world} | {kt} | {bn[0][0]:.0f} | {bn[0][1]:.0f} | {' / '.join(f'{t[1]:.0f}' for t in tn)} | {bo[0][0]:.0f} | {bo[0][1]:.0f} | {bo[0][2]:.0f} | {bo[0][3]:.0f} | "
+              f"{' / '.join(f'{t[1]:.0f}' for t in to)} | {min(t[1] for t in to) / min(t[1] for t in tn):.2f} |", flush=True)
+    lib.lo_vae_destroy(h)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--op", default="conv")
@@ -78,10 +184,12 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--stats", type=int, default=1)
     ap.add_argument("--stride", type=int, default=2, help="--op imgdgrad: 2 = the VAE's first conv (64 channels), 1 = the teacher's conv1 (32)")
-    ap.add_argument("--pairs", type=int, default=3, help="--op tconv: interleaved fp16 / e4m3 pairs per shape")
+    ap.add_argument("--pairs", type=int, default=3, help="--op tconv / lowrank_gathered: interleaved pairs per shape")
     a = ap.parse_args()
     if a.op == "tconv":
         return tconv(a)
+    if a.op == "lowrank_gathered":
+        return lowrank_gathered(a)
     lib = _lib.lib
     B, H, Cin, Cout, kind = a.B, a.H, a.Cin, a.Cout, a.kind
     Ho = H if kind in (0, 3, 6) else (H // 2 if kind in (1, 5) else 2 * H)
