@@ -54,6 +54,11 @@ int lo_scale_copy_dev_run(const float* src, float* dst, size_t n, const float* s
 int lo_scale_dev_run(float* x, size_t n, const float* scale_dev, const unsigned int* fail, hipStream_t st);
 int lo_adamw(float* p, const float* g, float* m, float* v, size_t n, const float* norm, float lr, float beta1, float beta2,
              float eps, float wd, int step, hipStream_t st, f16* cast = nullptr);
+// what one optimizer step hands to every AdamW launch: norm[1] clip coefficient, norm[2] finite flag (lo_gradnorm); step counts from 1
+struct LoAdamHyper { const float* norm; float lr, beta1, beta2, eps, wd; int step; };
+static inline int lo_adamw(float* p, const float* g, float* m, float* v, size_t n, const LoAdamHyper& hp, hipStream_t st, f16* cast = nullptr) {
+  return lo_adamw(p, g, m, v, n, hp.norm, hp.lr, hp.beta1, hp.beta2, hp.eps, hp.wd, hp.step, st, cast);
+}
 
 // lo_attn.hip
 int lo_selfattn2d_fwd(const float* x, const float* wq, const float* bq, const float* wk, const float* bk, const float* wv,
@@ -72,16 +77,14 @@ int lo_transpose_pad_f16_multi(const f16* const* src, f16* const* dst, const int
 struct LoLowrankNorm { const f16* fshort; int n_short; const f16* flong; int n_long; float* gram; float* partial; int nslots; };
 int lo_lowrank_sumsq(const LoLowrankNorm* layers, int nlayers, int B, float scale, hipStream_t st);
 struct LoLowrankMat { float* p; float* m; float* v; f16* cast; f16* cast_t; const f16* xt; const f16* yt; int N, K; };   // W [N][K] (cast_t [K][N]); xt [K][Bp], yt [N][Bp]
-int lo_adamw_lowrank(const LoLowrankMat* mats, int nmat, int B, float gscale, const float* norm, float lr, float beta1, float beta2,
-                     float eps, float wd, int step, hipStream_t st);
-int lo_lowrank_materialize(float* gout, const f16* xt, const f16* yt, int N, int K, int B, float gscale, hipStream_t st);
+int lo_adamw_lowrank(const LoLowrankMat* mats, int nmat, int B, float gscale, const LoAdamHyper& hp, hipStream_t st);
 int lo_lowrank_materialize_gathered(float* gout, const f16* xt, const f16* yt, size_t rank_stride_elems, int world, int N, int K, int B,
                                     float gscale, hipStream_t st);
 // data parallel, mode 3: the same two from `world` gathered factor blocks (rank r's copy of a factor rank_stride_elems * r further on);
 // world * lo_lowrank_bp(B) <= 512.  LoLowrankNorm's factors are then the TRANSPOSED ones ([n][Bp]); gram: [KT][KT] per layer
 bool lo_lowrank_gathered_applies(int world, int B);
 size_t lo_lowrank_gathered_gram_elems(int world, int B);   // fp32 elements of Gram scratch for two layers: 2 (world Bp)^2
-int lo_adamw_lowrank_gathered(const LoLowrankMat* mats, int nmat, size_t rank_stride_elems, int world, int B, float gscale, const float* norm,
-                              float lr, float beta1, float beta2, float eps, float wd, int step, hipStream_t st);
+int lo_adamw_lowrank_gathered(const LoLowrankMat* mats, int nmat, size_t rank_stride_elems, int world, int B, float gscale,
+                              const LoAdamHyper& hp, hipStream_t st);
 int lo_lowrank_sumsq_gathered(const LoLowrankNorm* layers, int nlayers, size_t rank_stride_elems, int world, int B, float scale, hipStream_t st);
 int lo_sumsq_blocks(const float* g, size_t n, float* partial, int nblocks, hipStream_t st);   // lo_train.hip: partial[0 .. nblocks)

@@ -14,8 +14,8 @@
 // (input feature) and j = n (output feature), A = X^T rows, B = dY^T rows.  A lane then owns four consecutive k of one n
 // (D row = 4 (lane >> 4) + r, column = lane & 15): one 16-byte load / store per tensor and tile, 64 contiguous bytes per matrix row
 // and instruction, 256 per row over the four k tiles of a wave's 64 x 64 block.
-// A materialising variant (same tiles, same arithmetic, gradient written to the flat buffer) exists for tests and for
-// lo_vae_materialize_linear_grads.  No reference counterpart below aten::linear_backward / torch.optim.AdamW.
+// lo_lowrank_materialize_gathered_kernel writes the same tiles (same MFMA sequence per tile, same scale) to the flat buffer: for
+// tests and lo_vae_materialize_linear_grads.  No reference counterpart below aten::linear_backward / torch.optim.AdamW.
 #include "lo_common.h"
 #include "lo_internal.h"
 #include "lo_conv_dev.h"
@@ -74,6 +74,8 @@ __global__ __launch_bounds__(256) void lo_transpose_pad_f16_kernel(LoTransposeJo
 // one workgroup for the small matrix and dependent loads inside the step loops, took 36 us per layer; the loads are now issued in
 // batches of 8 steps (small) / 4 steps (long) before the MFMAs that consume them.
 // ---------------------------------------------------------------------------------------------
+// one layer of either norm (this rank's factors, natural layout, or the gathered ones, transposed): the long factor's contraction
+// is cut into `chunks` pieces of `per` steps, one partial-sum slot per (chunk, cell of the Gram matrix) -- lowrank_gram_layer below
 struct LoGramLayer { const f16* fshort; const f16* flong; float* gram; float* partial; int n_short, n_long, chunks, per, nslots; };
 struct LoGramJobs { LoGramLayer l[2]; int B, Bp; float scale2; };
 __device__ __forceinline__ f16x8 lo_gram_frag(const f16* __restrict__ src, int B, int n, int bi, int kc, int lane) {
@@ -184,7 +186,6 @@ struct LoLowrankArgs {
   float* p; float* m; float* v;   // [N][K] fp32 (parameter, Adam moments)
   f16* cast;                      // [N][K] fp16 operand copy of the updated parameter (may be null)
   f16* cast_t;                    // [K][N] the same, transposed (operand of the layer's data gradient; may be null)
-  float* gout;                    // materialising variant: the gradient [N][K]
   const f16* xt;                  // X^T  [K][Bp]
   const f16* yt;                  // dY^T [N][Bp]
   int N, K, Bp;
@@ -210,7 +211,8 @@ __device__ __forceinline__ void lo_adamw_elem_lr(float& p, float g, float& m, fl
 // One wave owns a 64-column band of the matrix (k0 .. k0 + 63: its 4 x KB X^T fragments are loaded ONCE) and walks down the rows
 // in 16-row groups: per group KB dY^T fragments and 4 tiles x (p, m, v) 16-byte loads.  The walk is software-pipelined over the
 // groups, across 64-row tile boundaries: the loads of group g + 1 are issued before the MFMAs and the update of group g, so a lane
-// always has 12 - 24 loads in flight; two workgroups per CU (8 waves, <= 256 registers each) keep ~100 KB per CU outstanding.
+// always has 12 - 24 loads in flight; two workgroups per CU (8 waves) keep ~100 KB per CU outstanding where a wave fits into 256
+// registers: KB <= 3 (the counts are at the launch, lo_adamw_lowrank).
 // Both matrices of the model share ONE launch (LoLowrankPair): one ramp and one tail instead of two.
 // Neighbouring waves own neighbouring bands: the 256-byte row segments of the waves of a workgroup are contiguous in memory.
 // (The first version -- one wave per 64 x 64 block, nothing in flight across blocks -- ran at 4.8 TB/s against lo_adamw's 6.2.)
@@ -220,20 +222,56 @@ struct LoLowrankPair { LoLowrankArgs l[2]; int nwg0; };      // workgroups [0, n
 // groups are done: 2 more bytes per parameter on this pass instead of a separate transpose pass over both fp16 copies (4 bytes per
 // parameter, 45 us per step for the two matrices).
 #define LR_TP 72     // LDS pitch of a transposed block in halves (64 + 8: rows 144 bytes apart)
-template <int KB, bool MAT>
+// what every element of a launch shares: clip coefficient and the constants of lo_adamw
+struct LoLowrankConsts { float coef, step_size, decay, omb1, omb2; };
+__device__ __forceinline__ LoLowrankConsts lo_lowrank_consts(const LoLowrankArgs& a) {
+  return {a.norm ? a.norm[1] : 1.0f, a.lr / a.bc1, 1.0f - a.lr * a.wd, 1.0f - a.beta1, 1.0f - a.beta2};
+}
+// One 16 x 16 tile: the element update on the accumulator, p / m / v and the fp16 copy stored at element offset `off` (a lane's
+// four consecutive k of one n), and the 2-byte scatter into the wave's transposed LDS block tb at rows krow .. krow + 3, column ncol
+__device__ __forceinline__ void lo_lowrank_update_tile(const LoLowrankArgs& a, const LoLowrankConsts& c, size_t off, f32x4 acc, f32x4 pe,
+                                                       f32x4 me, f32x4 ve, f16* tb, int krow, int ncol) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float pr = pe[r], mr = me[r], vr = ve[r];
+    lo_adamw_elem_lr(pr, acc[r] * a.gscale, mr, vr, c.coef, c.decay, c.omb1, a.beta2, c.omb2, a.bc2_sqrt, a.eps, c.step_size);
+    pe[r] = pr; me[r] = mr; ve[r] = vr;
+  }
+  *reinterpret_cast<f32x4*>(a.p + off) = pe;
+  *reinterpret_cast<f32x4*>(a.m + off) = me;
+  *reinterpret_cast<f32x4*>(a.v + off) = ve;
+  if (a.cast) *reinterpret_cast<f16x4*>(a.cast + off) = (f16x4){(f16)pe[0], (f16)pe[1], (f16)pe[2], (f16)pe[3]};
+  if (a.cast_t) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) tb[(krow + r) * LR_TP + ncol] = (f16)pe[r];
+  }
+}
+// A wave's 64 x 64 block is in (four 16-row groups): 64 rows (k, from k0) x 64 columns (n, from n_first); instruction j stores rows
+// 8 j .. 8 j + 7, 128 contiguous bytes each
+__device__ __forceinline__ void lo_lowrank_flush_block(const LoLowrankArgs& a, const f16* tb, int k0, size_t n_first, int lane) {
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int kk = 8 * j + (lane >> 3), ch = lane & 7;
+    *reinterpret_cast<f16x8*>(a.cast_t + (size_t)(k0 + kk) * a.N + n_first + 8 * ch) = *reinterpret_cast<const f16x8*>(tb + kk * LR_TP + 8 * ch);
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+template <int KB>
 __global__ __launch_bounds__(256) void lo_adamw_lowrank_kernel(LoLowrankPair A) {
-  __shared__ __attribute__((aligned(16))) f16 tbuf[MAT ? 1 : 4][MAT ? 8 : 64 * LR_TP];
+  __shared__ __attribute__((aligned(16))) f16 tbuf[4][64 * LR_TP];
   const bool second = (int)blockIdx.x >= A.nwg0;
   const LoLowrankArgs& a = second ? A.l[1] : A.l[0];
   const int bid = second ? (int)blockIdx.x - A.nwg0 : (int)blockIdx.x, nbl = second ? (int)gridDim.x - A.nwg0 : A.nwg0;
-  const float coef = a.norm ? a.norm[1] : 1.0f;
-  if (!MAT && a.norm && a.norm[2] == 0.f) return;        // non-finite norm / lost launch: the update is skipped
+  const LoLowrankConsts c = lo_lowrank_consts(a);
+  if (a.norm && a.norm[2] == 0.f) return;                // non-finite norm / lost launch: the update is skipped
   const int lane = threadIdx.x & 63, l15 = lane & 15, lq = lane >> 4;
   const int bands = a.K / 64, tiles_n = a.N / 64;
   const int W = nbl * 4, gw = bid * 4 + (threadIdx.x >> 6);
   const int wpb = W >= bands ? W / bands : 1;            // waves per band
-  const float step_size = a.lr / a.bc1, decay = 1.0f - a.lr * a.wd, omb1 = 1.0f - a.beta1, omb2 = 1.0f - a.beta2;
   const int Bp = a.Bp;
+  f16* tb = &tbuf[threadIdx.x >> 6][0];
   for (int vw = gw; vw < bands * wpb; vw += W) {
     const int band = vw % bands, sub = vw / bands;
     if (sub >= tiles_n) continue;
@@ -252,14 +290,12 @@ __global__ __launch_bounds__(256) void lo_adamw_lowrank_kernel(LoLowrankPair A) 
       const size_t row = row_of(g);
 #pragma unroll
       for (int kb = 0; kb < KB; ++kb) yf[buf][kb] = *reinterpret_cast<const f16x8*>(a.yt + row * Bp + 32 * kb + 8 * lq);
-      if (!MAT) {
-        const size_t base = row * a.K + k0 + 4 * lq;
+      const size_t base = row * a.K + k0 + 4 * lq;
 #pragma unroll
-        for (int ik = 0; ik < 4; ++ik) {
-          pv[buf][ik] = *reinterpret_cast<const f32x4*>(a.p + base + 16 * ik);
-          mv[buf][ik] = *reinterpret_cast<const f32x4*>(a.m + base + 16 * ik);
-          vv[buf][ik] = *reinterpret_cast<const f32x4*>(a.v + base + 16 * ik);
-        }
+      for (int ik = 0; ik < 4; ++ik) {
+        pv[buf][ik] = *reinterpret_cast<const f32x4*>(a.p + base + 16 * ik);
+        mv[buf][ik] = *reinterpret_cast<const f32x4*>(a.m + base + 16 * ik);
+        vv[buf][ik] = *reinterpret_cast<const f32x4*>(a.v + base + 16 * ik);
       }
     };
     auto do_group = [&](int g, int buf) {
@@ -269,41 +305,9 @@ __global__ __launch_bounds__(256) void lo_adamw_lowrank_kernel(LoLowrankPair A) 
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kb = 0; kb < KB; ++kb) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(xf[ik][kb], yf[buf][kb], acc, 0, 0, 0);
-        if (MAT) {
-          f32x4 gr = {acc[0] * a.gscale, acc[1] * a.gscale, acc[2] * a.gscale, acc[3] * a.gscale};
-          *reinterpret_cast<f32x4*>(a.gout + base + 16 * ik) = gr;
-        } else {
-          f32x4 pe = pv[buf][ik], me = mv[buf][ik], ve = vv[buf][ik];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            float pr = pe[r], mr = me[r], vr = ve[r];
-            lo_adamw_elem_lr(pr, acc[r] * a.gscale, mr, vr, coef, decay, omb1, a.beta2, omb2, a.bc2_sqrt, a.eps, step_size);
-            pe[r] = pr; me[r] = mr; ve[r] = vr;
-          }
-          *reinterpret_cast<f32x4*>(a.p + base + 16 * ik) = pe;
-          *reinterpret_cast<f32x4*>(a.m + base + 16 * ik) = me;
-          *reinterpret_cast<f32x4*>(a.v + base + 16 * ik) = ve;
-          if (a.cast) *reinterpret_cast<f16x4*>(a.cast + base + 16 * ik) = (f16x4){(f16)pe[0], (f16)pe[1], (f16)pe[2], (f16)pe[3]};
-          if (a.cast_t) {
-            f16* tb = &tbuf[threadIdx.x >> 6][0];
-            const int nloc = 16 * (g & 3) + l15;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) tb[(16 * ik + 4 * lq + r) * LR_TP + nloc] = (f16)pe[r];
-          }
-        }
+        lo_lowrank_update_tile(a, c, base + 16 * ik, acc, pv[buf][ik], mv[buf][ik], vv[buf][ik], tb, 16 * ik + 4 * lq, 16 * (g & 3) + l15);
       }
-      if (!MAT && a.cast_t && (g & 3) == 3) {
-        // the block's four groups are in: 64 rows (k) x 64 columns (n); instruction j stores rows 8 j .. 8 j + 7, 128 bytes each
-        __builtin_amdgcn_wave_barrier();
-        const f16* tb = &tbuf[threadIdx.x >> 6][0];
-        const size_t n_first = (size_t)(sub + (g >> 2) * wpb) * 64;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int kk = 8 * j + (lane >> 3), ch = lane & 7;
-          *reinterpret_cast<f16x8*>(a.cast_t + (size_t)(k0 + kk) * a.N + n_first + 8 * ch) = *reinterpret_cast<const f16x8*>(tb + kk * LR_TP + 8 * ch);
-        }
-        __builtin_amdgcn_wave_barrier();
-      }
+      if (a.cast_t && (g & 3) == 3) lo_lowrank_flush_block(a, tb, k0, (size_t)(sub + (g >> 2) * wpb) * 64, lane);
     };
     load_group(0, 0);
     for (int g = 0; g < ngroups; g += 2) {               // ngroups is a multiple of 4
@@ -388,7 +392,7 @@ __global__ __launch_bounds__(64 * NW) void lo_adamw_lowrank_gathered_kernel(LoGa
   __shared__ __attribute__((aligned(16))) f16 tbuf[NW][64 * LR_TP];
   const bool second = (int)blockIdx.x >= A.nwg0;
   const LoLowrankArgs& a = second ? A.l[1] : A.l[0];
-  const float coef = a.norm ? a.norm[1] : 1.0f;
+  const LoLowrankConsts c = lo_lowrank_consts(a);
   if (a.norm && a.norm[2] == 0.f) return;                // non-finite norm / lost launch: the update is skipped
   const int bid = second ? (int)blockIdx.x - A.nwg0 : (int)blockIdx.x;
   // neighbouring workgroups own neighbouring bands: what is resident on the chip at any moment covers whole rows of the matrix
@@ -399,7 +403,7 @@ __global__ __launch_bounds__(64 * NW) void lo_adamw_lowrank_gathered_kernel(LoGa
   const int tile0 = chunk * (TPW * NW) + wave;
   const bool live = tile0 < tiles_n;                     // a wave without a row tile only helps staging
   const int ngroups = TPW == 2 && tile0 + NW < tiles_n ? 8 : 4;
-  const float step_size = a.lr / a.bc1, decay = 1.0f - a.lr * a.wd, omb1 = 1.0f - a.beta1, omb2 = 1.0f - a.beta2;
+  f16* tb = &tbuf[wave][0];
   size_t yoff[KSMAX];                                    // where 32-sample step ks starts inside a dY^T row: rank block + column (wave-uniform)
 #pragma unroll
   for (int ks = 0; ks < KSMAX; ++ks) {
@@ -440,37 +444,9 @@ __global__ __launch_bounds__(64 * NW) void lo_adamw_lowrank_gathered_kernel(LoGa
   auto update = [&](int g, int buf) {
     const size_t base = row_of(g) * a.K + k0 + 4 * lq;
 #pragma unroll
-    for (int ik = 0; ik < 4; ++ik) {
-      f32x4 pe = pv[buf][ik], me = mv[buf][ik], ve = vv[buf][ik];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float pr = pe[r], mr = me[r], vr = ve[r];
-        lo_adamw_elem_lr(pr, acc[ik][r] * a.gscale, mr, vr, coef, decay, omb1, a.beta2, omb2, a.bc2_sqrt, a.eps, step_size);
-        pe[r] = pr; me[r] = mr; ve[r] = vr;
-      }
-      *reinterpret_cast<f32x4*>(a.p + base + 16 * ik) = pe;
-      *reinterpret_cast<f32x4*>(a.m + base + 16 * ik) = me;
-      *reinterpret_cast<f32x4*>(a.v + base + 16 * ik) = ve;
-      if (a.cast) *reinterpret_cast<f16x4*>(a.cast + base + 16 * ik) = (f16x4){(f16)pe[0], (f16)pe[1], (f16)pe[2], (f16)pe[3]};
-      if (a.cast_t) {
-        f16* tb = &tbuf[wave][0];
-        const int nloc = 16 * (g & 3) + l15;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) tb[(16 * ik + 4 * lq + r) * LR_TP + nloc] = (f16)pe[r];
-      }
-    }
-    if (a.cast_t && (g & 3) == 3) {
-      // the tile's four groups are in (see lo_adamw_lowrank_kernel): 64 rows (k) x 64 columns (n), 128 contiguous bytes per row
-      __builtin_amdgcn_wave_barrier();
-      const f16* tb = &tbuf[wave][0];
-      const size_t n_first = (size_t)(tile0 + NW * (g >> 2)) * 64;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int kk = 8 * j + (lane >> 3), ch = lane & 7;
-        *reinterpret_cast<f16x8*>(a.cast_t + (size_t)(k0 + kk) * a.N + n_first + 8 * ch) = *reinterpret_cast<const f16x8*>(tb + kk * LR_TP + 8 * ch);
-      }
-      __builtin_amdgcn_wave_barrier();
-    }
+    for (int ik = 0; ik < 4; ++ik)
+      lo_lowrank_update_tile(a, c, base + 16 * ik, acc[ik], pv[buf][ik], mv[buf][ik], vv[buf][ik], tb, 16 * ik + 4 * lq, 16 * (g & 3) + l15);
+    if (a.cast_t && (g & 3) == 3) lo_lowrank_flush_block(a, tb, k0, (size_t)(tile0 + NW * (g >> 2)) * 64, lane);
   };
   if (live) { load_y(0); load_pmv(0, 0); }
   for (int i = threadIdx.x; i < 64 * c8n; i += 64 * NW) {
@@ -502,13 +478,12 @@ __global__ __launch_bounds__(64 * NW) void lo_adamw_lowrank_gathered_kernel(LoGa
 //   DOT = true   the factor with the long rows, one c chunk per workgroup: partial[slot] = weight * scale^2 * sum over the block of
 //                small[b][b'] * (sum_{c in chunk} src[c][b] src[c][b'])  -- one slot per workgroup, added in wave order through LDS;
 //                slots beyond pairs x chunks are zeroed.  (A slot of an off-diagonal pair can be negative; their sum is the norm.)
-struct LoGramTLayer { const f16* fshort; const f16* flong; float* gram; float* partial; int n_short, n_long, chunks, per, nslots; };
-struct LoGramTJobs { LoGramTLayer l[2]; size_t rstride; int Bp, KT, nb; float scale2; };
+struct LoGramTJobs { LoGramLayer l[2]; size_t rstride; int Bp, KT, nb; float scale2; };
 template <bool DOT>
 __global__ __launch_bounds__(256) void lo_gram_gathered_kernel(LoGramTJobs J) {
   __shared__ __attribute__((aligned(1024))) unsigned char smem[2][2][64 * 256];      // [buffer][side][64 c rows][128 b]
   __shared__ float wsum[4];
-  const LoGramTLayer L = J.l[blockIdx.y];
+  const LoGramLayer L = J.l[blockIdx.y];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave & 1, wn = wave >> 1;
   const int nb = J.nb, npairs = nb * (nb + 1) / 2, KT = J.KT, Bp = J.Bp;
   const int slot = blockIdx.x, chunks = DOT ? L.chunks : 1;
@@ -646,6 +621,19 @@ int lo_transpose_pad_f16_multi(const f16* const* src, f16* const* dst, const int
   return LO_OK;
 }
 
+// The chunk policy of both norms: a layer's `nslots` partial-sum slots are shared out over `cells` cells of the Gram matrix (64 x 64
+// blocks here, pairs of 128-sample blocks for the gathered form), and each cell's contraction over `steps` steps of the long factor
+// is cut into as many equal chunks as that leaves slots for.  chunks = 0: too few slots.
+static LoGramLayer lowrank_gram_layer(const LoLowrankNorm& in, int cells, int steps) {
+  int chunks = in.nslots / cells, per = 0;
+  if (chunks > steps) chunks = steps;
+  if (chunks >= 1) {
+    per = (steps + chunks - 1) / chunks;
+    chunks = (steps + per - 1) / per;
+  }
+  return {in.fshort, in.flong, in.gram, in.partial, in.n_short, in.n_long, chunks, per, in.nslots};
+}
+
 // ||dY^T X||_F^2 * scale^2 of up to two Linear layers into their `nslots` partial-sum slots each (every slot is written).
 // fshort / flong: the two factors of a layer in their natural layouts [B][n_short], [B][n_long]; gram: [Bp][Bp] fp32 scratch per layer.
 int lo_lowrank_sumsq(const LoLowrankNorm* layers, int nlayers, int B, float scale, hipStream_t st) {
@@ -660,15 +648,8 @@ int lo_lowrank_sumsq(const LoLowrankNorm* layers, int nlayers, int B, float scal
   for (int i = 0; i < nlayers; ++i) {
     const LoLowrankNorm& in = layers[i];
     LO_REQUIRE(in.n_short % 32 == 0 && in.n_long % 32 == 0, "lo_lowrank_sumsq: row lengths must be multiples of 32");
-    int chunks = in.nslots / (nblk * nblk);
-    LO_REQUIRE(chunks >= 1, "lo_lowrank_sumsq: %d partial slots are too few", in.nslots);
-    const int steps = in.n_long / 32;
-    if (chunks > steps) chunks = steps;
-    const int per = (steps + chunks - 1) / chunks;
-    chunks = (steps + per - 1) / per;
-    LoGramLayer& l = J.l[i];
-    l.fshort = in.fshort; l.flong = in.flong; l.gram = in.gram; l.partial = in.partial;
-    l.n_short = in.n_short; l.n_long = in.n_long; l.chunks = chunks; l.per = per; l.nslots = in.nslots;
+    J.l[i] = lowrank_gram_layer(in, nblk * nblk, in.n_long / 32);
+    LO_REQUIRE(J.l[i].chunks >= 1, "lo_lowrank_sumsq: %d partial slots are too few", in.nslots);
     maxslots = in.nslots > maxslots ? in.nslots : maxslots;
     bytes += 2.0 * B * ((double)in.n_short + in.n_long);
   }
@@ -685,26 +666,17 @@ static int lowrank_blocks(const LoLowrankArgs& a, int cap) {
   int nblk = (total + 3) / 4;
   return nblk > cap ? cap : nblk;
 }
-static int lowrank_launch(const LoLowrankPair& A, int nblk_total, bool mat, hipStream_t st) {
-  const int KB = A.l[0].Bp / 32;
-#define LO_LR(KBV)                                                                                                                  \
-  do {                                                                                                                              \
-    if (mat) hipLaunchKernelGGL((lo_adamw_lowrank_kernel<KBV, true>), dim3(nblk_total), dim3(256), 0, st, A);                       \
-    else LO_LAUNCH_STOP((lo_adamw_lowrank_kernel<KBV, false>), dim3(nblk_total), dim3(256), 0, st, A);                              \
-  } while (0)
-  if (KB == 1) LO_LR(1);
-  else if (KB == 2) LO_LR(2);
-  else if (KB == 3) LO_LR(3);
-  else if (KB == 4) LO_LR(4);
-  else { lo_set_error("lo_adamw_lowrank: batch padding %d not supported", A.l[0].Bp); return LO_ERR_ARG; }
-#undef LO_LR
-  LO_LAUNCH_CHECK("adamw_lowrank");
-  return LO_OK;
+// one matrix of either AdamW launch from its table entry; returns the bytes of HBM traffic it stands for
+static double lowrank_fill(LoLowrankArgs& a, const LoLowrankMat& mt, int Bp, float gscale, const LoAdamHyper& hp) {
+  a.p = mt.p; a.m = mt.m; a.v = mt.v; a.cast = mt.cast; a.cast_t = mt.cast_t; a.xt = mt.xt; a.yt = mt.yt; a.N = mt.N; a.K = mt.K; a.Bp = Bp;
+  a.gscale = gscale; a.norm = hp.norm; a.lr = hp.lr; a.beta1 = hp.beta1; a.beta2 = hp.beta2; a.eps = hp.eps; a.wd = hp.wd;
+  a.bc1 = (float)(1.0 - pow((double)hp.beta1, (double)hp.step));
+  a.bc2_sqrt = (float)sqrt(1.0 - pow((double)hp.beta2, (double)hp.step));
+  return (24.0 + (mt.cast ? 2.0 : 0.0) + (mt.cast_t ? 2.0 : 0.0)) * ((double)mt.N * mt.K);
 }
 
 // AdamW of up to two factored weight matrices in ONE launch (the workgroups are shared out in proportion to the element counts)
-int lo_adamw_lowrank(const LoLowrankMat* mats, int nmat, int B, float gscale, const float* norm, float lr, float beta1, float beta2, float eps,
-                     float wd, int step, hipStream_t st) {
+int lo_adamw_lowrank(const LoLowrankMat* mats, int nmat, int B, float gscale, const LoAdamHyper& hp, hipStream_t st) {
   LO_REQUIRE(nmat >= 1 && nmat <= 2, "lo_adamw_lowrank: one or two matrices");
   LoLowrankPair A;
   memset(&A, 0, sizeof(A));
@@ -712,17 +684,13 @@ int lo_adamw_lowrank(const LoLowrankMat* mats, int nmat, int B, float gscale, co
   for (int i = 0; i < nmat; ++i) {
     const LoLowrankMat& mt = mats[i];
     LO_REQUIRE(lo_lowrank_applies(B, mt.N, mt.K), "lo_adamw_lowrank: shape B=%d N=%d K=%d not supported", B, mt.N, mt.K);
-    LoLowrankArgs& a = A.l[i];
-    a.p = mt.p; a.m = mt.m; a.v = mt.v; a.cast = mt.cast; a.cast_t = mt.cast_t; a.gout = nullptr; a.xt = mt.xt; a.yt = mt.yt; a.N = mt.N; a.K = mt.K; a.Bp = lo_lowrank_bp(B);
-    a.gscale = gscale; a.norm = norm; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = wd;
-    a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
-    a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+    bytes += lowrank_fill(A.l[i], mt, lo_lowrank_bp(B), gscale, hp);
     elems[i] = (double)mt.N * mt.K;
-    bytes += (24.0 + (mt.cast ? 2.0 : 0.0) + (mt.cast_t ? 2.0 : 0.0)) * elems[i];
   }
-  // workgroups of the larger matrix.  Two are resident per CU (208 registers); a longer grid measured better on the step, where the
-  // kernel runs beside the next forward: 512 / 1024 / 2048 / 4096 / 8192 -> 23 310 / 23 590 / 23 790 / 23 230 / 23 190 sprites/s
-  // (three interleaved rounds on one box)
+  // workgroups of the larger matrix.  Registers per lane (VGPR + AGPR in the code object, allocated in eights) for KB = Bp / 32 =
+  // 1 / 2 / 3 / 4: 208 / 232 / 252 / 271 -- two workgroups are resident per CU up to KB = 3, one at KB = 4.  A longer grid measured
+  // better on the step (batch 64), where the kernel runs beside the next forward: 512 / 1024 / 2048 / 4096 / 8192 -> 23 310 / 23 590 /
+  // 23 790 / 23 230 / 23 190 sprites/s (three interleaved rounds on one box)
   constexpr int cap = 2048;
   int nb0 = lowrank_blocks(A.l[0], cap), nb1 = 0;
   if (nmat == 2) {
@@ -731,20 +699,20 @@ int lo_adamw_lowrank(const LoLowrankMat* mats, int nmat, int B, float gscale, co
   }
   A.nwg0 = nb0;
   LoProfScope _p("lo_adamw_lowrank", 0, bytes, st);     // HBM-bound: rated against the HBM roofline (2 Bp FLOP per element ride along)
-  return lowrank_launch(A, nb0 + nb1, false, st);
+  const dim3 grid(nb0 + nb1);
+  switch (A.l[0].Bp / 32) {
+    case 1: LO_LAUNCH_STOP((lo_adamw_lowrank_kernel<1>), grid, dim3(256), 0, st, A); break;
+    case 2: LO_LAUNCH_STOP((lo_adamw_lowrank_kernel<2>), grid, dim3(256), 0, st, A); break;
+    case 3: LO_LAUNCH_STOP((lo_adamw_lowrank_kernel<3>), grid, dim3(256), 0, st, A); break;
+    case 4: LO_LAUNCH_STOP((lo_adamw_lowrank_kernel<4>), grid, dim3(256), 0, st, A); break;
+    default: lo_set_error("lo_adamw_lowrank: batch padding %d not supported", A.l[0].Bp); return LO_ERR_ARG;
+  }
+  LO_LAUNCH_CHECK("adamw_lowrank");
+  return LO_OK;
 }
 
-int lo_lowrank_materialize(float* gout, const f16* xt, const f16* yt, int N, int K, int B, float gscale, hipStream_t st) {
-  LO_REQUIRE(lo_lowrank_applies(B, N, K), "lo_lowrank_materialize: shape B=%d N=%d K=%d not supported", B, N, K);
-  LoLowrankPair A;
-  memset(&A, 0, sizeof(A));
-  LoLowrankArgs& a = A.l[0];
-  a.gout = gout; a.xt = xt; a.yt = yt; a.N = N; a.K = K; a.Bp = lo_lowrank_bp(B); a.gscale = gscale;
-  A.nwg0 = lowrank_blocks(a, 512);
-  LoProfScope _p("lo_lowrank_materialize", 0, 4.0 * (double)N * K, st);
-  return lowrank_launch(A, A.nwg0, true, st);
-}
-
+// gout = gscale * sum_r dY_r^T X_r from `world` factor blocks, rank_stride_elems apart.  One block (this rank's own, world = 1) gives
+// tile for tile what lo_adamw_lowrank forms: the same MFMAs in the same kb order, the same `* gscale`
 int lo_lowrank_materialize_gathered(float* gout, const f16* xt, const f16* yt, size_t rank_stride_elems, int world, int N, int K, int B,
                                     float gscale, hipStream_t st) {
   LO_REQUIRE(lo_lowrank_applies(B, N, K) && world >= 1, "lo_lowrank_materialize_gathered: shape B=%d N=%d K=%d world=%d not supported", B, N, K, world);
@@ -766,8 +734,8 @@ size_t lo_lowrank_gathered_gram_elems(int world, int B) { const size_t kt = (siz
 
 // AdamW of up to two weight matrices whose AVERAGED gradient is gscale * sum_r dY_r^T X_r: xt / yt point at the factor inside rank 0's
 // block, rank r's copy sits rank_stride_elems further on per rank.  gscale carries 1 / (loss scale * world).
-int lo_adamw_lowrank_gathered(const LoLowrankMat* mats, int nmat, size_t rank_stride_elems, int world, int B, float gscale, const float* norm,
-                              float lr, float beta1, float beta2, float eps, float wd, int step, hipStream_t st) {
+int lo_adamw_lowrank_gathered(const LoLowrankMat* mats, int nmat, size_t rank_stride_elems, int world, int B, float gscale,
+                              const LoAdamHyper& hp, hipStream_t st) {
   LO_REQUIRE(nmat >= 1 && nmat <= 2, "lo_adamw_lowrank_gathered: one or two matrices");
   const int Bp = lo_lowrank_bp(B);
   LO_REQUIRE(lo_lowrank_gathered_applies(world, B), "lo_adamw_lowrank_gathered: world %d x padded batch %d is outside the combined rank the "
@@ -783,14 +751,8 @@ int lo_adamw_lowrank_gathered(const LoLowrankMat* mats, int nmat, size_t rank_st
     const LoLowrankMat& mt = mats[i];
     LO_REQUIRE(lo_lowrank_applies(B, mt.N, mt.K), "lo_adamw_lowrank_gathered: shape B=%d N=%d K=%d not supported", B, mt.N, mt.K);
     LO_REQUIRE(lo_aligned16(mt.p, mt.m, mt.v, mt.cast, mt.cast_t, mt.xt, mt.yt), "lo_adamw_lowrank_gathered: every tensor pointer must be 16-byte aligned");
-    LoLowrankArgs& a = A.l[i];
-    a.p = mt.p; a.m = mt.m; a.v = mt.v; a.cast = mt.cast; a.cast_t = mt.cast_t; a.gout = nullptr; a.xt = mt.xt; a.yt = mt.yt; a.N = mt.N; a.K = mt.K; a.Bp = Bp;
-    a.gscale = gscale; a.norm = norm; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = wd;
-    a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
-    a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
-    const double elems = (double)mt.N * mt.K;
-    bytes += (24.0 + (mt.cast ? 2.0 : 0.0) + (mt.cast_t ? 2.0 : 0.0)) * elems;
-    flops += 2.0 * world * Bp * elems;
+    bytes += lowrank_fill(A.l[i], mt, Bp, gscale, hp);
+    flops += 2.0 * world * Bp * ((double)mt.N * mt.K);
     nwg[i] = (mt.K / 64) * ((mt.N / 64 + tpw * nw - 1) / (tpw * nw));
   }
   A.nwg0 = nwg[0];
@@ -823,15 +785,8 @@ int lo_lowrank_sumsq_gathered(const LoLowrankNorm* layers, int nlayers, size_t r
     const LoLowrankNorm& in = layers[i];
     LO_REQUIRE(in.n_short >= 32 && in.n_long >= 32 && in.n_short % 32 == 0 && in.n_long % 32 == 0, "lo_lowrank_sumsq_gathered: row lengths must be multiples of 32");
     LO_REQUIRE(lo_aligned16(in.fshort, in.flong), "lo_lowrank_sumsq_gathered: the factor pointers must be 16-byte aligned");
-    int chunks = in.nslots / npairs;
-    LO_REQUIRE(chunks >= 1, "lo_lowrank_sumsq_gathered: %d partial slots are too few", in.nslots);
-    const int steps = (in.n_long + 63) / 64;     // 64 rows of the long factor per step
-    if (chunks > steps) chunks = steps;
-    const int per = (steps + chunks - 1) / chunks;
-    chunks = (steps + per - 1) / per;
-    LoGramTLayer& l = J.l[i];
-    l.fshort = in.fshort; l.flong = in.flong; l.gram = in.gram; l.partial = in.partial;
-    l.n_short = in.n_short; l.n_long = in.n_long; l.chunks = chunks; l.per = per; l.nslots = in.nslots;
+    J.l[i] = lowrank_gram_layer(in, npairs, (in.n_long + 63) / 64);     // 64 rows of the long factor per step
+    LO_REQUIRE(J.l[i].chunks >= 1, "lo_lowrank_sumsq_gathered: %d partial slots are too few", in.nslots);
     maxslots = in.nslots > maxslots ? in.nslots : maxslots;
     bytes += 2.0 * J.KT * ((double)in.n_short + in.n_long);
     flops += 2.0 * 128 * 128 * npairs * ((double)in.n_short + in.n_long);

@@ -54,6 +54,19 @@ struct ConvLayer {           // conv + GroupNorm + Mish
   int sk_fwd = 0, sk_dgrad = 0;
 };
 
+// How the weight gradients of fc_mu | fc_logvar and decoder.fc travel through a fused step (lo_vae_set_linear_factored's numbers;
+// DESIGN.md has the table).  Readers ask the predicates below, never the value.
+enum class LoLinearMode : int {
+  off = 0,           // written to the flat buffer like every other gradient
+  local = 1,         // single process: the backward leaves factors + their share of the norm, AdamW forms the tiles
+  dp_factors = 2,    // data parallel: phase 1 leaves factors, the ranks all-gather them and write the averaged matrices out
+  dp_gathered = 3,   // ... and never write them: norm and AdamW read the gathered blocks
+};
+// What one step leaves for the next optimizer step.  ready: a fused backward (mode 3: + lo_vae_gathered_early_norm) has left this
+// step's factors and the Gram part of the gradient norm; scale: 1 / loss scale of that backward; gathered / world: the blocks
+// lo_vae_gathered_early_norm was given (the caller keeps them alive and unchanged until the step that follows has read them)
+struct LoFactorStep { bool ready = false; float scale = 1.f; const f16* gathered = nullptr; int world = 0; };
+
 struct LoVae {
   int B = 0, L = 0;
   // parameters
@@ -96,7 +109,7 @@ struct LoVae {
   bool lvl_pending[6] = {};
   // pipelined optimizer step: levels 2..5 (AdamW of 97 % of the parameters + their operand refresh) are ENQUEUED by the next
   // forward once its first stage has run -- see lo_vae_optimizer_step
-  struct { bool pending = false; float* P; const float* G; float* M; float* V; void* ws; const float* norm; float lr, beta1, beta2, eps, wd; int step; } defer;
+  struct { bool pending = false; float* P; const float* G; float* M; float* V; void* ws; LoAdamHyper hp; } defer;
   int n_packjobs_s4 = 0, pack_blocks_s4 = 0, n_packjobs8_s4 = 0, pack_blocks8_s4 = 0;   // job-table prefix up to and including encoder stage 4
   int bwd_layer = 0;         // conv layers processed so far in the current backward (selects the dv buffer / events)
   size_t o_skslab = 0;       // slabs of the split-K convolutions (one launch at a time on the caller's stream)
@@ -109,18 +122,11 @@ struct LoVae {
   bool fuse_gna = true;      // fuse the GroupNorm-backward APPLY pass into the data-gradient epilogue that already carries its reduction
   size_t o_sync_fail = 0;    // one word: set by a workgroup whose rendezvous poll ran out (never, unless a launch was lost)
   // rank-B Linear-layer weight gradients kept as their factors (lo_lowrank.hip): transposed, batch-padded factor copies
-  // dml^T [2L][Bp], xflat^T [32768][Bp], Gfc^T [32768][Bp], z^T [L][Bp] (one contiguous block), Gram scratch; fac_ready: a fused
-  // backward has left this step's factors and the Gram part of the gradient norm; fac_scale: 1 / loss scale of that backward
-  bool lin_factored = false, fac_ready = false;
-  bool lin_factored_dp = false;   // data parallel: phase 1 leaves the factors (no Linear weight gradients); the ranks all-gather them
-  // ... and mode 3 on top of it: norm and AdamW read the gathered blocks (lo_vae_gathered_early_norm remembers where they are; the
-  // caller keeps the buffer alive and unchanged until the step that follows has read it -- see lo_vae_gathered_early_norm)
-  bool lin_gathered = false;
-  const f16* fac_gathered = nullptr;
-  int fac_world = 0;
+  // dml^T [2L][Bp], xflat^T [32768][Bp], Gfc^T [32768][Bp], z^T [L][Bp] (one contiguous block), Gram scratch
+  LoLinearMode lin_mode = LoLinearMode::off;
+  LoFactorStep fac;
   int Bp = 0;
   size_t o_fac_dmlT = 0, o_fac_xT = 0, o_fac_gfcT = 0, o_fac_zT = 0, o_gram = 0;
-  float fac_scale = 1.f;
   int n_cu = 0;              // compute units of the device (partition) this plan was made on; 0 = no device: nothing that waits across workgroups is planned
   const void* sync_for_ws = nullptr;
   // fp8 operand mode of the forward convs (lo_vae_create_ex flag LO_VAE_FP8_FWD)
@@ -200,8 +206,16 @@ struct LoProfTag {
   ~LoProfTag() { end(); }
 };
 
-// the optimizer step forms the two Linear weight gradients from factors (this rank's: mode 1; the gathered blocks: mode 3)
-static inline bool vae_fac_opt(const LoVae* h) { return h->lin_factored || h->lin_gathered; }
+// the optimizer step forms the tiles of the two Linear weight gradients from factors (modes 1, 3)
+static inline bool vae_opt_from_factors(const LoVae* h) { return h->lin_mode == LoLinearMode::local || h->lin_mode == LoLinearMode::dp_gathered; }
+// ... and those factors are the gathered blocks of every rank, not this rank's own in the workspace (mode 3)
+static inline bool vae_factors_gathered(const LoVae* h) { return h->lin_mode == LoLinearMode::dp_gathered; }
+// a fused single-call backward leaves factors and their share of the norm instead of the two matrices (mode 1)
+static inline bool vae_single_leaves_factors(const LoVae* h) { return h->lin_mode == LoLinearMode::local; }
+// a fused phase-1 backward leaves factors for the ranks to all-gather instead of the two matrices (modes 2, 3)
+static inline bool vae_phased_leaves_factors(const LoVae* h) { return h->lin_mode == LoLinearMode::dp_factors || h->lin_mode == LoLinearMode::dp_gathered; }
+// the flat gradient buffer lacks the two matrices after a step: the mode's number (1 / 3), else 0 -- what lo_vae_linear_factored returns
+static inline int vae_flat_lacks_linear(const LoVae* h) { return vae_opt_from_factors(h) ? (int)h->lin_mode : 0; }
 // Gathered factor blocks (data parallel): every rank's block keeps the workspace's layout dml^T | xflat^T | Gfc^T | z^T.  Elements from
 // one rank's block to the next, and where the factor at workspace offset o_fac sits inside rank 0's block of `gathered`:
 static inline size_t vae_fac_block_elems(const LoVae* h) { return (h->o_gram - h->o_fac_dmlT) / 2; }

@@ -70,17 +70,15 @@ static LoLinearRanges vae_linear_ranges(const LoVae* h, float* P, float* M, floa
   const size_t bh = h->p_off[h->idx_fc_mu_w], bd = h->p_off[h->idx_dfc_w];
   auto copy = [&](size_t off) -> f16* { return casts ? WSP(f16, off) : nullptr; };
   // mode 3: the factors of rank 0's block of the gathered buffer (the blocks keep the workspace's layout; rank stride = block size)
-  auto fac = [&](size_t off) -> const f16* { return h->lin_gathered ? vae_fac_in_block(h, h->fac_gathered, off) : WSP(f16, off); };
+  auto fac = [&](size_t off) -> const f16* { return vae_factors_gathered(h) ? vae_fac_in_block(h, h->fac.gathered, off) : WSP(f16, off); };
   return {bh, (size_t)2 * L * 32768, bd, (size_t)32768 * L,
           {{P + bh, M + bh, V + bh, copy(h->o_wp_head), copy(h->o_wp_head_t), fac(h->o_fac_xT), fac(h->o_fac_dmlT), 2 * L, 32768},
            {P + bd, M + bd, V + bd, copy(h->o_wp_dfc), copy(h->o_wp_dfc_t), fac(h->o_fac_zT), fac(h->o_fac_gfcT), 32768, L}}};
 }
-// AdamW of the two matrices from their factors: this rank's (mode 1) or the `fac_world` gathered blocks, 1 / world folded into the scale
-static int vae_adamw_linear(const LoVae* h, const LoLinearRanges& r, const float* norm, float lr, float beta1, float beta2, float eps, float wd,
-                            int step, hipStream_t st) {
-  if (!h->lin_gathered) return lo_adamw_lowrank(r.lrm, 2, h->B, h->fac_scale, norm, lr, beta1, beta2, eps, wd, step, st);
-  return lo_adamw_lowrank_gathered(r.lrm, 2, vae_fac_block_elems(h), h->fac_world, h->B, h->fac_scale / (float)h->fac_world, norm, lr, beta1,
-                                   beta2, eps, wd, step, st);
+// AdamW of the two matrices from their factors: this rank's (mode 1) or the `fac.world` gathered blocks, 1 / world folded into the scale
+static int vae_adamw_linear(const LoVae* h, const LoLinearRanges& r, const LoAdamHyper& hp, hipStream_t st) {
+  if (!vae_factors_gathered(h)) return lo_adamw_lowrank(r.lrm, 2, h->B, h->fac.scale, hp, st);
+  return lo_adamw_lowrank_gathered(r.lrm, 2, vae_fac_block_elems(h), h->fac.world, h->B, h->fac.scale / (float)h->fac.world, hp, st);
 }
 
 // Levels 2..5 of a pipelined optimizer step: AdamW of everything from the encoder's last stage on, in the order the forward needs
@@ -99,7 +97,7 @@ int vae_flush_deferred(LoVae* h, hipStream_t after_main) {
   const LoPackJob* jobs = WSP(LoPackJob, h->o_packjobs);
   const LoPackF8Job* jobs8 = WSP(LoPackF8Job, h->o_packjobs8);
   auto adam = [&](size_t lo, size_t hi, f16* cast = nullptr) {
-    return hi > lo ? lo_adamw(P + lo, G + lo, M + lo, V + lo, hi - lo, d.norm, d.lr, d.beta1, d.beta2, d.eps, d.wd, d.step, sd, cast) : LO_OK;
+    return hi > lo ? lo_adamw(P + lo, G + lo, M + lo, V + lo, hi - lo, d.hp, sd, cast) : LO_OK;
   };
   // level 2: encoder stage 4 (10 % of the parameters): first consumer ~0.45 ms into the forward
   LO_TRY(adam(b4, bh));
@@ -112,19 +110,19 @@ int vae_flush_deferred(LoVae* h, hipStream_t after_main) {
   // pass: +0.6 % on the step against the separate transposes, 25 002 / 25 077 / 24 998 vs 24 720 / 25 047 / 24 867)
   // Factored: both matrices (fc_mu | fc_logvar and decoder.fc) in one launch: the forward needs neither before the end of the
   // encoder, ~1 ms away, and one launch has one ramp and one tail
-  if (vae_fac_opt(h)) LO_TRY(vae_adamw_linear(h, r, d.norm, d.lr, d.beta1, d.beta2, d.eps, d.wd, d.step, sd));
+  if (vae_opt_from_factors(h)) LO_TRY(vae_adamw_linear(h, r, d.hp, sd));
   else LO_TRY(adam(bh, bh + nh, WSP(f16, h->o_wp_head)));
   LO_TRY(adam(bh + nh, bd));
   LO_TRY(vae_side_record(h, 3, sd));
   // level 4: decoder.fc (unless it went with the encoder heads), the decoder and final convs
-  if (!vae_fac_opt(h)) LO_TRY(adam(bd, bd + nd, WSP(f16, h->o_wp_dfc)));
+  if (!vae_opt_from_factors(h)) LO_TRY(adam(bd, bd + nd, WSP(f16, h->o_wp_dfc)));
   LO_TRY(adam(bd + nd, n));
   LO_TRY(lo_pack_all(jobs + h->n_packjobs_s4, h->n_packjobs - h->n_packjobs_s4, h->pack_blocks - h->pack_blocks_s4, sd, h->pack_blocks_s4));
   if (h->fp8_fwd)
     LO_TRY(lo_pack_f8_all(jobs8 + h->n_packjobs8_s4, h->n_packjobs8 - h->n_packjobs8_s4, h->pack_blocks8 - h->pack_blocks8_s4, sd, h->pack_blocks8_s4));
   LO_TRY(vae_side_record(h, 4, sd));
   // level 5: the transposed copies (data gradients of the Linear layers: backward only); the factored AdamW pass has written them
-  if (!vae_fac_opt(h)) LO_TRY(vae_linear_transposes(h, ws, sd));
+  if (!vae_opt_from_factors(h)) LO_TRY(vae_linear_transposes(h, ws, sd));
   return vae_side_record(h, 5, sd);
 }
 
@@ -190,13 +188,13 @@ extern "C" int lo_vae_optimizer_step(LoVae* h, float* P, const float* G, float* 
   // and skips the update on the device, like a non-finite norm (ADVICE r3 / VERDICT r3 item 1b)
   const unsigned int* fail = WSP(unsigned int, h->o_sync_fail);
   hipStream_t st = S(stream);
-  if (vae_fac_opt(h)) {
-    if (!h->fac_ready || !presummed) {
+  if (vae_opt_from_factors(h)) {
+    if (!h->fac.ready || !presummed) {
       lo_set_error("lo_vae_optimizer_step: the factored Linear-gradient mode needs a fused lo_vae_backward (with the gradient-norm scratch set; "
                    "mode 3: lo_vae_backward_phase and lo_vae_gathered_early_norm) before every step, and LO_OPT_PRESUMMED");
       return LO_ERR_STATE;
     }
-    h->fac_ready = false;
+    h->fac.ready = false;
   }
   LO_TRY(vae_flush_deferred(h, nullptr));     // two optimizer steps without a forward in between
   // b: begin of the range whose sum of squares may be presummed (fc_mu.weight);  b4: begin of the encoder's last stage -- the
@@ -205,13 +203,13 @@ extern "C" int lo_vae_optimizer_step(LoVae* h, float* P, const float* G, float* 
   LO_TRY(vae_ensure_pack_jobs(h, P, ws, st));
   if (presummed) LO_TRY(lo_gradnorm_split(G, b, max_norm, scratch, scratch + 1024, st, fail));
   else LO_TRY(lo_gradnorm(G, n, max_norm, scratch, scratch + 1024, st, fail));
-  const float* norm = scratch + 1024;
+  const LoAdamHyper hp = {scratch + 1024, lr, beta1, beta2, eps, weight_decay, step};
   if (serial || !vae_side_on(h)) {
-    auto adam = [&](size_t lo, size_t hi) { return lo_adamw(P + lo, G + lo, M + lo, V + lo, hi - lo, norm, lr, beta1, beta2, eps, weight_decay, step, st); };
-    if (vae_fac_opt(h)) {
+    auto adam = [&](size_t lo, size_t hi) { return lo_adamw(P + lo, G + lo, M + lo, V + lo, hi - lo, hp, st); };
+    if (vae_opt_from_factors(h)) {
       const LoLinearRanges r = vae_linear_ranges(h, P, M, V, ws, false);      // no copies: lo_vae_pack below makes them
       LO_TRY(adam(0, r.bh));
-      LO_TRY(vae_adamw_linear(h, r, norm, lr, beta1, beta2, eps, weight_decay, step, st));
+      LO_TRY(vae_adamw_linear(h, r, hp, st));
       LO_TRY(adam(r.bh + r.nh, r.bd));
       LO_TRY(adam(r.bd + r.nd, n));
     } else {
@@ -221,7 +219,7 @@ extern "C" int lo_vae_optimizer_step(LoVae* h, float* P, const float* G, float* 
   }
   {
     LoHandover ho(h->ev_pre, true);      // the hand-over event rides on the AdamW launch (LO_LAUNCH_STOP)
-    LO_TRY(lo_adamw(P, G, M, V, b4, norm, lr, beta1, beta2, eps, weight_decay, step, st));
+    LO_TRY(lo_adamw(P, G, M, V, b4, hp, st));
     LO_TRY(ho.finish(st));
   }
   hipStream_t sd = h->side;
@@ -229,7 +227,7 @@ extern "C" int lo_vae_optimizer_step(LoVae* h, float* P, const float* G, float* 
   LO_TRY(lo_pack_all(WSP(LoPackJob, h->o_packjobs), h->n_packjobs_enc, h->pack_blocks_enc, sd));
   if (h->fp8_fwd) LO_TRY(lo_pack_f8_all(WSP(LoPackF8Job, h->o_packjobs8), h->n_packjobs8_enc, h->pack_blocks8_enc, sd));
   LO_TRY(vae_side_record(h, 1, sd));
-  h->defer = {true, P, G, M, V, ws, norm, lr, beta1, beta2, eps, weight_decay, step};
+  h->defer = {true, P, G, M, V, ws, hp};
   // (deferring this tail behind the next forward's first stage was measured in round 2: no difference -- where the AdamW traffic
   // lands only changes WHICH kernels it slows down, not the sum -- so it is enqueued at once)
   LO_TRY(vae_flush_deferred(h, nullptr));
@@ -251,13 +249,9 @@ extern "C" int lo_vae_join(LoVae* h, void* stream) {
 // ordered behind that backward (it is, for the stream the backward ran on).
 extern "C" int lo_vae_materialize_linear_grads(LoVae* h, void* ws, float* G, void* stream) {
   LO_REQUIRE(h && ws && G, "lo_vae_materialize_linear_grads: null argument");
-  if (!vae_fac_opt(h)) return LO_OK;            // the backward (mode 2: the exchange) wrote them itself
-  hipStream_t st = S(stream);
-  const int L = h->L;
-  if (h->lin_gathered) {                        // mode 3: the averaged matrices from the gathered blocks the last norm call was given
-    if (!h->fac_gathered) { lo_set_error("lo_vae_materialize_linear_grads: mode 3 has not seen lo_vae_gathered_early_norm yet"); return LO_ERR_STATE; }
-    return lo_vae_materialize_gathered_linear_grads(h, h->fac_gathered, h->fac_world, G, stream);
-  }
-  LO_TRY(lo_lowrank_materialize(G + h->p_off[h->idx_fc_mu_w], WSP(f16, h->o_fac_xT), WSP(f16, h->o_fac_dmlT), 2 * L, 32768, h->B, h->fac_scale, st));
-  return lo_lowrank_materialize(G + h->p_off[h->idx_dfc_w], WSP(f16, h->o_fac_zT), WSP(f16, h->o_fac_gfcT), 32768, L, h->B, h->fac_scale, st);
+  if (!vae_opt_from_factors(h)) return LO_OK;   // the backward (mode 2: the exchange) wrote them itself
+  // mode 1: this rank's factor block in the workspace, alone; mode 3: the gathered blocks the last norm call was given
+  const bool gathered = vae_factors_gathered(h);
+  if (gathered && !h->fac.gathered) { lo_set_error("lo_vae_materialize_linear_grads: mode 3 has not seen lo_vae_gathered_early_norm yet"); return LO_ERR_STATE; }
+  return lo_vae_materialize_gathered_linear_grads(h, gathered ? h->fac.gathered : WSP(f16, h->o_fac_dmlT), gathered ? h->fac.world : 1, G, stream);
 }

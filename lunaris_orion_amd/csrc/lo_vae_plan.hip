@@ -323,7 +323,7 @@ extern "C" int lo_vae_set_gradnorm_scratch(LoVae* h, float* scratch) {
   h->norm_scratch = scratch;
   return LO_OK;
 }
-extern "C" int lo_vae_gradnorm_presummed(const LoVae* h) { return h && h->norm_scratch && (vae_side_on(h) || h->lin_factored); }
+extern "C" int lo_vae_gradnorm_presummed(const LoVae* h) { return h && h->norm_scratch && (vae_side_on(h) || vae_single_leaves_factors(h)); }
 // Factored Linear-layer gradients (lo_lowrank.hip): with the mode on, a FUSED single-call lo_vae_backward does not write the weight
 // gradients of fc_mu | fc_logvar and decoder.fc into flat_grads (those ranges keep whatever they held); it leaves their factors and
 // their share of the gradient norm (needs lo_vae_set_gradnorm_scratch), and lo_vae_optimizer_step forms the gradient tiles inside
@@ -334,12 +334,8 @@ extern "C" int lo_vae_set_linear_factored(LoVae* h, int on) {
              "or 3 (data parallel: factored AdamW and norm from the gathered factors)");
   if (on) LO_REQUIRE(lo_lowrank_applies(h->B, 2 * h->L, 32768) && lo_lowrank_applies(h->B, 32768, h->L),
                      "lo_vae_set_linear_factored: batch %d is above the rank the factored update is built for (128)", h->B);
-  h->lin_factored = on == 1;
-  h->lin_factored_dp = on == 2 || on == 3;
-  h->lin_gathered = on == 3;
-  h->fac_ready = false;
-  h->fac_gathered = nullptr;
-  h->fac_world = 0;
+  h->lin_mode = (LoLinearMode)on;
+  h->fac = LoFactorStep{};
   return LO_OK;
 }
 // Mode 3: the gathered blocks stay the only form of the two Linear weight gradients (block addressing: lo_vae.h)
@@ -359,7 +355,7 @@ extern "C" size_t lo_vae_gathered_scratch_bytes(const LoVae* h, int world) {
 extern "C" int lo_vae_gathered_early_norm(LoVae* h, const void* gathered, int world, float* gram_scratch, const float* G, float* scratch,
                                           void* stream) {
   LO_REQUIRE(h && gathered && gram_scratch && G && scratch, "lo_vae_gathered_early_norm: null argument");
-  if (!h->lin_gathered) { lo_set_error("lo_vae_gathered_early_norm: needs mode 3 of lo_vae_set_linear_factored"); return LO_ERR_STATE; }
+  if (!vae_factors_gathered(h)) { lo_set_error("lo_vae_gathered_early_norm: needs mode 3 of lo_vae_set_linear_factored"); return LO_ERR_STATE; }
   LO_REQUIRE(lo_lowrank_gathered_applies(world, h->B), "lo_vae_gathered_early_norm: world %d x padded batch %d is above the combined rank "
              "the gathered update is built for (512): use mode 2", world, h->Bp);
   hipStream_t st = S(stream);
@@ -372,10 +368,10 @@ extern "C" int lo_vae_gathered_early_norm(LoVae* h, const void* gathered, int wo
   const LoLowrankNorm nl[2] = {
       {vae_fac_in_block(h, base, h->o_fac_dmlT), 2 * L, vae_fac_in_block(h, base, h->o_fac_xT), 32768, gram_scratch, scratch + 768, 128},
       {vae_fac_in_block(h, base, h->o_fac_zT), L, vae_fac_in_block(h, base, h->o_fac_gfcT), 32768, gram_scratch + kt * kt, scratch + 896, 128}};
-  LO_TRY(lo_lowrank_sumsq_gathered(nl, 2, vae_fac_block_elems(h), world, h->B, h->fac_scale / (float)world, st));
-  h->fac_gathered = base;
-  h->fac_world = world;
-  h->fac_ready = true;
+  LO_TRY(lo_lowrank_sumsq_gathered(nl, 2, vae_fac_block_elems(h), world, h->B, h->fac.scale / (float)world, st));
+  h->fac.gathered = base;
+  h->fac.world = world;
+  h->fac.ready = true;
   return LO_OK;
 }
 // data parallel (mode 2): where the factor block -- dml^T | xflat^T | Gfc^T | z^T, transposed and batch-padded fp16, one contiguous
@@ -394,7 +390,7 @@ extern "C" int lo_vae_materialize_gathered_linear_grads(LoVae* h, const void* ga
   const int L = h->L;
   const size_t blk = vae_fac_block_elems(h);
   const f16* base = reinterpret_cast<const f16*>(gathered);
-  const float sc = h->fac_scale / (float)world;
+  const float sc = h->fac.scale / (float)world;
   LO_TRY(lo_lowrank_materialize_gathered(G + h->p_off[h->idx_fc_mu_w], vae_fac_in_block(h, base, h->o_fac_xT), vae_fac_in_block(h, base, h->o_fac_dmlT),
                                          blk, world, 2 * L, 32768, h->B, sc, st));
   return lo_lowrank_materialize_gathered(G + h->p_off[h->idx_dfc_w], vae_fac_in_block(h, base, h->o_fac_zT), vae_fac_in_block(h, base, h->o_fac_gfcT),
@@ -402,7 +398,7 @@ extern "C" int lo_vae_materialize_gathered_linear_grads(LoVae* h, const void* ga
 }
 // non-zero: the flat gradient buffer does not hold the two matrices after a step (1 or 3 = the mode; lo_vae_materialize_linear_grads
 // writes them out).  Mode 2 materialises them itself: 0
-extern "C" int lo_vae_linear_factored(const LoVae* h) { return !h ? 0 : (h->lin_factored ? 1 : (h->lin_gathered ? 3 : 0)); }
+extern "C" int lo_vae_linear_factored(const LoVae* h) { return h ? vae_flat_lacks_linear(h) : 0; }
 extern "C" int lo_vae_num_params(const LoVae* h) { return h->nparam; }
 extern "C" size_t lo_vae_param_offset(const LoVae* h, int i) { return (i >= 0 && i < h->nparam) ? h->p_off[i] : (size_t)-1; }
 extern "C" size_t lo_vae_param_numel(const LoVae* h, int i) { return (i >= 0 && i < h->nparam) ? h->p_numel[i] : 0; }
@@ -468,7 +464,7 @@ extern "C" int lo_lowrank_gathered_adamw(float* p, float* m, float* v, void* cas
   LO_REQUIRE(p && m && v && xt && yt && step >= 1, "lo_lowrank_gathered_adamw: bad argument");
   const LoLowrankMat mt = {p, m, v, reinterpret_cast<f16*>(cast), reinterpret_cast<f16*>(cast_t), reinterpret_cast<const f16*>(xt),
                            reinterpret_cast<const f16*>(yt), N, K};
-  return lo_adamw_lowrank_gathered(&mt, 1, rank_stride_elems, world, batch, gscale, norm, lr, beta1, beta2, eps, weight_decay, step, S(stream));
+  return lo_adamw_lowrank_gathered(&mt, 1, rank_stride_elems, world, batch, gscale, {norm, lr, beta1, beta2, eps, weight_decay, step}, S(stream));
 }
 
 // ... and the two passes of the optimizer's materialised path they are measured against (tools/op_bench.py --op lowrank_gathered)

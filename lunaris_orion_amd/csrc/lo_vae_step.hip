@@ -460,8 +460,8 @@ int VaeBackward::early_norm(bool fac1) {
   const LoLowrankNorm nl[2] = {{WSP(f16, h->o_dml), 2 * L, WSP(f16, h->o_xflat), 32768, WSP(float, h->o_gram), sc + 768, 128},
                                {WSP(f16, h->o_z), L, WSP(f16, h->o_gfc), 32768, WSP(float, h->o_gram) + 128 * 128, sc + 896, 128}};
   LO_TRY(lo_lowrank_sumsq(nl, 2, h->B, inv, ns));
-  h->fac_scale = inv;
-  h->fac_ready = true;
+  h->fac.scale = inv;
+  h->fac.ready = true;
   return LO_OK;
 }
 
@@ -524,9 +524,9 @@ extern "C" int lo_vae_backward_dx(LoVae* h, const float* x, const float* P, void
   VaeBackward b(h, P, G, ws, loss_scale, stream);
   LO_TRY(b.begin(true));
   // the Linear layers' weight gradients stay factored (lo_lowrank.hip): the fused single-call backward of a stepper only
-  const bool fac1 = h->lin_factored && fused;
+  const bool fac1 = vae_single_leaves_factors(h) && fused;
   if (fac1 && !h->norm_scratch) { lo_set_error("lo_vae_backward: the factored Linear-gradient mode needs lo_vae_set_gradnorm_scratch"); return LO_ERR_STATE; }
-  h->fac_ready = false;
+  h->fac.ready = false;
   // decoder layers finalized early, norm of [fc_mu.weight, end) taken beside the encoder backward
   const bool early = h->norm_scratch && (b.side || fac1);
   LO_TRY(vae_zero_gaps(h, G, (b.side && fused) ? h->side : b.st));
@@ -558,12 +558,12 @@ extern "C" int lo_vae_backward_phase(LoVae* h, int phase, const float* x, const 
   LO_TRY(b.begin(phase == 1));
   const bool async = b.side && h->async_handover;
   if (phase == 1) {
-    const bool facdp = h->lin_factored_dp && fused;     // data parallel: the factors leave this rank, not the gradients
-    h->fac_ready = false;
+    const bool facdp = vae_phased_leaves_factors(h) && fused;    // data parallel: the factors leave this rank, not the gradients
+    h->fac.ready = false;
     LO_TRY(vae_zero_gaps(h, G, (b.side && fused) ? h->side : b.st));
     LO_TRY(b.decoder_chain(fused, recon, target, drecon, facdp, nullptr));
     LO_TRY(b.latent_and_heads(fused, gmu, glv, facdp, true, async));
-    if (facdp) h->fac_scale = b.inv;
+    if (facdp) h->fac.scale = b.inv;
     // every gradient from fc_mu.weight to the end of the buffer is complete now: hand the range over, or join the side stream
     // (decoder weight gradients) and finish the decoder's GroupNorm / bias gradients, so that the caller can start exchanging
     // that range while the encoder backward runs

@@ -160,19 +160,25 @@ class FlatGradSync:
         if (self.world == 1 and not self.force) or g.numel() == 0:
             return False
         self._phase_bytes.append(g.numel() * (2 if (self.compress and g.numel() >= self.compress_min_elems) else g.element_size()))
-        if not g.is_cuda:
-            self._run(g)                                  # CPU tensors (gloo tests): synchronous
+        return self._enqueue(g, lambda on_gpu: self._run(g, sumsq_scratch if on_gpu else None), then, pre)
+
+    def _enqueue(self, t: torch.Tensor, body, then, pre) -> bool:
+        """One hand-over: `body(on_gpu)` on the communication stream, which first waits for what the current stream holds now (`t` is
+        final once that has run), between the `pre` and `then` hooks; its completion is left as an event for finish().  CPU tensors
+        (gloo tests): `body` alone, synchronously, no hooks.  Returns whether the hooks were enqueued."""
+        if not t.is_cuda:
+            body(False)
             self._pending.append(None)
             return False
         if self._comm is None:
-            self._comm = torch.cuda.Stream(device=g.device)
+            self._comm = torch.cuda.Stream(device=t.device)
         ready = torch.cuda.Event()
-        ready.record()                                    # `g` is final once the work enqueued so far has run
+        ready.record()
         self._comm.wait_event(ready)
         with torch.cuda.stream(self._comm):
             if pre is not None:
                 pre()
-            self._run(g, sumsq_scratch)
+            body(True)
             if then is not None:
                 then()
             done = torch.cuda.Event()
@@ -203,31 +209,13 @@ class FlatGradSync:
         if self.world == 1 and not self.force:
             return False
         self._phase_bytes.append(factors.numel() * factors.element_size() + sum(p.numel() * p.element_size() for p in pieces))
-        if not factors.is_cuda:                           # CPU tensors (gloo tests): synchronous
+
+        def body(on_gpu):
             materialize(self.gather(factors), self.world)
             self._mode_log.append("factors")
             for p in pieces:
                 self._run(p)
-            self._pending.append(None)
-            return False
-        if self._comm is None:
-            self._comm = torch.cuda.Stream(device=factors.device)
-        ready = torch.cuda.Event()
-        ready.record()
-        self._comm.wait_event(ready)
-        with torch.cuda.stream(self._comm):
-            if pre is not None:
-                pre()
-            materialize(self.gather(factors), self.world)
-            self._mode_log.append("factors")
-            for p in pieces:
-                self._run(p)
-            if then is not None:
-                then()
-            done = torch.cuda.Event()
-            done.record()
-        self._pending.append(done)
-        return True
+        return self._enqueue(factors, body, then, pre)
 
     def finish(self) -> None:
         ev = None

@@ -16,6 +16,7 @@ The teacher's contribution is the detached scalar ``mean_advantage`` (SURVEY §3
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 import os
 from typing import Callable, Dict, Optional
@@ -40,6 +41,20 @@ def cosine_warm_restarts_lr(base_lr: float, eta_min: float, t0: int, t_mult: int
         t_cur -= t_i
         t_i *= t_mult
     return eta_min + (base_lr - eta_min) * (1.0 + math.cos(math.pi * t_cur / t_i)) / 2.0
+
+
+def _set_linear_mode(eng, mode: int) -> None:
+    """lo_vae_set_linear_factored, if the engine is not in that mode already (`eng.fac_mode` mirrors the library's state)."""
+    if eng.fac_mode != mode:
+        _lib.check(_lib.lib.lo_vae_set_linear_factored(eng.handle, mode), "lo_vae_set_linear_factored")
+        eng.fac_mode = mode
+
+
+def _grad_range(eng, query: str):
+    """One of the library's two-`size_t` queries on an engine (the lo_vae_*_grad_range family, lo_vae_factor_block) as a pair of ints."""
+    first, second = C.c_size_t(), C.c_size_t()
+    _lib.check(getattr(_lib.lib, query)(eng.handle, C.byref(first), C.byref(second)), query)
+    return first.value, second.value
 
 
 class LossScalePolicy:
@@ -95,14 +110,16 @@ class VAEStepper:
         # their factors -- norm from Gram matrices, gradient tiles formed inside the AdamW pass (csrc/lo_lowrank.hip) -- instead of
         # writing and re-reading 201 MB.  Single process, batch <= 128; LO_LINEAR_FACTORED=0: the materialised path (A/B).
         # `parameter_grads()` still returns all 72 gradients (the two matrices are written out on demand).
-        self.linear_factored = grad_sync is None and os.environ.get("LO_LINEAR_FACTORED", "1") != "0"
+        knob = os.environ.get("LO_LINEAR_FACTORED", "1")
+        self.linear_factored = grad_sync is None and knob != "0"
         # data parallel: the ranks all-gather the FACTORS (8.6 MB of fp16 per rank, exact) instead of exchanging the 201 MB of Linear
         # weight gradients, and each forms the averaged gradient from the gathered blocks (FlatGradSync.begin_factored)
-        self.dp_factored = hasattr(grad_sync, "begin_factored") and os.environ.get("LO_LINEAR_FACTORED", "1") != "0"
+        self.dp_factored = hasattr(grad_sync, "begin_factored") and knob != "0"
         # ... and, opt-in (LO_LINEAR_FACTORED=2, or dp_factored_adamw=True), never writes the averaged matrices either: norm and AdamW
         # read the gathered blocks (mode 3 of lo_vae_set_linear_factored; world * padded batch <= 512, else mode 2 as above)
-        self.dp_factored_adamw = (os.environ.get("LO_LINEAR_FACTORED", "1") == "2") if dp_factored_adamw is None else bool(dp_factored_adamw)
+        self.dp_factored_adamw = (knob == "2") if dp_factored_adamw is None else bool(dp_factored_adamw)
         self._gram_scratch = {}         # (world, batch) -> Gram scratch of lo_vae_gathered_early_norm
+        self._linear_bounds = None      # _linear_matrix_bounds
         self.dp_three_phase = True      # hand the encoder's last stage over before stages 3..1 run (False: one encoder range)
         flat = vae.flat_parameters()
         self.grads = torch.zeros_like(flat)
@@ -176,116 +193,118 @@ class VAEStepper:
     def _backward_and_exchange(self, eng, images: torch.Tensor, recon: torch.Tensor, st) -> None:
         """Native backward of the fused loss into ``self.grads`` (+ the data-parallel exchange, overlapped with it)."""
         vae = self.vae
-        flat = vae._flat
         self._last_engine = eng
-        bargs = (images.data_ptr(), flat.data_ptr(), eng.ws.data_ptr(), recon.data_ptr(), images.data_ptr(), 1, None, None, None,
+        bargs = (images.data_ptr(), vae._flat.data_ptr(), eng.ws.data_ptr(), recon.data_ptr(), images.data_ptr(), 1, None, None, None,
                  float(vae.loss_scale), self.grads.data_ptr(), st)
         if self.grad_sync is not None and hasattr(self.grad_sync, "begin"):
-            # data parallel: everything from fc_mu.weight to the end of the flat buffer (Linear layers, decoder and final
-            # convs: 90 % of the bytes) is final after phase 1 and is exchanged while the encoder backward runs; the
-            # encoder's last stage (94 % of the encoder bytes) is final after phase 3 and is exchanged during stages 3..1;
-            # only the small remainder (7.7 MB) is exchanged with nothing left to hide it
-            import ctypes as C
-            b, e, b4, e4 = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
-            kw = {}
-            _lib.check(_lib.lib.lo_vae_phase1_grad_range(eng.handle, C.byref(b), C.byref(e)), "lo_vae_phase1_grad_range")
-            _lib.check(_lib.lib.lo_vae_stage4_grad_range(eng.handle, C.byref(b4), C.byref(e4)), "lo_vae_stage4_grad_range")
-            assert e4.value == b.value and e.value == self.grads.numel()
-            # FlatGradSync runs the exchange on its own stream: the phases then hand their range over as an event for THAT stream
-            # (lo_vae_set_async_handover) instead of holding this one up until the side stream's weight gradients have finished
-            active = getattr(self.grad_sync, "world", 1) > 1 or getattr(self.grad_sync, "force", False)
-            hooks = getattr(self.grad_sync, "supports_then", False)
-            early = os.environ.get("LO_EARLY_NORM", "1") != "0" and hooks
-            mode = self._dp_linear_mode(eng, active, early)
-            dpf = mode != 0
-            if eng.fac_mode != mode:
-                _lib.check(_lib.lib.lo_vae_set_linear_factored(eng.handle, mode), "lo_vae_set_linear_factored")
-                eng.fac_mode = mode
-            _lib.check(_lib.lib.lo_vae_set_async_handover(eng.handle, 1 if hooks else 0), "lo_vae_set_async_handover")
-            def wait_range():
-                _lib.check(_lib.lib.lo_vae_wait_handover(eng.handle, _lib.stream_ptr()), "lo_vae_wait_handover")
-            kw = {"pre": wait_range} if hooks else {}
-            _lib.check(_lib.lib.lo_vae_backward_phase(eng.handle, 1, *bargs), "lo_vae_backward_phase(1)")
-            # ... and so is the sum of squares of that range for clip_grad_norm_ (of the AVERAGED gradients): taken right behind the
-            # exchange on the communication stream, beside the encoder backward; the tail of the step reads only the encoder range
-            if dpf:
-                # the Linear weight gradients of this range travel as factors: gather, form the averaged matrices locally, average the
-                # rest of the range (head biases; decoder.fc.bias, decoder and final convs), then the range's share of the norm
-                fo, fb = C.c_size_t(), C.c_size_t()
-                _lib.check(_lib.lib.lo_vae_factor_block(eng.handle, C.byref(fo), C.byref(fb)), "lo_vae_factor_block")
-                factors = eng.ws[fo.value:fo.value + fb.value]
-                L = vae.latent_dim
-                h_end, d_beg, d_end = b.value + 2 * L * 32768, None, None
-                lb, le = C.c_size_t(), C.c_size_t()
-                _lib.check(_lib.lib.lo_vae_linear_grad_range(eng.handle, C.byref(lb), C.byref(le)), "lo_vae_linear_grad_range")
-                d_end = le.value - 32768                 # decoder.fc.bias is the last tensor of the Linear range (32768 elements, aligned)
-                d_beg = d_end - 32768 * L
-                pieces = [self.grads[h_end:d_beg], self.grads[d_end:e.value]]
-
-                if mode == 3:
-                    # nothing is materialised: the callback only notes what the all-gather delivered, and the hook behind the exchange
-                    # of `pieces` takes the range's share of the norm -- the rest of the range from the averaged flat buffer, the two
-                    # matrices from the Gram matrices of the gathered factors -- and leaves the buffer to the optimizer step
-                    seen = []
-
-                    def keep_gathered(gathered, world):
-                        seen.append((gathered, world))
-
-                    def norm_of_gathered(eng=eng):
-                        gathered, world = seen[-1]
-                        key = (world, eng.batch)
-                        if key not in self._gram_scratch:
-                            self._gram_scratch[key] = _alloc_scratch(_lib.lib.lo_vae_gathered_scratch_bytes(eng.handle, world), gathered.device)
-                        _lib.check(_lib.lib.lo_vae_gathered_early_norm(eng.handle, gathered.data_ptr(), world, self._gram_scratch[key].data_ptr(),
-                                                                       self.grads.data_ptr(), self.scratch.data_ptr(), _lib.stream_ptr()),
-                                   "lo_vae_gathered_early_norm")
-
-                    if not self.grad_sync.begin_factored(pieces, factors, keep_gathered, then=norm_of_gathered, **kw):
-                        raise RuntimeError("dp_factored_adamw: the gradient exchange did not run its hooks (begin_factored returned False)")
-                    self._presummed_begin = b.value
-                else:
-                    def materialize(gathered, world, eng=eng):
-                        _lib.check(_lib.lib.lo_vae_materialize_gathered_linear_grads(eng.handle, gathered.data_ptr(), world, self.grads.data_ptr(),
-                                                                                     _lib.stream_ptr()), "lo_vae_materialize_gathered_linear_grads")
-
-                    def norm_of_range():
-                        _lib.check(_lib.lib.lo_gradnorm_early_range(self.grads.data_ptr(), b.value, e.value, self.scratch.data_ptr(), _lib.stream_ptr()),
-                                   "lo_gradnorm_early_range")
-
-                    if self.grad_sync.begin_factored(pieces, factors, materialize, then=norm_of_range if early else None, **kw) and early:
-                        self._presummed_begin = b.value
-            elif early:
-                if self.grad_sync.begin(self.grads[b.value:e.value], sumsq_scratch=self.scratch.data_ptr(), **kw):
-                    self._presummed_begin = b.value
-            else:
-                self.grad_sync.begin(self.grads[b.value:e.value], **kw)
-            if self.dp_three_phase:
-                _lib.check(_lib.lib.lo_vae_backward_phase(eng.handle, 3, *bargs), "lo_vae_backward_phase(3)")
-                self.grad_sync.begin(self.grads[b4.value:e4.value], **kw)
-                _lib.check(_lib.lib.lo_vae_backward_phase(eng.handle, 4, *bargs), "lo_vae_backward_phase(4)")
-                self.grad_sync.begin(self.grads[:b4.value])
-            else:                    # two-call form: the whole encoder range after phase 2
-                _lib.check(_lib.lib.lo_vae_backward_phase(eng.handle, 2, *bargs), "lo_vae_backward_phase(2)")
-                self.grad_sync.begin(self.grads[:b.value])
-            self.grad_sync.finish()
+            self._backward_data_parallel(eng, bargs)
         else:
-            # single process: the backward takes the sum of squares of everything from fc_mu.weight on as soon as it is final,
-            # beside the encoder backward; _clip_adamw then reads only the encoder range for the norm
-            fac = self.linear_factored and eng.batch <= 128
-            if eng.fac_mode != (1 if fac else 0):
-                _lib.check(_lib.lib.lo_vae_set_linear_factored(eng.handle, 1 if fac else 0), "lo_vae_set_linear_factored")
-                eng.fac_mode = 1 if fac else 0
-            early = self.grad_sync is None and (fac or os.environ.get("LO_EARLY_NORM", "1") != "0")       # LO_EARLY_NORM=0: A/B knob
-            _lib.check(_lib.lib.lo_vae_set_gradnorm_scratch(eng.handle, self.scratch.data_ptr() if early else None),
-                       "lo_vae_set_gradnorm_scratch")
-            _lib.check(_lib.lib.lo_vae_backward(eng.handle, *bargs), "lo_vae_backward")
-            if self.grad_sync is not None:
-                self.grad_sync(self.grads)
-            elif _lib.lib.lo_vae_gradnorm_presummed(eng.handle):
-                import ctypes as C
-                b, e = C.c_size_t(), C.c_size_t()
-                _lib.check(_lib.lib.lo_vae_phase1_grad_range(eng.handle, C.byref(b), C.byref(e)), "lo_vae_phase1_grad_range")
-                self._presummed_begin = b.value
+            self._backward_single(eng, bargs)
+
+    def _backward_single(self, eng, bargs) -> None:
+        """Single process (or a plain `grad_sync` callable): the backward takes the sum of squares of everything from fc_mu.weight on
+        as soon as it is final, beside the encoder backward; _clip_adamw then reads only the encoder range for the norm."""
+        fac = self.linear_factored and eng.batch <= 128
+        _set_linear_mode(eng, 1 if fac else 0)
+        early = self.grad_sync is None and (fac or os.environ.get("LO_EARLY_NORM", "1") != "0")       # LO_EARLY_NORM=0: A/B knob
+        _lib.check(_lib.lib.lo_vae_set_gradnorm_scratch(eng.handle, self.scratch.data_ptr() if early else None),
+                   "lo_vae_set_gradnorm_scratch")
+        _lib.check(_lib.lib.lo_vae_backward(eng.handle, *bargs), "lo_vae_backward")
+        if self.grad_sync is not None:
+            self.grad_sync(self.grads)
+        elif _lib.lib.lo_vae_gradnorm_presummed(eng.handle):
+            self._presummed_begin = _grad_range(eng, "lo_vae_phase1_grad_range")[0]
+
+    def _backward_data_parallel(self, eng, bargs) -> None:
+        """Everything from fc_mu.weight to the end of the flat buffer (Linear layers, decoder and final convs: 90 % of the bytes) is
+        final after phase 1 and is exchanged while the encoder backward runs; the encoder's last stage (94 % of the encoder bytes) is
+        final after phase 3 and is exchanged during stages 3..1; only the small remainder (7.7 MB) is exchanged with nothing left to
+        hide it."""
+        sync, g = self.grad_sync, self.grads
+        b, e = _grad_range(eng, "lo_vae_phase1_grad_range")
+        b4, e4 = _grad_range(eng, "lo_vae_stage4_grad_range")
+        assert e4 == b and e == g.numel()
+        # FlatGradSync runs the exchange on its own stream: the phases then hand their range over as an event for THAT stream
+        # (lo_vae_set_async_handover) instead of holding this one up until the side stream's weight gradients have finished
+        active = getattr(sync, "world", 1) > 1 or getattr(sync, "force", False)
+        hooks = getattr(sync, "supports_then", False)
+        early = os.environ.get("LO_EARLY_NORM", "1") != "0" and hooks
+        mode = self._dp_linear_mode(eng, active, early)
+        _set_linear_mode(eng, mode)
+        _lib.check(_lib.lib.lo_vae_set_async_handover(eng.handle, 1 if hooks else 0), "lo_vae_set_async_handover")
+
+        def wait_range():
+            _lib.check(_lib.lib.lo_vae_wait_handover(eng.handle, _lib.stream_ptr()), "lo_vae_wait_handover")
+        kw = {"pre": wait_range} if hooks else {}
+        _lib.check(_lib.lib.lo_vae_backward_phase(eng.handle, 1, *bargs), "lo_vae_backward_phase(1)")
+        if self._exchange_first_range(eng, mode, b, e, early, kw):
+            self._presummed_begin = b
+        if self.dp_three_phase:
+            _lib.check(_lib.lib.lo_vae_backward_phase(eng.handle, 3, *bargs), "lo_vae_backward_phase(3)")
+            sync.begin(g[b4:e4], **kw)
+            _lib.check(_lib.lib.lo_vae_backward_phase(eng.handle, 4, *bargs), "lo_vae_backward_phase(4)")
+            sync.begin(g[:b4])
+        else:                    # two-call form: the whole encoder range after phase 2
+            _lib.check(_lib.lib.lo_vae_backward_phase(eng.handle, 2, *bargs), "lo_vae_backward_phase(2)")
+            sync.begin(g[:b])
+        sync.finish()
+
+    def _exchange_first_range(self, eng, mode: int, b: int, e: int, early: bool, kw) -> bool:
+        """Hands the phase-1 range [b, e) to the exchange.  True: the range's share of the sum of squares for clip_grad_norm_ (of
+        the AVERAGED gradients) was taken right behind the exchange on the communication stream, beside the encoder backward, so the
+        tail of the step reads only the encoder range.  Three forms, by the mode of lo_vae_set_linear_factored:
+          0  the whole range is averaged like any other;
+          2  the two Linear weight gradients travel as factors: all-gather, write the averaged matrices out locally, average the rest
+             of the range (head biases; decoder.fc.bias, decoder and final convs), then the norm of the range;
+          3  the factors are kept: the callback only notes what the all-gather delivered, and the hook behind the exchange of the
+             rest takes the norm -- the rest from the averaged flat buffer, the two matrices from the Gram matrices of the gathered
+             factors -- and leaves the gathered buffer to the optimizer step."""
+        sync, g = self.grad_sync, self.grads
+        if mode == 0:
+            if early:
+                return sync.begin(g[b:e], sumsq_scratch=self.scratch.data_ptr(), **kw)
+            sync.begin(g[b:e], **kw)
+            return False
+        fo, fb = _grad_range(eng, "lo_vae_factor_block")
+        factors = eng.ws[fo:fo + fb]
+        h_end, d_beg, d_end = self._linear_matrix_bounds(eng)
+        pieces = [g[h_end:d_beg], g[d_end:e]]
+        if mode == 3:
+            seen = []
+            if not sync.begin_factored(pieces, factors, lambda gathered, world: seen.append((gathered, world)),
+                                       then=lambda: self._norm_of_gathered(eng, *seen[-1]), **kw):
+                raise RuntimeError("dp_factored_adamw: the gradient exchange did not run its hooks (begin_factored returned False)")
+            return True
+
+        def materialize(gathered, world):
+            _lib.check(_lib.lib.lo_vae_materialize_gathered_linear_grads(eng.handle, gathered.data_ptr(), world, g.data_ptr(), _lib.stream_ptr()),
+                       "lo_vae_materialize_gathered_linear_grads")
+
+        def norm_of_range():
+            _lib.check(_lib.lib.lo_gradnorm_early_range(g.data_ptr(), b, e, self.scratch.data_ptr(), _lib.stream_ptr()), "lo_gradnorm_early_range")
+
+        return sync.begin_factored(pieces, factors, materialize, then=norm_of_range if early else None, **kw) and early
+
+    def _norm_of_gathered(self, eng, gathered: torch.Tensor, world: int) -> None:
+        key = (world, eng.batch)
+        if key not in self._gram_scratch:
+            self._gram_scratch[key] = _alloc_scratch(_lib.lib.lo_vae_gathered_scratch_bytes(eng.handle, world), gathered.device)
+        _lib.check(_lib.lib.lo_vae_gathered_early_norm(eng.handle, gathered.data_ptr(), world, self._gram_scratch[key].data_ptr(),
+                                                       self.grads.data_ptr(), self.scratch.data_ptr(), _lib.stream_ptr()),
+                   "lo_vae_gathered_early_norm")
+
+    def _linear_matrix_bounds(self, eng):
+        """(end of fc_mu | fc_logvar.weight, begin of decoder.fc.weight, its end) in the flat buffer, from the module's layout table
+        by parameter name; checked once against the ranges the library reports."""
+        if self._linear_bounds is None:
+            at = {name: (o, n) for (name, _p), (o, n, _s) in zip(self.vae.named_parameters(), self.vae._layout)}
+            (mu, n_mu), (lv, n_lv), (fc, n_fc) = at["encoder.fc_mu.weight"], at["encoder.fc_logvar.weight"], at["decoder.fc.weight"]
+            lin_b, lin_e = _grad_range(eng, "lo_vae_linear_grad_range")
+            assert lv == mu + n_mu and mu == lin_b == _grad_range(eng, "lo_vae_phase1_grad_range")[0], "flat layout: head weights"
+            # decoder.fc.bias is the last tensor of the Linear range (32768 elements, aligned)
+            assert at["decoder.fc.bias"][0] == fc + n_fc == lin_e - 32768, "flat layout: decoder.fc"
+            self._linear_bounds = (lv + n_lv, fc, fc + n_fc)
+        return self._linear_bounds
 
     def _dp_linear_mode(self, eng, active: bool, early: bool) -> int:
         """Mode of lo_vae_set_linear_factored for a data-parallel step: 0 the Linear weight gradients are exchanged like the rest,
@@ -419,7 +438,6 @@ class HybridStepper(VAEStepper):
         self._t_ready = False
 
     def _teacher_setup(self, batch: int):
-        import ctypes as C
         t = self.teacher
         h, ws, _ = t._engine(batch)
         b, e = C.c_size_t(), C.c_size_t()

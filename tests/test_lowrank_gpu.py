@@ -76,8 +76,11 @@ def test_factored_gradients_match_the_oracle():
     assert abs(st.metrics()["grad_norm"] - o["grad_norm"]) <= 2e-3 * o["grad_norm"]
 
 
-@pytest.mark.parametrize("B,L,pipelined", [(4, 256, False), (64, 512, True)], ids=["b4_l256_serial", "b64_l512_pipelined"])
+@pytest.mark.parametrize("B,L,pipelined", [(4, 256, False), (64, 512, True), (96, 64, False), (128, 64, False)],
+                         ids=["b4_l256_serial", "b64_l512_pipelined", "b96_l64_serial", "b128_l64_serial"])
 def test_factored_optimizer_steps_equal_the_materialised_path(B, L, pipelined):
+    """Batches 4 / 64 / 96 / 128 = one to four MFMA K steps per tile (the four instantiations of the AdamW kernel) with a non-zero
+    learning rate; latent 64 is the smallest the plan accepts."""
     lr = 1e-4
     xs = [R.normalise_sprites(R.closed_form_sprites(B, salt=s)).cuda() for s in range(2)]
     res = {}
@@ -103,6 +106,35 @@ def test_factored_optimizer_steps_equal_the_materialised_path(B, L, pipelined):
     dv = (res[True][3] - res[False][3]).norm().item() / res[False][3].norm().item()
     assert dm <= 1e-4 and dv <= 1e-4, (dm, dv)
     assert (res[True][4] - res[False][4]).abs().max().item() <= 5e-3 and (res[True][5] - res[False][5]).abs().max().item() <= 5e-3
+
+
+def test_one_materialiser_behind_both_entry_points():
+    """lo_vae_materialize_linear_grads in mode 1 is lo_vae_materialize_gathered_linear_grads on ONE block, the workspace's own factor
+    block: the same bits in the two Linear ranges, and nothing else of the buffer is written.  Batch 33: zero padding of the factors'
+    batch axis, two MFMA K steps."""
+    import ctypes as C
+    from lunaris_orion_amd import _lib
+    B, L = 33, 64
+    m, st = _stepper(L, True, lr=0.0, weight_decay=0.0, max_grad_norm=1e9)
+    st.step(R.normalise_sprites(R.closed_form_sprites(B)).cuda(), 0, R.closed_form_eps(B, L, salt=0).cuda())
+    eng = m._engine(B)
+    assert _lib.lib.lo_vae_linear_factored(eng.handle) == 1
+    off, nbytes = C.c_size_t(), C.c_size_t()
+    _lib.check(_lib.lib.lo_vae_factor_block(eng.handle, C.byref(off), C.byref(nbytes)), "lo_vae_factor_block")
+    own, one_block = torch.full_like(st.grads, float("nan")), torch.full_like(st.grads, float("nan"))
+    _lib.check(_lib.lib.lo_vae_materialize_linear_grads(eng.handle, eng.ws.data_ptr(), own.data_ptr(), _lib.stream_ptr()),
+               "lo_vae_materialize_linear_grads")
+    _lib.check(_lib.lib.lo_vae_materialize_gathered_linear_grads(eng.handle, eng.ws.data_ptr() + off.value, 1, one_block.data_ptr(),
+                                                                 _lib.stream_ptr()), "lo_vae_materialize_gathered_linear_grads")
+    torch.cuda.synchronize()
+    written = torch.zeros(st.grads.numel(), dtype=torch.bool, device="cuda")
+    for (o, n, _), (k, _p) in zip(m._layout, m.named_parameters()):
+        if k in _lin_names(None):
+            assert torch.isfinite(own[o:o + n]).all() and own[o:o + n].abs().max().item() > 0, k
+            assert torch.equal(own[o:o + n], one_block[o:o + n]), k
+            written[o:o + n] = True
+    assert written.sum().item() == 3 * L * 32768
+    assert torch.isnan(one_block[~written]).all() and torch.isnan(own[~written]).all()
 
 
 def test_factored_update_is_skipped_on_a_non_finite_norm():
