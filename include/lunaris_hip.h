@@ -445,6 +445,27 @@ int lo_teacher_full_backward_dx(LoTeacher* h, const float* images_nchw, float* f
                                 const float* pooled_e, const float* raw_q, const float* expert_weights, const float* d_quality,
                                 const float* d_weights, float dropout_p, uint64_t drop_seed, float gscale, float* rows, float* flat_grads,
                                 float* dx, void* stream);
+/* LunarMoETeacher.forward in eval mode (lunar_evaluator.py:408-462 under module.eval(): every BatchNorm2d with its running statistics,
+ * lunar_evaluator.py:61-89, 240-257; every Dropout / Dropout2d the identity), plain form, every tensor the backward reads left in bws
+ * (lo_teacher_full_backward_bytes): the forward of the eval-mode teacher used as a differentiable reward.  Not one byte of flat_state
+ * changes; the pooled features and pre-weighting logits are where lo_teacher_heads_saved says; lo_teacher_last_path reports 1.  The
+ * outputs differ from lo_teacher_forward(training = 0) (folded form at feature_dim 128) at the fp16 rounding level. */
+int lo_teacher_forward_keep_eval(LoTeacher* h, const float* images_nchw, const float* flat_state, void* ws, void* bws,
+                                 float* quality_scores, float* expert_weights, float* style_embedding,
+                                 float* prompt_embedding, float* semantic_score, void* stream);
+/* Its backward for upstream gradients d_quality [B][4] / d_weights [B][E] (either may be NULL): the chain of
+ * lo_teacher_full_backward_dx with frozen BatchNorm -- y = (r - running_mean) rstd gamma + beta has dr = gamma rstd ls g, no batch
+ * statistic term couples the samples -- and no dropout.  Parameter gradients keep their form (dbeta = ls sum g, dgamma = ls sum g xhat,
+ * dls = gamma S2 + beta S1); running statistics get none.  flat_grads NULL: parameter gradients are not computed at all (no
+ * weight-gradient GEMM, no column sums, no BatchNorm reduce; one streaming pass per BatchNorm) -- the frozen-reward case; dx has the
+ * same bits with and without flat_grads.  dx NULL: frozen-BatchNorm fine-tuning.  After lo_teacher_forward_keep_eval on the same bws
+ * nothing is recomputed; after anything else (a train-mode kept forward included) the trunk is recomputed in eval mode from
+ * images_nchw.  gscale as for lo_teacher_full_backward (eval-mode gradients are smaller than train-mode ones). */
+int lo_teacher_eval_backward(LoTeacher* h, const float* images_nchw, const float* flat_state, void* ws, void* bws,
+                             const float* pooled_f, const float* pooled_e, const float* raw_q, const float* expert_weights,
+                             const float* d_quality, const float* d_weights, float gscale, float* rows,
+                             float* flat_grads /* NULL: parameter gradients not wanted */,
+                             float* dx /* fp32 NCHW [B,3,128,128]; NULL: not wanted */, void* stream);
 /* clip_grad_norm_(teacher.parameters()) + AdamW (train_hybrid.py:914, 922) with every teacher parameter live: the norm over the whole
  * flat gradient of lo_teacher_full_backward, the update over exactly the tensors that have a .grad in the reference (not the
  * BatchNorm buffers, not the style / prompt / semantic heads, whose .grad is None there).  m, v: lo_teacher_flat_elems floats each,

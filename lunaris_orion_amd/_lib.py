@@ -76,6 +76,8 @@ SIGNATURES = {
     "lo_teacher_full_backward_ex": (i32, [vp, f32p, f32p, vp, vp, f32p, f32p, f32p, f32p, f32p, f32p, flt, u64, flt, f32p, f32p, vp]),
     "lo_teacher_full_backward_dx": (i32, [vp, f32p, f32p, vp, vp, f32p, f32p, f32p, f32p, f32p, f32p, flt, u64, flt, f32p, f32p, f32p, vp]),
     "lo_teacher_forward_keep": (i32, [vp, f32p, f32p, vp, vp, flt, u64, f32p, f32p, f32p, f32p, f32p, vp]),
+    "lo_teacher_forward_keep_eval": (i32, [vp, f32p, f32p, vp, vp, f32p, f32p, f32p, f32p, f32p, vp]),
+    "lo_teacher_eval_backward": (i32, [vp, f32p, f32p, vp, vp, f32p, f32p, f32p, f32p, f32p, f32p, flt, f32p, f32p, f32p, vp]),
     "lo_teacher_full_backward": (i32, [vp, f32p, f32p, vp, vp, f32p, flt, flt, f32p, f32p, vp]),
     "lo_teacher_clip_adamw_full": (i32, [vp, f32p, f32p, f32p, f32p, flt, flt, flt, flt, flt, flt, i32, f32p, vp]),
     "lo_teacher_full_param_count": (i32, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),

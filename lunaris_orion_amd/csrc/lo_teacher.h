@@ -113,7 +113,10 @@ struct LoTeacher {
   float last_p = 0.f; uint64_t last_seed = 0; int last_path = -1;
   // full-backward mode (lo_teacher_bwd.hip): lo_teacher_forward_keep is a forward of its own (plain form, every tensor of every block
   // kept inside the backward's scratch `kept_bws`); lo_teacher_full_backward on the same scratch then recomputes nothing
-  const void* kept_bws = nullptr; bool kept = false;
+  // kept_eval: which mode left the tensors (lo_teacher_forward_keep_eval: running statistics, no dropout); a backward of the other
+  // mode recomputes instead of consuming them
+  const void* kept_bws = nullptr; bool kept = false, kept_eval = false;
+  bool bwd_shared = false;    // LO_T_BWD_SHARED=1: the full backward's shared-tensor-set plan (one recomputation per block) at any size
 };
 
 // ---- lo_teacher_kernels.hip ---------------------------------------------------------------------------------------------------------
@@ -208,10 +211,14 @@ struct TbPlan {
 struct TbCtx {
   LoTeacher* h; float* P; void* ws; void* bws; float* G; hipStream_t st; TbPlan pl;
   LoDropCfg d; float gscale, inv_g;
+  int frozen = 0;                         // 1: eval mode -- every BatchNorm with its running statistics, differentiated as constants
   LoGeom d1a, d1b, dq, dpc, dsc;          // data gradients of a block's conv 128->F, conv F->F, qkv, proj on the compact rows, shortcut
 };
 // BatchNorm backward of one layer: upstream din -> gradient wrt the conv output (out), parameter gradients into G (dbias: the bias
-// gradient of the conv in front).  A view = C channels of a [pix][pitch] tensor from channel `off`
+// gradient of the conv in front).  A view = C channels of a [pix][pitch] tensor from channel `off`.  frozen (default: the call's mode,
+// TbCtx::frozen): statistics are constants, out = gamma rstd ls g slope.  Without a gradient buffer (TbCtx::G null, frozen only) the
+// layer is ONE streaming pass; tail_y set, that pass is also the ExpertBlock tail in front of it: din.p = dy (null: the broadcast of
+// tail_dpool) and tail_ds receives dS = dy slope(y), the value the BatchNorm then reads
 struct TbView { const f16* p; int pitch, off = 0; };
 struct TbViewOut { f16* p; int pitch, off = 0; };
 enum TbAct { TB_ACT_NONE = 0, TB_ACT_LRELU = 1 };                          // TbBnArgs::act: the stored tensor is LeakyReLU(conv)
@@ -220,6 +227,7 @@ struct TbDrop { int mode = TB_DROP_NONE; uint32_t site = 0; int idx_pitch = 0, i
 struct TbBnBwd {
   TbView din, raw; const float* mr; const TBnOff& bn; const float* ls = nullptr; float* dls = nullptr;
   TbViewOut out; int C; int act = TB_ACT_NONE; TbDrop drop = {}; float* dbias = nullptr;
+  const f16* tail_y = nullptr; const float* tail_dpool = nullptr; f16* tail_ds = nullptr;
 };
 int tb_bn_backward(TbCtx& c, const TbBnBwd& op);
 // backward of ExpertBlock (e, l): scratch holds its recomputation; y = the block output, dy / dpool = its gradient.

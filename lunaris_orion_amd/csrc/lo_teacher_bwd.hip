@@ -212,7 +212,8 @@ static void tb_plan(const LoTeacher* h, TbPlan* p) {
   const size_t px = (size_t)h->B * T_HW, F = (size_t)h->F;
   // every block's tensors kept (nothing is ever recomputed) while that fits comfortably: 8 F-channel tensors per block, 12 blocks --
   // 26 GB at batch 64 / feature_dim 128, 103 GB at 512; above 160 GB one shared set and a recomputation per block
-  p->saved = (double)px * (double)F * 2.0 * 8.0 * 3.0 * (double)h->E <= 160.0e9;
+  // (LO_T_BWD_SHARED=1 takes the shared set at any size: how the tests reach that plan)
+  p->saved = !h->bwd_shared && (double)px * (double)F * 2.0 * 8.0 * 3.0 * (double)h->E <= 160.0e9;
   p->o_raw32 = take(px * 32 * 2);
   for (int b = 0; b < 3; ++b) p->o_dwb[b] = take(px * 32 * 2);
   p->o_cat = take(px * 192 * 2); p->o_catd = take(px * 192 * 2);
@@ -289,46 +290,51 @@ static int tb_block_forward(TbCtx& c, int e, int l, const f16* xin, f16* xout, i
   return t_block_plain(c.h, c.P, c.ws, e, l, c.d, t, xin, xout, train, pool_partial, nm, c.st);
 }
 // the trunk in plain form: feature extractor and the 12 blocks, every block's output (and, with a saved plan, every tensor its backward
-// reads) left inside bws.  train 1: the step's forward (pooled features for the heads, running statistics move); 2: the backward's own pass
-static int tb_trunk_forward(TbCtx& c, const float* x, int train) {
+// reads) left inside bws.  train 1: the step's forward (pooled features for the heads, running statistics move); 2: the backward's own pass;
+// 0: eval mode (running statistics, read only; the (mean, rstd) tables hold them).  pool: the pooled features for the heads as well
+static int tb_trunk_forward(TbCtx& c, const float* x, int train, bool pool) {
   LoTeacher* h = c.h; void* ws = c.ws; void* bws = c.bws;
   const int B = h->B, F = h->F;
-  float* poolp = train == 1 ? TW(float, h->o_poolp) : nullptr;
+  float* poolp = pool ? TW(float, h->o_poolp) : nullptr;
   // the feature extractor keeps every tensor its backward reads: the raw concatenation next to catd = Dropout(BN(cat))
   const TFeDst fd{TB(f16, c.pl.o_raw32), {TB(f16, c.pl.o_dwb[0]), TB(f16, c.pl.o_dwb[1]), TB(f16, c.pl.o_dwb[2])}, TB(f16, c.pl.o_cat), TB(f16, c.pl.o_catd),
                   TB(f16, c.pl.o_rawF), TB(f16, c.pl.o_feat), nullptr, TB(float, c.pl.o_ssx[3]), TB(float, c.pl.o_mr[3]),
                   {TB(float, c.pl.o_mr[4]), TB(float, c.pl.o_mr[5]), TB(float, c.pl.o_mr[6])}, TB(float, c.pl.o_mr[7]), poolp};
   static const TFeNames fe_names{nullptr, nullptr, nullptr, nullptr};
   LO_TRYT(t_fe_forward(h, x, c.P, ws, train, c.d, false, fd, fe_names, c.st));
-  if (train == 1) LO_TRYT(t_pool(h, TW(float, h->o_pool_f), 128, ws, c.st));
+  if (pool) LO_TRYT(t_pool(h, TW(float, h->o_pool_f), 128, ws, c.st));
   const f16* feat = TB(f16, c.pl.o_feat);
   for (int e = 0; e < h->E; ++e) {
     for (int l = 0; l < 3; ++l)
       LO_TRYT(tb_block_forward(c, e, l, l ? TB(f16, c.pl.o_xs[e][l - 1]) : feat, TB(f16, c.pl.o_xs[e][l]), train, l == 2 ? poolp : nullptr));
-    if (train == 1) LO_TRYT(t_pool(h, TW(float, h->o_pool_e) + (size_t)e * B * F, F, ws, c.st));
+    if (pool) LO_TRYT(t_pool(h, TW(float, h->o_pool_e) + (size_t)e * B * F, F, ws, c.st));
   }
   return LO_OK;
 }
 
-// feature extractor backward, from dfeat (gradient wrt the features, scaled); dx (NULL = not wanted): the gradient wrt the images
+// feature extractor backward, from dfeat (gradient wrt the features, scaled); dx (NULL = not wanted): the gradient wrt the images.
+// Without a gradient buffer (c.G null) the weight-gradient kernels and their column sums are skipped
 static int tb_fe_backward(TbCtx& c, const float* x, float* dx) {
   LoTeacher* h = c.h; float* P = c.P; float* G = c.G; void* bws = c.bws; hipStream_t st = c.st;
+  const bool wg = G != nullptr;
   const TFeOff& fe = h->fe;
   const int B = h->B;
   const size_t px = (size_t)B * T_HW;
   f16* dcf = TB(f16, c.pl.o_dA);                   // gradient wrt the fusion conv's output [pix][128]
   LO_TRYT(tb_bn_backward(c, {.din = {TB(f16, c.pl.o_dfeat), 128}, .raw = {TB(f16, c.pl.o_rawF), 128}, .mr = TB(float, c.pl.o_mr[7]),
-                             .bn = fe.bn_fus, .out = {dcf, 128}, .C = 128, .act = TB_ACT_LRELU, .dbias = TG(fe.fus_b)}));
+                             .bn = fe.bn_fus, .out = {dcf, 128}, .C = 128, .act = TB_ACT_LRELU, .dbias = wg ? TG(fe.fus_b) : nullptr}));
   // fusion conv 192 -> 128 as three 64-channel slices (the GEMM kernels want power-of-two channel counts)
   LoGeom d64;
   LO_TRYT(lo_make_geom(&d64, LO_LINEAR, B, 128, 128, 128, 64));
   for (int b = 0; b < 3; ++b) {
-    const size_t nchunk = px * 8;
-    hipLaunchKernelGGL(lo_tb_slice64_kernel, dim3((unsigned)((nchunk + 255) / 256)), dim3(256), 0, st, TB(f16, c.pl.o_catd), 64 * b, TB(f16, c.pl.o_cat64), nchunk);
-    LO_LAUNCH_CHECK("tb_slice64");
-    LO_TAGGED("tb fusion wgrad", lo_wgrad_run(h->gfw, TB(f16, c.pl.o_cat64), dcf, TB(float, c.pl.o_wslab), TB(float, c.pl.o_tmpw), c.inv_g, st));
-    hipLaunchKernelGGL(lo_tb_scatter_cols_kernel, dim3(32), dim3(256), 0, st, TB(float, c.pl.o_tmpw), TG(fe.fus_w), 64 * b);
-    LO_LAUNCH_CHECK("tb_scatter_cols");
+    if (wg) {
+      const size_t nchunk = px * 8;
+      hipLaunchKernelGGL(lo_tb_slice64_kernel, dim3((unsigned)((nchunk + 255) / 256)), dim3(256), 0, st, TB(f16, c.pl.o_catd), 64 * b, TB(f16, c.pl.o_cat64), nchunk);
+      LO_LAUNCH_CHECK("tb_slice64");
+      LO_TAGGED("tb fusion wgrad", lo_wgrad_run(h->gfw, TB(f16, c.pl.o_cat64), dcf, TB(float, c.pl.o_wslab), TB(float, c.pl.o_tmpw), c.inv_g, st));
+      hipLaunchKernelGGL(lo_tb_scatter_cols_kernel, dim3(32), dim3(256), 0, st, TB(float, c.pl.o_tmpw), TG(fe.fus_w), 64 * b);
+      LO_LAUNCH_CHECK("tb_scatter_cols");
+    }
     // data gradient of the slice: dcat[pix][64 b + ci] = sum_co dcf[pix][co] W[co][64 b + ci]  (operand [ci][co], written at its channel offset)
     hipLaunchKernelGGL(lo_tb_wt_kernel, dim3((64 * 128 + 255) / 256), dim3(256), 0, st, TP(fe.fus_w), TB(f16, c.pl.o_wt), 64, 128, 192, 64 * b);
     LO_LAUNCH_CHECK("tb_wt");
@@ -345,32 +351,38 @@ static int tb_fe_backward(TbCtx& c, const float* x, float* dx) {
     // Dropout (element index pix * 192 + 64 b + c), BatchNorm of the branch, LeakyReLU
     LO_TRYT(tb_bn_backward(c, {.din = {TB(f16, c.pl.o_dcat), 192, 64 * b}, .raw = {TB(f16, c.pl.o_cat), 192, 64 * b},
                                .mr = TB(float, c.pl.o_mr[4 + b]), .bn = br.bn, .out = {dpw, 64}, .C = 64, .act = TB_ACT_LRELU,
-                               .drop = {TB_DROP_ELEM, LO_DS_FE, 192, 64 * b}, .dbias = TG(br.pw_b)}));
-    hipLaunchKernelGGL(lo_tb_pw_wgrad_kernel, dim3((unsigned)(px / 1024)), dim3(256), 0, st, dpw, 64, 0, TB(f16, c.pl.o_dwb[b]), TB(float, c.pl.o_part));
-    LO_LAUNCH_CHECK("tb_pw_wgrad");
-    LO_TRYT(lo_colsum(TB(float, c.pl.o_part), TG(br.pw_w), (int)(px / 1024), 2048, 2048, c.inv_g, st));
+                               .drop = {TB_DROP_ELEM, LO_DS_FE, 192, 64 * b}, .dbias = wg ? TG(br.pw_b) : nullptr}));
+    if (wg) {
+      hipLaunchKernelGGL(lo_tb_pw_wgrad_kernel, dim3((unsigned)(px / 1024)), dim3(256), 0, st, dpw, 64, 0, TB(f16, c.pl.o_dwb[b]), TB(float, c.pl.o_part));
+      LO_LAUNCH_CHECK("tb_pw_wgrad");
+      LO_TRYT(lo_colsum(TB(float, c.pl.o_part), TG(br.pw_w), (int)(px / 1024), 2048, 2048, c.inv_g, st));
+    }
     hipLaunchKernelGGL(lo_tb_pw_dgrad_kernel, dim3((unsigned)((px * 4 + 255) / 256)), dim3(256), 0, st, dpw, 64, 0, TP(br.pw_w), ddw, px);
     LO_LAUNCH_CHECK("tb_pw_dgrad");
     if (K == 5) {
-      hipLaunchKernelGGL((lo_tb_dw_wgrad_kernel<5>), dim3(128, B), dim3(256), 0, st, ddw, TB(f16, c.pl.o_raw32), ss32, TB(float, c.pl.o_part), TB(float, c.pl.o_bpart));
+      if (wg) hipLaunchKernelGGL((lo_tb_dw_wgrad_kernel<5>), dim3(128, B), dim3(256), 0, st, ddw, TB(f16, c.pl.o_raw32), ss32, TB(float, c.pl.o_part), TB(float, c.pl.o_bpart));
       LO_LAUNCH_CHECK("tb_dw_wgrad");
       hipLaunchKernelGGL((lo_tb_dw_dgrad_kernel<5>), dim3(128, B), dim3(256), 0, st, ddw, TP(br.dw_w), b ? dn0 : (const f16*)nullptr, dn0);
     } else {
-      hipLaunchKernelGGL((lo_tb_dw_wgrad_kernel<3>), dim3(128, B), dim3(256), 0, st, ddw, TB(f16, c.pl.o_raw32), ss32, TB(float, c.pl.o_part), TB(float, c.pl.o_bpart));
+      if (wg) hipLaunchKernelGGL((lo_tb_dw_wgrad_kernel<3>), dim3(128, B), dim3(256), 0, st, ddw, TB(f16, c.pl.o_raw32), ss32, TB(float, c.pl.o_part), TB(float, c.pl.o_bpart));
       LO_LAUNCH_CHECK("tb_dw_wgrad");
       hipLaunchKernelGGL((lo_tb_dw_dgrad_kernel<3>), dim3(128, B), dim3(256), 0, st, ddw, TP(br.dw_w), b ? dn0 : (const f16*)nullptr, dn0);
     }
     LO_LAUNCH_CHECK("tb_dw_dgrad");
-    LO_TRYT(lo_colsum(TB(float, c.pl.o_part), TG(br.dw_w), B * 128, 32 * K * K, 32 * K * K, c.inv_g, st));
-    LO_TRYT(lo_colsum(TB(float, c.pl.o_bpart), TG(br.dw_b), B * 128, 32, 32, c.inv_g, st));
+    if (wg) {
+      LO_TRYT(lo_colsum(TB(float, c.pl.o_part), TG(br.dw_w), B * 128, 32 * K * K, 32 * K * K, c.inv_g, st));
+      LO_TRYT(lo_colsum(TB(float, c.pl.o_bpart), TG(br.dw_b), B * 128, 32, 32, c.inv_g, st));
+    }
   }
   // BatchNorm + LeakyReLU of conv1, then its weight gradient and -- for a caller whose images require grad -- its data gradient
   LO_TRYT(tb_bn_backward(c, {.din = {dn0, 32}, .raw = {TB(f16, c.pl.o_raw32), 32}, .mr = TB(float, c.pl.o_mr[3]), .bn = fe.bn1,
                              .out = {ddw, 32}, .C = 32, .act = TB_ACT_LRELU}));
-  hipLaunchKernelGGL(lo_tb_conv1_wgrad_kernel, dim3(128, B), dim3(256), 0, st, x, ddw, TB(float, c.pl.o_part), TB(float, c.pl.o_bpart));
-  LO_LAUNCH_CHECK("tb_conv1_wgrad");
-  LO_TRYT(lo_colsum(TB(float, c.pl.o_part), TG(fe.conv1_w), B * 128, 864, 864, c.inv_g, st));
-  LO_TRYT(lo_colsum(TB(float, c.pl.o_bpart), TG(fe.conv1_b), B * 128, 32, 32, c.inv_g, st));
+  if (wg) {
+    hipLaunchKernelGGL(lo_tb_conv1_wgrad_kernel, dim3(128, B), dim3(256), 0, st, x, ddw, TB(float, c.pl.o_part), TB(float, c.pl.o_bpart));
+    LO_LAUNCH_CHECK("tb_conv1_wgrad");
+    LO_TRYT(lo_colsum(TB(float, c.pl.o_part), TG(fe.conv1_w), B * 128, 864, 864, c.inv_g, st));
+    LO_TRYT(lo_colsum(TB(float, c.pl.o_bpart), TG(fe.conv1_b), B * 128, 32, 32, c.inv_g, st));
+  }
   if (dx) LO_TRYT(lo_image_dgrad(ddw, 32, 1, TP(fe.conv1_w), B, c.inv_g, dx, st));
   return LO_OK;
 }
@@ -388,9 +400,25 @@ extern "C" int lo_teacher_forward_keep(LoTeacher* h, const float* x, float* P, v
   h->kept = false; h->kept_bws = nullptr;
   h->last_p = c.d.on ? dropout_p : 0.f; h->last_seed = drop_seed; h->last_path = c.d.on ? 2 : 1;
   LO_TRYT(tb_zero_attc(c));
-  LO_TRYT(tb_trunk_forward(c, x, 1));
+  LO_TRYT(tb_trunk_forward(c, x, 1, true));
   LO_TRYT(t_run_heads(h, P, ws, quality, weights, style, prompt, semantic, c.d, c.st));
-  h->kept = true; h->kept_bws = bws;
+  h->kept = true; h->kept_eval = false; h->kept_bws = bws;
+  return LO_OK;
+}
+// The same in eval mode (lunar_evaluator.py:408-462 under module.eval()): BatchNorm with the running statistics, no dropout, nothing of
+// the state written (training = 0 of the plain-form code; P is const for the caller); the (mean, rstd) tables hold (running_mean,
+// 1 / sqrt(running_var + eps)) for lo_teacher_eval_backward
+extern "C" int lo_teacher_forward_keep_eval(LoTeacher* h, const float* x, const float* P, void* ws, void* bws, float* quality, float* weights,
+                                            float* style, float* prompt, float* semantic, void* stream) {
+  LO_REQUIRE(h && x && P && ws && bws && quality && weights && style && prompt && semantic, "lo_teacher_forward_keep_eval: null argument");
+  TbCtx c;
+  LO_TRYT(tb_ctx_init(c, h, const_cast<float*>(P), ws, bws, nullptr, 0.f, 0, 1.0f, stream));
+  h->kept = false; h->kept_bws = nullptr;
+  h->last_p = 0.f; h->last_seed = 0; h->last_path = 1;
+  LO_TRYT(tb_zero_attc(c));
+  LO_TRYT(tb_trunk_forward(c, x, 0, true));
+  LO_TRYT(t_run_heads(h, c.P, ws, quality, weights, style, prompt, semantic, c.d, c.st));
+  h->kept = true; h->kept_eval = true; h->kept_bws = bws;
   return LO_OK;
 }
 
@@ -399,28 +427,32 @@ extern "C" int lo_teacher_forward_keep(LoTeacher* h, const float* x, float* P, v
 // which the fp16 activation gradients are multiplied (parameter gradients come out unscaled).  rows: [B][head range] scratch of
 // lo_teacher_heads_backward.  grads: the teacher's flat gradient buffer (state-table layout); every parameter on the loss path is
 // written, everything else is zeroed.
+// frozen (lo_teacher_eval_backward): the eval-mode function -- running statistics as constants, no dropout; grads may then be null (no
+// parameter gradient is computed: no weight-gradient GEMM, no column sum, no BatchNorm reduce) and dx alone is produced.
 static int tb_full_backward_impl(LoTeacher* h, const float* x, float* P, void* ws, void* bws, const float* pooled_f, const float* pooled_e,
                                  const float* raw_q, const float* expert_weights, const float* dq_up, const float* dw_up, float coef,
-                                 float drop_p, uint64_t drop_seed, float gscale, float* rows, float* grads, float* dx, void* stream) {
-  LO_REQUIRE(h && x && P && ws && bws && expert_weights && rows && grads, "lo_teacher_full_backward: null argument");
+                                 float drop_p, uint64_t drop_seed, float gscale, float* rows, float* grads, float* dx, void* stream, int frozen = 0) {
+  LO_REQUIRE(h && x && P && ws && bws && expert_weights && rows && (grads || (frozen && dx)), "lo_teacher_full_backward: null argument");
   LO_REQUIRE(gscale > 0.f, "lo_teacher_full_backward: gscale must be positive");
   LO_REQUIRE(h->last_path >= 0, "lo_teacher_full_backward: no forward has run on this engine");
   TbCtx c;
   LO_TRYT(tb_ctx_init(c, h, P, ws, bws, grads, drop_p, drop_seed, gscale, stream));
+  c.frozen = frozen;
   hipStream_t st = c.st;
   float* G = grads;
   const int B = h->B, F = h->F, E = h->E;
   const size_t px = (size_t)B * T_HW;
-  LO_HIP(hipMemsetAsync(G, 0, h->flat_elems * sizeof(float), st));
+  if (G) LO_HIP(hipMemsetAsync(G, 0, h->flat_elems * sizeof(float), st));
   // heads: their own parameter gradients + d loss / d pooled features
   LO_TRYT(t_heads_backward(h, P, pooled_f, pooled_e, raw_q, expert_weights, dq_up, dw_up, coef, c.d, rows, grads, st,
                            TB(float, c.pl.o_dpool_f), TB(float, c.pl.o_dpool_e)));
   // pass 1: the trunk again in plain form -- unless the forward of this step was lo_teacher_forward_keep on this bws
-  const bool kept = h->kept && h->kept_bws == bws && h->last_seed == drop_seed && h->last_p == drop_p;
+  // (kept by the forward of the same mode: eval tensors are not train tensors)
+  const bool kept = h->kept && h->kept_eval == (frozen != 0) && h->kept_bws == bws && h->last_seed == drop_seed && h->last_p == drop_p;
   h->kept = false; h->kept_bws = nullptr;
   if (!kept) {
     LO_TRYT(tb_zero_attc(c));
-    LO_TRYT(tb_trunk_forward(c, x, 2));
+    LO_TRYT(tb_trunk_forward(c, x, frozen ? 0 : 2, false));
   }
   const bool recompute = !c.pl.saved;          // one shared tensor set: every block is recomputed in front of its backward
   const f16* feat = TB(f16, c.pl.o_feat);
@@ -429,7 +461,7 @@ static int tb_full_backward_impl(LoTeacher* h, const float* x, float* P, void* w
   for (int e = 0; e < E; ++e) {
     for (int l = 2; l >= 0; --l) {
       const f16* xin = l ? TB(f16, c.pl.o_xs[e][l - 1]) : feat;
-      if (recompute) LO_TRYT(tb_block_forward(c, e, l, xin, nullptr, 2, nullptr));
+      if (recompute) LO_TRYT(tb_block_forward(c, e, l, xin, nullptr, frozen ? 0 : 2, nullptr));      // in the call's mode: frozen = running statistics
       f16* dx = l ? TB(f16, c.pl.o_dC) : (e == 0 ? TB(f16, c.pl.o_dfeat) : TB(f16, c.pl.o_dqkv));
       LO_TRYT(tb_block_backward(c, e, l, xin, TB(f16, c.pl.o_xs[e][l]), l == 2 ? (const f16*)nullptr : TB(f16, c.pl.o_dC),
                                 l == 2 ? TB(float, c.pl.o_dpool_e) + (size_t)e * B * F : (const float*)nullptr, dx));
@@ -513,4 +545,17 @@ extern "C" int lo_teacher_full_backward_ex(LoTeacher* h, const float* x, float* 
                                            float dropout_p, uint64_t drop_seed, float gscale, float* rows, float* grads, void* stream) {
   return lo_teacher_full_backward_dx(h, x, P, ws, bws, pooled_f, pooled_e, raw_q, expert_weights, d_quality, d_weights, dropout_p, drop_seed,
                                      gscale, rows, grads, nullptr, stream);
+}
+
+// Backward of lo_teacher_forward_keep_eval (the eval-mode teacher as a differentiable reward, or fine-tuned with frozen BatchNorm): the
+// chain of lo_teacher_full_backward_dx with every BatchNorm differentiated at its running statistics and no dropout.  flat_grads NULL:
+// parameter gradients not wanted -- one streaming pass per BatchNorm (the block tail fused into BatchNorm2's), no weight-gradient
+// GEMM, no column sum, no reduce / finalize, no memset of a flat buffer; dx has the same bits either way.  Does not find its own kept
+// tensors in bws: recomputes the trunk with training = 0 from the images.
+extern "C" int lo_teacher_eval_backward(LoTeacher* h, const float* x, const float* P, void* ws, void* bws, const float* pooled_f,
+                                        const float* pooled_e, const float* raw_q, const float* expert_weights, const float* d_quality,
+                                        const float* d_weights, float gscale, float* rows, float* grads, float* dx, void* stream) {
+  LO_REQUIRE(pooled_f && pooled_e && raw_q && (d_quality || d_weights) && (grads || dx), "lo_teacher_eval_backward: null argument");
+  return tb_full_backward_impl(h, x, const_cast<float*>(P), ws, bws, pooled_f, pooled_e, raw_q, expert_weights, d_quality, d_weights, 0.f, 0.f, 0,
+                               gscale, rows, grads, dx, stream, 1);
 }

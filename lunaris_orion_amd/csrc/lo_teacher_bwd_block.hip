@@ -13,6 +13,9 @@
 //   S1 = sum g, S2 = sum g * xhat                              (reduce kernel: partial rows, fixed order)
 //   dbeta = ls S1, dgamma = ls S2, dls = gamma S2 + beta S1    (finalize)
 //   dr = gamma rstd (dn - ls S1 / N - xhat ls S2 / N);  dconv = dr * (r > 0 ? 1 : 0.2)   (apply)
+// BatchNorm(eval) backward (`frozen`): mean / rstd are the running statistics, constants of the graph, and there is no dropout:
+//   dr = gamma rstd ls g;  dconv = dr * (r > 0 ? 1 : 0.2);  dbeta, dgamma, dls as above (reduce + finalize run for them only)
+// A call that wants no parameter gradient runs lo_tb_bn_frozen_kernel alone: one streaming pass per layer.
 // ---------------------------------------------------------------------------------------------
 struct TbBnArgs {
   const f16* din; int din_pitch, din_off;       // upstream gradient [pix][din_pitch] (+ channel offset)
@@ -25,7 +28,16 @@ struct TbBnArgs {
   f16* out; int out_pitch, out_off;             // apply: gradient wrt the conv output
   int C, act;                                   // act 1: the stored tensor is LeakyReLU(conv): multiply by its slope
   int dmode; LoDropSite ds; uint32_t thr; float inv_keep; int didx_pitch, didx_off;   // 0 none, 1 Dropout2d (idx b*C+c), 2 Dropout (idx pix*pitch+off+c)
+  // lo_tb_bn_frozen_kernel<true>: the ExpertBlock tail in front of the BatchNorm, y / tds dense [pix][C]; din null = tdpool broadcast
+  const f16* ty; const float* tdpool; float tbscale; f16* tds;
 };
+// the frozen data path of one element, shared by the apply kernel (with parameters) and the fused pass (without): products only, so
+// both give the same bits
+__device__ __forceinline__ float tb_frozen_d(float gr, float ls, float g, float rv, int act) {
+  float d = gr * (ls * g);
+  if (act && !(rv > 0.f)) d *= 0.2f;
+  return d;
+}
 __device__ __forceinline__ float tb_keep(const TbBnArgs& a, int n, size_t pix, int c) {
   if (a.dmode == 0 || a.thr == 0) return 1.f;
   const uint32_t idx = a.dmode == 1 ? (uint32_t)(n * a.C + c) : (uint32_t)(pix * (size_t)a.didx_pitch + a.didx_off + c);
@@ -99,6 +111,8 @@ __global__ __launch_bounds__(256) void lo_tb_bn_finalize_kernel(const float* __r
   dgamma[c] = (float)(l * s2 * (double)inv_gscale);
   if (dls) dls[c] = (float)(((double)gamma[c] * s2 + (double)beta[c] * s1) * (double)inv_gscale);
 }
+// FROZEN: no statistic terms, coef is not read (the instantiation without it is the train-mode kernel, untouched)
+template <bool FROZEN>
 __global__ __launch_bounds__(256) void lo_tb_bn_apply_kernel(TbBnArgs a) {
   __shared__ float s_red[256 * 8];
   const int tid = threadIdx.x, n = blockIdx.y, blk = blockIdx.x;
@@ -109,7 +123,7 @@ __global__ __launch_bounds__(256) void lo_tb_bn_apply_kernel(TbBnArgs a) {
   for (int j = 0; j < 8; ++j) {
     acc[j] = 0.f;
     mean[j] = a.mr[(c0 + j) * 2]; rstd[j] = a.mr[(c0 + j) * 2 + 1];
-    k1[j] = a.coef[(c0 + j) * 2]; k2[j] = a.coef[(c0 + j) * 2 + 1];
+    k1[j] = FROZEN ? 0.f : a.coef[(c0 + j) * 2]; k2[j] = FROZEN ? 0.f : a.coef[(c0 + j) * 2 + 1];
     gr[j] = a.gamma[c0 + j] * rstd[j];
     lsv[j] = a.ls ? a.ls[c0 + j] : 1.f;
     kc[j] = a.dmode == 1 ? tb_keep(a, n, 0, c0 + j) : 1.f;
@@ -124,8 +138,12 @@ __global__ __launch_bounds__(256) void lo_tb_bn_apply_kernel(TbBnArgs a) {
     for (int j = 0; j < 8; ++j) {
       const float k = a.dmode == 2 ? tb_keep(a, n, pix, c0 + j) : kc[j];
       const float rv = (float)v[j], xh = (rv - mean[j]) * rstd[j];
-      float d = gr[j] * (lsv[j] * ((float)g[j] * k) - k1[j] - xh * k2[j]);
-      if (a.act && !(rv > 0.f)) d *= 0.2f;
+      float d;
+      if (FROZEN) d = tb_frozen_d(gr[j], lsv[j], (float)g[j], rv, a.act);
+      else {
+        d = gr[j] * (lsv[j] * ((float)g[j] * k) - k1[j] - xh * k2[j]);
+        if (a.act && !(rv > 0.f)) d *= 0.2f;
+      }
       o[j] = (f16)d;
       acc[j] += (float)o[j];            // the bias gradient sums the values the weight-gradient GEMM will also see
     }
@@ -140,6 +158,59 @@ __global__ __launch_bounds__(256) void lo_tb_bn_apply_kernel(TbBnArgs a) {
     float tot = 0.f;
     for (int s = 0; s < nslot; ++s) tot += s_red[(s * CC + ccx) * 8 + j];
     a.bpartial[((size_t)n * 64 + blk) * C + c] = tot;
+  }
+}
+
+// Frozen BatchNorm backward without parameter gradients, one pass: out = f16(gamma rstd ls g slope(raw)).  TAIL: also the ExpertBlock
+// tail in front of BatchNorm2 -- g = dS = f16(dy slope(y)) (dy a tensor or the broadcast pooled gradient, as in lo_tb_tail_kernel) is
+// written for the identity branch and the BatchNorm reads the ROUNDED value, so the bits are those of the two-kernel form.
+// 3 reads + 2 writes per element (TAIL), 2 + 1 otherwise.  Thread = (8-channel chunk, row slot) like lo_tb_bn_apply_kernel; per-channel
+// constants in registers, U rows' 16-byte loads issued before the first use.
+template <bool TAIL>
+__global__ __launch_bounds__(256) void lo_tb_bn_frozen_kernel(TbBnArgs a) {
+  const int tid = threadIdx.x, n = blockIdx.y, blk = blockIdx.x;
+  const int C = a.C, CC = C >> 3;
+  const int cc = tid % CC, slot = tid / CC, nslot = 256 / CC, c0 = cc * 8;
+  float gr[8], lsv[8], dpb[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    gr[j] = a.gamma[c0 + j] * a.mr[(c0 + j) * 2 + 1];
+    lsv[j] = a.ls ? a.ls[c0 + j] : 1.f;
+    dpb[j] = (TAIL && !a.din) ? a.tdpool[(size_t)n * C + c0 + j] * a.tbscale : 0.f;
+  }
+  const size_t row0 = (size_t)n * T_HW + (size_t)blk * 256;
+  constexpr int U = 4;                     // 256 / nslot = C / 8 rows per thread: a multiple of 4 for every C >= 32
+  for (int r = slot; r < 256; r += U * nslot) {
+    f16x8 g[U], v[U], yv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const size_t pix = row0 + r + u * nslot;
+      v[u] = *reinterpret_cast<const f16x8*>(a.raw + pix * a.raw_pitch + a.raw_off + c0);
+      if (TAIL) {
+        yv[u] = *reinterpret_cast<const f16x8*>(a.ty + pix * C + c0);
+        if (a.din) g[u] = *reinterpret_cast<const f16x8*>(a.din + pix * C + c0);
+      } else {
+        g[u] = *reinterpret_cast<const f16x8*>(a.din + pix * a.din_pitch + a.din_off + c0);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const size_t pix = row0 + r + u * nslot;
+      f16x8 o;
+      if (TAIL) {
+        f16x8 s;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float sl = (float)yv[u][j] > 0.f ? 1.f : 0.2f;
+          s[j] = a.din ? (f16)((float)g[u][j] * sl) : (f16)(dpb[j] * sl);
+        }
+        *reinterpret_cast<f16x8*>(a.tds + pix * C + c0) = s;
+        g[u] = s;
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o[j] = (f16)tb_frozen_d(gr[j], lsv[j], (float)g[u][j], (float)v[u][j], a.act);
+      *reinterpret_cast<f16x8*>(a.out + pix * a.out_pitch + a.out_off + c0) = o;
+    }
   }
 }
 
@@ -346,7 +417,20 @@ int tb_bn_backward(TbCtx& c, const TbBnBwd& op) {
   a.out = op.out.p; a.out_pitch = op.out.pitch; a.out_off = op.out.off; a.C = C; a.act = op.act;
   a.dmode = c.d.on ? op.drop.mode : TB_DROP_NONE; a.ds = c.d.site(op.drop.site); a.thr = c.d.thr; a.inv_keep = c.d.inv_keep;
   a.didx_pitch = op.drop.idx_pitch; a.didx_off = op.drop.idx_off;
+  a.ty = op.tail_y; a.tdpool = op.tail_dpool; a.tbscale = c.gscale / (float)T_HW; a.tds = op.tail_ds;
   LO_REQUIRE(C % 8 == 0 && 256 % (C / 8) == 0, "tb_bn_backward: C = %d", C);
+  if (!G) {
+    // no parameter gradient wanted (frozen only): the layer is one streaming pass
+    const bool tail = op.tail_y != nullptr;
+    LO_REQUIRE(c.frozen && a.dmode == TB_DROP_NONE && C >= 32, "tb_bn_backward: the pass without parameter gradients is the frozen one (C = %d)", C);
+    LO_REQUIRE(!tail || (op.tail_ds && (op.din.p || op.tail_dpool) && op.out.pitch == C && op.raw.pitch == C), "tb_bn_backward: tail arguments");
+    LoProfScope _p(tail ? "lo_tb_bn_frozen<tail>" : "lo_tb_bn_frozen", 0, (tail ? 10.0 : 6.0) * h->B * T_HW * C, c.st);
+    if (tail) hipLaunchKernelGGL(lo_tb_bn_frozen_kernel<true>, dim3(64, h->B), dim3(256), 0, c.st, a);
+    else hipLaunchKernelGGL(lo_tb_bn_frozen_kernel<false>, dim3(64, h->B), dim3(256), 0, c.st, a);
+    LO_LAUNCH_CHECK("tb_bn_frozen");
+    return LO_OK;
+  }
+  LO_REQUIRE(!op.tail_y, "tb_bn_backward: the fused tail belongs to the pass without parameter gradients");
   {
     LoProfScope _p("lo_tb_bn_reduce", 0, 4.0 * h->B * T_HW * C, c.st);
     hipLaunchKernelGGL(lo_tb_bn_reduce_kernel, dim3(64, h->B), dim3(256), 0, c.st, a);
@@ -357,7 +441,8 @@ int tb_bn_backward(TbCtx& c, const TbBnBwd& op) {
   LO_LAUNCH_CHECK("tb_bn_finalize");
   {
     LoProfScope _p("lo_tb_bn_apply", 0, 6.0 * h->B * T_HW * C, c.st);
-    hipLaunchKernelGGL(lo_tb_bn_apply_kernel, dim3(64, h->B), dim3(256), 0, c.st, a);
+    if (c.frozen) hipLaunchKernelGGL(lo_tb_bn_apply_kernel<true>, dim3(64, h->B), dim3(256), 0, c.st, a);
+    else hipLaunchKernelGGL(lo_tb_bn_apply_kernel<false>, dim3(64, h->B), dim3(256), 0, c.st, a);
   }
   LO_LAUNCH_CHECK("tb_bn_apply");
   if (dbias) LO_TRYT(lo_colsum(TB(float, c.pl.o_part), dbias, h->B * 64, C, C, c.inv_g, c.st));      // bias gradient of the conv in front of the BatchNorm
@@ -409,35 +494,49 @@ int tb_block_backward(TbCtx& c, int e, int l, const f16* xin, const f16* y, cons
   f16* dS = TB(f16, c.pl.o_dA);      // ds: gradient of the pre-activation sum = gradient of the identity branch
   f16* dT = TB(f16, c.pl.o_dB);
   f16* dU = TB(f16, c.pl.o_dC);
-  hipLaunchKernelGGL(lo_tb_tail_kernel, dim3((unsigned)((nchunk + 255) / 256)), dim3(256), 0, st, y, dy, dpool, c.gscale / (float)T_HW, dS, lgc8, nchunk);
-  LO_LAUNCH_CHECK("tb_tail");
+  // G null (the eval backward for the images' gradient alone): no weight gradient, no bias column sum, and the tail rides in
+  // BatchNorm2's single pass
+  const bool wg = G != nullptr;
+  if (wg) {
+    hipLaunchKernelGGL(lo_tb_tail_kernel, dim3((unsigned)((nchunk + 255) / 256)), dim3(256), 0, st, y, dy, dpool, c.gscale / (float)T_HW, dS, lgc8, nchunk);
+    LO_LAUNCH_CHECK("tb_tail");
+  }
   // BatchNorm2 (+ layer_scale, Dropout2d): dS -> dT = gradient wrt conv2's output
-  LO_TRYT(tb_bn_backward(c, {.din = {dS, F}, .raw = {TB(f16, b.rawB), F}, .mr = TB(float, b.mrB), .bn = k.bn2, .ls = TP(k.layer_scale),
-                             .dls = TG(k.layer_scale), .out = {dT, F}, .C = F, .act = TB_ACT_LRELU,
-                             .drop = {TB_DROP_2D, LO_DS_BLOCK(e, l, 3)}, .dbias = TG(k.conv2_b)}));
-  LO_TAGGED("tb conv2 wgrad", lo_wgrad_run(h->g3b, TB(f16, b.a2), dT, TB(float, c.pl.o_wslab), TG(k.conv2_w), c.inv_g, st));
+  LO_TRYT(tb_bn_backward(c, {.din = {wg ? dS : dy, F}, .raw = {TB(f16, b.rawB), F}, .mr = TB(float, b.mrB), .bn = k.bn2, .ls = TP(k.layer_scale),
+                             .dls = wg ? TG(k.layer_scale) : nullptr, .out = {dT, F}, .C = F, .act = TB_ACT_LRELU,
+                             .drop = {TB_DROP_2D, LO_DS_BLOCK(e, l, 3)}, .dbias = wg ? TG(k.conv2_b) : nullptr,
+                             .tail_y = wg ? nullptr : y, .tail_dpool = dpool, .tail_ds = dS}));
+  if (wg) LO_TAGGED("tb conv2 wgrad", lo_wgrad_run(h->g3b, TB(f16, b.a2), dT, TB(float, c.pl.o_wslab), TG(k.conv2_w), c.inv_g, st));
   LO_TRYT(lo_pack_weight(TP(k.conv2_w), TB(f16, c.pl.o_wd), c.d1b, st));
   LO_TAGGED("tb conv2 dgrad", lo_conv_run(c.d1b, {.in = dT, .w = TB(f16, c.pl.o_wd), .out = dU}, st));     // dU = d a2
   // proj_drop, proj (compact rows)
-  hipLaunchKernelGGL(lo_tb_projdrop_bwd_kernel, dim3(64, B), dim3(256), 0, st, dU, TB(f16, c.pl.o_dprojc), TB(float, c.pl.o_part), F,
-                     c.d.site(LO_DS_BLOCK(e, l, 2)), c.d.thr, c.d.inv_keep);
-  LO_LAUNCH_CHECK("tb_projdrop_bwd");
-  LO_TRYT(lo_colsum(TB(float, c.pl.o_part), TG(k.proj_b), B * 64, F, F, c.inv_g, st));
-  LO_TAGGED("tb proj wgrad", lo_wgrad_run(h->gpc, TB(f16, b.attc), TB(f16, c.pl.o_dprojc), TB(float, c.pl.o_wslab), TG(k.proj_w), c.inv_g, st));
+  if (wg) {
+    hipLaunchKernelGGL(lo_tb_projdrop_bwd_kernel, dim3(64, B), dim3(256), 0, st, dU, TB(f16, c.pl.o_dprojc), TB(float, c.pl.o_part), F,
+                       c.d.site(LO_DS_BLOCK(e, l, 2)), c.d.thr, c.d.inv_keep);
+    LO_LAUNCH_CHECK("tb_projdrop_bwd");
+    LO_TRYT(lo_colsum(TB(float, c.pl.o_part), TG(k.proj_b), B * 64, F, F, c.inv_g, st));
+    LO_TAGGED("tb proj wgrad", lo_wgrad_run(h->gpc, TB(f16, b.attc), TB(f16, c.pl.o_dprojc), TB(float, c.pl.o_wslab), TG(k.proj_w), c.inv_g, st));
+  } else {
+    // no bias gradient and (frozen) no mask: what is left of the pass is the copy of each sample's first 1024 rows to the compact tensor
+    LO_REQUIRE(!c.d.on, "tb_block_backward: the backward without parameter gradients has no dropout");
+    LO_HIP(hipMemcpy2DAsync(TB(f16, c.pl.o_dprojc), (size_t)1024 * F * 2, dU, (size_t)T_HW * F * 2, (size_t)1024 * F * 2, B, hipMemcpyDeviceToDevice, st));
+  }
   LO_TRYT(lo_transpose_cast(TP(k.proj_w), TB(f16, c.pl.o_wt), F, F, st));
   LO_TAGGED("tb proj dgrad", lo_conv_run(c.dpc, {.in = TB(f16, c.pl.o_dprojc), .w = TB(f16, c.pl.o_wt), .out = TB(f16, c.pl.o_dattc)}, st));
   LO_TRYT(tb_attn_backward(c, e, l, TB(f16, b.qkv)));
   // qkv conv
-  LO_TRYT(tb_colsum16(c, TB(f16, c.pl.o_dqkv), TG(k.qkv_b), px, 3 * F));
-  LO_TAGGED("tb qkv wgrad", lo_wgrad_run(h->gqF, TB(f16, b.bnA), TB(f16, c.pl.o_dqkv), TB(float, c.pl.o_wslab), TG(k.qkv_w), c.inv_g, st));
+  if (wg) {
+    LO_TRYT(tb_colsum16(c, TB(f16, c.pl.o_dqkv), TG(k.qkv_b), px, 3 * F));
+    LO_TAGGED("tb qkv wgrad", lo_wgrad_run(h->gqF, TB(f16, b.bnA), TB(f16, c.pl.o_dqkv), TB(float, c.pl.o_wslab), TG(k.qkv_w), c.inv_g, st));
+  }
   LO_TRYT(lo_transpose_cast(TP(k.qkv_w), TB(f16, c.pl.o_wt), 3 * F, F, st));
   LO_TAGGED("tb qkv dgrad", lo_conv_run(c.dq, {.in = TB(f16, c.pl.o_dqkv), .w = TB(f16, c.pl.o_wt), .out = dU}, st));      // dU = d a1
   // Dropout2d, BatchNorm1: dU -> dT = gradient wrt conv1's output
   LO_TRYT(tb_bn_backward(c, {.din = {dU, F}, .raw = {TB(f16, b.rawA), F}, .mr = TB(float, b.mrA), .bn = k.bn1, .out = {dT, F}, .C = F,
-                             .act = TB_ACT_LRELU, .drop = {TB_DROP_2D, LO_DS_BLOCK(e, l, 0)}, .dbias = TG(k.conv1_b)}));
+                             .act = TB_ACT_LRELU, .drop = {TB_DROP_2D, LO_DS_BLOCK(e, l, 0)}, .dbias = wg ? TG(k.conv1_b) : nullptr}));
   const LoGeom& g1 = l == 0 ? h->g3a : h->g3b;
   const LoGeom& d1 = l == 0 ? c.d1a : c.d1b;
-  LO_TAGGED("tb conv1 wgrad", lo_wgrad_run(g1, xin, dT, TB(float, c.pl.o_wslab), TG(k.conv1_w), c.inv_g, st));
+  if (wg) LO_TAGGED("tb conv1 wgrad", lo_wgrad_run(g1, xin, dT, TB(float, c.pl.o_wslab), TG(k.conv1_w), c.inv_g, st));
   LO_TRYT(lo_pack_weight(TP(k.conv1_w), TB(f16, c.pl.o_wd), d1, st));
   if (!sc) {
     LO_TAGGED("tb conv1 dgrad", lo_conv_run(d1, {.in = dT, .w = TB(f16, c.pl.o_wd), .add_src = dS, .out = dx_out}, st));    // + the identity branch
@@ -445,8 +544,8 @@ int tb_block_backward(TbCtx& c, int e, int l, const f16* xin, const f16* y, cons
     // shortcut = BatchNorm(Conv1x1(x)): dS -> gradient wrt the shortcut conv's output (no activation), its parameters, then both data gradients
     LO_TAGGED("tb conv1 dgrad", lo_conv_run(d1, {.in = dT, .w = TB(f16, c.pl.o_wd), .out = dU}, st));
     LO_TRYT(tb_bn_backward(c, {.din = {dS, F}, .raw = {TB(f16, b.scraw), F}, .mr = TB(float, b.mrS), .bn = k.bn_sc, .out = {dT, F}, .C = F,
-                               .dbias = TG(k.sc_b)}));
-    LO_TAGGED("tb shortcut wgrad", lo_wgrad_run(h->gsc, xin, dT, TB(float, c.pl.o_wslab), TG(k.sc_w), c.inv_g, st));
+                               .dbias = wg ? TG(k.sc_b) : nullptr}));
+    if (wg) LO_TAGGED("tb shortcut wgrad", lo_wgrad_run(h->gsc, xin, dT, TB(float, c.pl.o_wslab), TG(k.sc_w), c.inv_g, st));
     LO_TRYT(lo_transpose_cast(TP(k.sc_w), TB(f16, c.pl.o_wt), F, 128, st));
     LO_TAGGED("tb shortcut dgrad", lo_conv_run(c.dsc, {.in = dT, .w = TB(f16, c.pl.o_wt), .add_src = dU, .out = dx_out}, st));
   }

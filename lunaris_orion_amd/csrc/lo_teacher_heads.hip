@@ -347,9 +347,11 @@ int t_heads_backward(LoTeacher* h, const float* P, const float* pooled_f, const 
   a.thr = d.thr; a.inv_keep = d.inv_keep;
   a.ds_gate = d.site(LO_DS_GATE);
   for (int e = 0; e < h->E; ++e) a.ds_q[e] = d.site(LO_DS_QUALITY(e));
-  LO_HIP(hipMemsetAsync(rows, 0, (size_t)h->B * a.row_len * sizeof(float), st));   // alignment padding inside the rows
+  // grads null (the eval backward for the images' gradient alone): the per-sample rows are scratch and only d_pool_* is the result
+  if (grads) LO_HIP(hipMemsetAsync(rows, 0, (size_t)h->B * a.row_len * sizeof(float), st));   // alignment padding inside the rows
   hipLaunchKernelGGL(lo_t_heads_bwd_kernel, dim3(h->B), dim3(256), 0, st, a);
   LO_LAUNCH_CHECK("t_heads_bwd");
+  if (!grads) return LO_OK;
   return lo_colsum(rows, grads + b0, h->B, (int)a.row_len, (int)a.row_len, 1.0f, st);
 }
 // coef = quality_weight / accum.  Must follow lo_teacher_forward on the evaluated batch (uses its pooled features and masks).

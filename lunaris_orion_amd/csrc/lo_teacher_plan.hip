@@ -151,6 +151,8 @@ static int t_plan_workspace(LoTeacher* h, unsigned flags) {
   h->o_ss_cat = take(192 * 2 * 4);
   const char* dense = getenv("LO_T_DENSE");
   h->sparse = !(dense && atoi(dense) != 0);
+  const char* shared = getenv("LO_T_BWD_SHARED");
+  h->bwd_shared = shared && atoi(shared) != 0;
   const size_t cpx = (size_t)B * 1024;
   h->o_qin = take((size_t)h->qrows * 128 * 2); h->o_U = take((size_t)h->qrows * 1024 * 2); h->o_Z = take(cpx * 1088 * 2);
   h->o_projc = take(cpx * 128 * 2); h->o_rawBc = take(cpx * 128 * 2);

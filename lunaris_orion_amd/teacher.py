@@ -85,6 +85,14 @@ class ExpertBlock(nn.Module):
         self.layer_scale = nn.Parameter(torch.ones(1, out_channels, 1, 1) * layer_scale_init)
 
 
+# gscale of lo_teacher_eval_backward (the train path passes 2**20).  Eval-mode activation gradients are smaller than train-mode ones
+# (x.grad 57x in norm for the same loss on the closed-form state), so 2**20 was not taken for granted:
+# tests/test_teacher_eval_grad_gpu.py::test_gscale_2p20_and_2p24 runs 2**20 and 2**24 against the fp16-rounding oracle.  Measured on the
+# MI355X: both 4.168e-3 from it (16x16-pooled 8.5e-4) and 5.8e-5 from each other -- no underflow at 2**20, which keeps 16x more
+# headroom below fp16's maximum for larger upstream gradients, so the train path's value stays.
+EVAL_GSCALE = 2 ** 20
+
+
 def _alloc_workspace(nbytes: int, device: torch.device) -> torch.Tensor:
     """Device memory for a teacher engine's workspace (`ws`), full-backward scratch (`bws`) or head-gradient `rows`; contents unspecified, see
     `vae._alloc_workspace`.  The poisoned-workspace tests swap this function."""
@@ -119,14 +127,17 @@ class _TeacherFunction(torch.autograd.Function):
     431-432): differentiable outputs quality_scores [B,4] and expert_weights [B,E]; the embeddings and the semantic score are
     returned without a graph (nothing in the reference step differentiates them).  The head inputs of THIS call (pooled
     features, pre-weighting logits, dropout stream) are copied out of the workspace, so later forward calls do not disturb it.
-    want_dx (train mode, input requires grad): the full backward with the images' gradient (lo_teacher_full_backward_dx)."""
+    want_dx (train mode, input requires grad): the full backward with the images' gradient (lo_teacher_full_backward_dx).
+    Eval mode with ``eval_input_grad=True`` and (want_dx or full_backward): the eval kept forward + lo_teacher_eval_backward (frozen
+    BatchNorm, no dropout); without a live parameter its flat gradient is NULL and only the images' gradient is computed."""
 
     @staticmethod
     def forward(ctx, model, want_dx, x, *live):
-        full = (model.all_parameters_live or want_dx) and model.training
+        frozen = (not model.training) and model.eval_input_grad and bool(model.all_parameters_live or want_dx)
+        full = ((model.all_parameters_live or want_dx) and model.training) or frozen
         xd = x.detach().contiguous().float()
-        out, eng, p, seed = model._native_forward(xd, keep=full)
-        ctx.full, ctx.x, ctx.want_dx, ctx.x_dtype = full, (xd if full else None), bool(want_dx and full), x.dtype
+        out, eng, p, seed = model._native_forward(xd, keep=full and not frozen, keep_eval=frozen)
+        ctx.full, ctx.x, ctx.want_dx, ctx.x_dtype, ctx.frozen = full, (xd if full else None), bool(want_dx and full), x.dtype, frozen
         offs, elems = (C.c_size_t * 3)(), (C.c_size_t * 3)()
         _lib.check(_lib.lib.lo_teacher_heads_saved(eng.handle, offs, elems), "lo_teacher_heads_saved")
         saved = [eng.ws[offs[i]:offs[i] + 4 * elems[i]].view(torch.float32).clone() for i in range(3)]
@@ -146,7 +157,8 @@ class _TeacherFunction(torch.autograd.Function):
         b, e = C.c_size_t(), C.c_size_t()
         _lib.check(_lib.lib.lo_teacher_grad_range(eng.handle, C.byref(b), C.byref(e)), "lo_teacher_grad_range")
         rows = _alloc_workspace(w.shape[0] * (e.value - b.value) * 4, w.device).view(torch.float32)
-        grads = torch.zeros_like(model._flat)
+        # (the eval backward with no live parameter computes no parameter gradient: its flat buffer is NULL)
+        grads = torch.zeros_like(model._flat) if (ctx.live_offsets or not ctx.frozen) else None
         dx = None
         if ctx.full and (gq is not None or gw is not None):
             # every parameter on the path (lo_teacher_full_backward_dx; dx = NULL unless the images require grad).  A foreign loss scale (GradScaler: 65 536) is divided out on the
@@ -157,10 +169,17 @@ class _TeacherFunction(torch.autograd.Function):
             if getattr(eng, "bws", None) is None:
                 eng.bws = _alloc_workspace(_lib.lib.lo_teacher_full_backward_bytes(eng.handle), w.device)
             dx = torch.empty_like(ctx.x) if ctx.want_dx and ctx.needs_input_grad[2] else None
-            _lib.check(_lib.lib.lo_teacher_full_backward_dx(eng.handle, ctx.x.data_ptr(), model._flat.data_ptr(), eng.ws.data_ptr(), eng.bws.data_ptr(),
-                                                            pooled_f.data_ptr(), pooled_e.data_ptr(), raw_q.data_ptr(), w.data_ptr(), _lib.ptr(gq),
-                                                            _lib.ptr(gw), float(ctx.drop[0]), int(ctx.drop[1]), float(2 ** 20), rows.data_ptr(),
-                                                            grads.data_ptr(), _lib.ptr(dx), _lib.stream_ptr()), "lo_teacher_full_backward_dx")
+            if ctx.frozen and (grads is not None or dx is not None):
+                _lib.check(_lib.lib.lo_teacher_eval_backward(eng.handle, ctx.x.data_ptr(), model._flat.data_ptr(), eng.ws.data_ptr(), eng.bws.data_ptr(),
+                                                             pooled_f.data_ptr(), pooled_e.data_ptr(), raw_q.data_ptr(), w.data_ptr(), _lib.ptr(gq),
+                                                             _lib.ptr(gw), float(EVAL_GSCALE), rows.data_ptr(), _lib.ptr(grads), _lib.ptr(dx),
+                                                             _lib.stream_ptr()), "lo_teacher_eval_backward")
+            elif not ctx.frozen:
+                _lib.check(_lib.lib.lo_teacher_full_backward_dx(
+                    eng.handle, ctx.x.data_ptr(), model._flat.data_ptr(), eng.ws.data_ptr(), eng.bws.data_ptr(),
+                    pooled_f.data_ptr(), pooled_e.data_ptr(), raw_q.data_ptr(), w.data_ptr(), _lib.ptr(gq),
+                    _lib.ptr(gw), float(ctx.drop[0]), int(ctx.drop[1]), float(2 ** 20), rows.data_ptr(),
+                    grads.data_ptr(), _lib.ptr(dx), _lib.stream_ptr()), "lo_teacher_full_backward_dx")
             for t in (grads, dx):
                 if t is not None:
                     _lib.check(_lib.lib.lo_grad_unscale_dev(t.data_ptr(), t.numel(), scr.data_ptr() + 4, None, _lib.stream_ptr()),
@@ -183,8 +202,13 @@ class _TeacherFunction(torch.autograd.Function):
 
 class LunarMoETeacher(nn.Module):
     def __init__(self, num_experts=4, feature_dim=128, dropout_rate=0.1, rel_pos_size=8, use_checkpointing=True,
-                 expert_layers=3, intermediate_dim=256, embedding_dim=64, mfma_precision: str = "fp16", full_backward: bool = False):
+                 expert_layers=3, intermediate_dim=256, embedding_dim=64, mfma_precision: str = "fp16", full_backward: bool = False,
+                 eval_input_grad: bool = False):
         super().__init__()
+        # eval_input_grad (an addition of this build, opt-in): in eval mode an input that requires grad gets its gradient (and, with
+        # full_backward, the trunk its parameter gradients) through BatchNorm at the running statistics -- see `forward`.  Default:
+        # the eval-mode teacher gives the images no gradient and warns
+        self.eval_input_grad = bool(eval_input_grad)
         # full_backward (an addition of this build): the autograd graph of `quality_scores` / `expert_weights` covers EVERY
         # parameter on their path -- experts and feature extractor included -- i.e. the reference with `use_reentrant=False` at its three
         # checkpoint calls (lunar_evaluator.py:194-197, 266-275, 411-414).  Default: the reference as it executes (gate + quality heads only).
@@ -370,9 +394,10 @@ class LunarMoETeacher(nn.Module):
         with torch.no_grad():
             self._nbt += 1
 
-    def _native_forward(self, x: torch.Tensor, keep: bool = False):
+    def _native_forward(self, x: torch.Tensor, keep: bool = False, keep_eval: bool = False):
         """One `lo_teacher_forward` (keep: `lo_teacher_forward_keep`, the train-mode forward of a step that ends in `full_backward`: every
-        block's output stays in the backward's scratch).  Returns (outputs, engine, dropout_p, call seed)."""
+        block's output stays in the backward's scratch; keep_eval: `lo_teacher_forward_keep_eval`, the same for an eval-mode module and
+        `lo_teacher_eval_backward`, which moves no state).  Returns (outputs, engine, dropout_p, call seed)."""
         if x.dim() != 4 or tuple(x.shape[1:]) != (3, 128, 128):
             raise ValueError(f"expected input of shape [B, 3, 128, 128], got {tuple(x.shape)}")
         x = x.detach().contiguous().float()
@@ -392,6 +417,12 @@ class LunarMoETeacher(nn.Module):
             _lib.check(_lib.lib.lo_teacher_forward_keep(eng.handle, x.data_ptr(), self._flat.data_ptr(), eng.ws.data_ptr(), eng.bws.data_ptr(),
                                                         p, seed, q.data_ptr(), w.data_ptr(), st.data_ptr(), pr.data_ptr(), sem.data_ptr(),
                                                         _lib.stream_ptr()), "lo_teacher_forward_keep")
+        elif keep_eval and not self.training:
+            if getattr(eng, "bws", None) is None:
+                eng.bws = _alloc_workspace(_lib.lib.lo_teacher_full_backward_bytes(eng.handle), dev)
+            _lib.check(_lib.lib.lo_teacher_forward_keep_eval(eng.handle, x.data_ptr(), self._flat.data_ptr(), eng.ws.data_ptr(), eng.bws.data_ptr(),
+                                                             q.data_ptr(), w.data_ptr(), st.data_ptr(), pr.data_ptr(), sem.data_ptr(),
+                                                             _lib.stream_ptr()), "lo_teacher_forward_keep_eval")
         else:
             _lib.check(_lib.lib.lo_teacher_forward(eng.handle, x.data_ptr(), self._flat.data_ptr(), eng.ws.data_ptr(), 1 if self.training else 0,
                                                    p, seed, q.data_ptr(), w.data_ptr(), st.data_ptr(), pr.data_ptr(), sem.data_ptr(),
@@ -440,11 +471,23 @@ class LunarMoETeacher(nn.Module):
         ``quality_scores`` / ``expert_weights`` receives its gradient (the ones ``full_backward=True`` gives), through the kept forward
         (its scratch is 26 GB at batch 64, feature_dim 128).  The BatchNorm running statistics move once per forward, as in the full
         backward (nothing is recomputed); the reference's reentrant recompute would advance them a second time.  In eval mode an input
-        that requires grad gets no gradient (a UserWarning says so) and the outputs are those of the eval forward."""
+        that requires grad gets no gradient (a UserWarning says so) and the outputs are those of the eval forward.
+
+        ``LunarMoETeacher(eval_input_grad=True)`` in eval mode (the frozen reward model: deterministic, independent of the other
+        samples of the batch, running statistics untouched) mirrors the train-mode rule with every BatchNorm differentiated at its
+        running statistics and no dropout.  An input that requires grad gets ``x.grad`` without a warning (eval kept forward +
+        ``lo_teacher_eval_backward``) and every parameter on the path that requires grad its gradient, whatever ``full_backward``
+        says; if none does (``teacher.requires_grad_(False)``) no parameter gradient is computed at all and ``x.grad`` has the same
+        bits.  An input that does not require grad with ``full_backward=True``: the same backward without the images' gradient
+        (fine-tuning with frozen BatchNorm); with ``full_backward=False``: the default eval forward and the heads-only backward.  The
+        outputs of such a call come from the plain-form eval forward: they differ from the default (folded at feature_dim 128) eval
+        forward at the fp16 rounding level, like any two paths of ``lo_teacher_forward``.  Running statistics, ``num_batches_tracked``
+        and the dropout stream (``drop_calls``) do not move; the three other outputs stay non-differentiable."""
         self._ensure_flat()
         if torch.is_grad_enabled():
-            want_dx = bool(x.requires_grad) and self.training
-            if x.requires_grad and not self.training:
+            ev = self.eval_input_grad and not self.training
+            want_dx = bool(x.requires_grad) and (self.training or ev)
+            if x.requires_grad and not self.training and not ev:
                 warnings.warn("LunarMoETeacher in eval mode: the input requires grad but gets no gradient (its input gradient is built "
                               "for train mode only); outputs are the eval-mode forward's", UserWarning, stacklevel=2)
             live = [p for p in self._live_parameters(want_dx) if p.requires_grad]
