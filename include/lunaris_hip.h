@@ -119,6 +119,10 @@ int lo_first_conv_wgrad_op(const float* x, const void* dv, float* partial /*B*16
  * dy fp16 NHWC [B][128/stride][128/stride][cout], w fp32 [cout][3][3][3].  Built for (stride 2, cout 64: the VAE's encoder.down1.0) and
  * (stride 1, cout 32: the teacher's feature_extractor.conv1.0).  Deterministic (no atomics). */
 int lo_image_dgrad_op(const void* dy, int cout, int stride, const float* w, int B, float scale, float* dx, void* stream);
+/* the seeded store of the (stride 1, cout 32) kernel: dx = scale * conv2d_input(dy, w) + seed_coef[0] * (recon - target); seed_coef one float
+ * on the device, recon / target fp32 NCHW [B,3,128,128], read at the address of the store.  seed_coef[0] == 0: the bits of lo_image_dgrad_op. */
+int lo_image_dgrad_seed_op(const void* dy, int cout, int stride, const float* w, int B, float scale, const float* seed_coef,
+                           const float* recon, const float* target, float* dx, void* stream);
 /* final conv Conv2d(32,3,k3,p1)+tanh (+MSE partial sums, B*64 floats) (lunar_generate.py:192,227-228; train_hybrid.py:859).
  * a4 / da4 fp16 NHWC [B,128,128,32]; w [3,32,3,3], bias / db [3]; recon, target, drecon fp32 NCHW [B,3,128,128]; coef_dev one float;
  * partial B*64*867 floats of scratch. */
@@ -310,9 +314,16 @@ int lo_vae_encoder_backward_dx(LoVae* h, const float* x, const float* flat_param
  * lo_vae_backward(fused=1). */
 int lo_vae_loss(LoVae* h, void* ws, float recon_weight, float kl_weight, float mean_advantage, const float* adv_dev,
                 float accum, float loss_scale, float* losses_dev, void* stream);
+/* The reward-gradient term of the hybrid step, behind lo_vae_loss on the same stream: q_eval = quality_scores [B][4] of the eval-mode
+ * teacher on the reconstruction.  out2 = {-weight * mean(q_eval) / accum, mean(q_eval)}; the term is added to losses_dev[2] (vae_loss);
+ * seed_coef[0] = the un-scaled MSE coefficient of d vae_loss / d recon (lo_vae_loss's, its loss scale divided out) for
+ * lo_teacher_eval_backward_seed.  loss_scale: the one lo_vae_loss was given. */
+int lo_vae_reward_term(LoVae* h, void* ws, const float* q_eval, float weight, float accum, float loss_scale, float* losses_dev,
+                       float* out2, float* seed_coef, void* stream);
 /* backward into flat_grads (same layout as the parameters; every element is written).  fused=1: gradients of the
  * vae_loss prepared by lo_vae_loss (needs `target`).  fused=0: explicit upstream gradients drecon/gmu/glv (fp32, may
- * be NULL = zero). */
+ * be NULL = zero).  fused=2: the latent seeds (KL) of lo_vae_loss as fused=1, the reconstruction's gradient the explicit, un-scaled
+ * drecon (the seed lo_teacher_eval_backward_seed leaves: reward term + MSE term). */
 int lo_vae_backward(LoVae* h, const float* x, const float* flat_params, void* ws, const float* recon, const float* target,
                     int fused, const float* drecon, const float* gmu, const float* glv, float loss_scale,
                     float* flat_grads, void* stream);
@@ -466,6 +477,17 @@ int lo_teacher_eval_backward(LoTeacher* h, const float* images_nchw, const float
                              const float* d_quality, const float* d_weights, float gscale, float* rows,
                              float* flat_grads /* NULL: parameter gradients not wanted */,
                              float* dx /* fp32 NCHW [B,3,128,128]; NULL: not wanted */, void* stream);
+/* lo_teacher_eval_backward with flat_grads = NULL whose last kernel (the image data gradient of conv1) stores the SEEDED form
+ *   dx = scale_factor * (d / d images) + seed_coef[0] * (images - target)
+ * seed_coef: one float on the device (lo_vae_reward_term writes it), target: fp32 NCHW [B,3,128,128].  The hybrid step's reward-gradient
+ * objective: the teacher's input IS the VAE's reconstruction, so dx is the complete d vae_loss / d recon (reward term + MSE term) with no
+ * add pass.  scale_factor multiplies the fp32 result, not the fp16 activation gradients: pass upstream rows of order 1 (the step passes
+ * constant rows of -2) and fold the objective's small coefficient in here.  seed_coef[0] == 0 and scale_factor == 1: the bits of
+ * lo_teacher_eval_backward. */
+int lo_teacher_eval_backward_seed(LoTeacher* h, const float* images_nchw, const float* flat_state, void* ws, void* bws,
+                                  const float* pooled_f, const float* pooled_e, const float* raw_q, const float* expert_weights,
+                                  const float* d_quality, const float* d_weights, float gscale, float* rows, const float* target,
+                                  const float* seed_coef, float scale_factor, float* dx, void* stream);
 /* clip_grad_norm_(teacher.parameters()) + AdamW (train_hybrid.py:914, 922) with every teacher parameter live: the norm over the whole
  * flat gradient of lo_teacher_full_backward, the update over exactly the tensors that have a .grad in the reference (not the
  * BatchNorm buffers, not the style / prompt / semantic heads, whose .grad is None there).  m, v: lo_teacher_flat_elems floats each,

@@ -49,6 +49,7 @@ SIGNATURES = {
     "lo_first_conv_forward": (i32, [f32p, f32p, f32p, vp, f32p, i32, vp]),
     "lo_first_conv_wgrad_op": (i32, [f32p, vp, f32p, f32p, i32, flt, vp]),
     "lo_image_dgrad_op": (i32, [vp, i32, i32, f32p, i32, flt, f32p, vp]),
+    "lo_image_dgrad_seed_op": (i32, [vp, i32, i32, f32p, i32, flt, f32p, f32p, f32p, f32p, vp]),
     "lo_final_conv_forward": (i32, [vp, f32p, f32p, f32p, f32p, f32p, i32, vp]),
     "lo_final_conv_backward": (i32, [vp, f32p, f32p, f32p, f32p, f32p, flt, vp, f32p, f32p, f32p, i32, flt, vp]),
     "lo_decode_sprites_u8": (i32, [vp, f32p, i32, vp]),
@@ -78,6 +79,7 @@ SIGNATURES = {
     "lo_teacher_forward_keep": (i32, [vp, f32p, f32p, vp, vp, flt, u64, f32p, f32p, f32p, f32p, f32p, vp]),
     "lo_teacher_forward_keep_eval": (i32, [vp, f32p, f32p, vp, vp, f32p, f32p, f32p, f32p, f32p, vp]),
     "lo_teacher_eval_backward": (i32, [vp, f32p, f32p, vp, vp, f32p, f32p, f32p, f32p, f32p, f32p, flt, f32p, f32p, f32p, vp]),
+    "lo_teacher_eval_backward_seed": (i32, [vp, f32p, f32p, vp, vp, f32p, f32p, f32p, f32p, f32p, f32p, flt, f32p, f32p, f32p, flt, f32p, vp]),
     "lo_teacher_full_backward": (i32, [vp, f32p, f32p, vp, vp, f32p, flt, flt, f32p, f32p, vp]),
     "lo_teacher_clip_adamw_full": (i32, [vp, f32p, f32p, f32p, f32p, flt, flt, flt, flt, flt, flt, i32, f32p, vp]),
     "lo_teacher_full_param_count": (i32, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
@@ -120,6 +122,7 @@ SIGNATURES = {
     "lo_vae_encoder_backward": (i32, [vp, f32p, f32p, vp, f32p, f32p, f32p, f32p, f32p, flt, f32p, vp]),
     "lo_vae_encoder_backward_dx": (i32, [vp, f32p, f32p, vp, f32p, f32p, f32p, f32p, f32p, flt, f32p, f32p, vp]),
     "lo_vae_loss": (i32, [vp, vp, flt, flt, flt, f32p, flt, flt, f32p, vp]),
+    "lo_vae_reward_term": (i32, [vp, vp, f32p, flt, flt, flt, f32p, f32p, f32p, vp]),
     "lo_vae_backward": (i32, [vp, f32p, f32p, vp, f32p, f32p, i32, f32p, f32p, f32p, flt, f32p, vp]),
     "lo_vae_backward_dx": (i32, [vp, f32p, f32p, vp, f32p, f32p, i32, f32p, f32p, f32p, flt, f32p, f32p, vp]),
     "lo_vae_backward_phase": (i32, [vp, i32, f32p, f32p, vp, f32p, f32p, i32, f32p, f32p, f32p, flt, f32p, vp]),

@@ -131,6 +131,11 @@ extern "C" int lo_first_conv_wgrad_op(const float* x, const void* dv, float* par
 extern "C" int lo_image_dgrad_op(const void* dy, int cout, int stride, const float* w, int B, float scale, float* dx, void* stream) {
   return lo_image_dgrad((const f16*)dy, cout, stride, w, B, scale, dx, S(stream));
 }
+extern "C" int lo_image_dgrad_seed_op(const void* dy, int cout, int stride, const float* w, int B, float scale, const float* seed_coef,
+                                      const float* recon, const float* target, float* dx, void* stream) {
+  const LoImgSeed seed{seed_coef, recon, target};
+  return lo_image_dgrad((const f16*)dy, cout, stride, w, B, scale, dx, S(stream), &seed);
+}
 extern "C" int lo_final_conv_forward(const void* a4, const float* w, const float* bias, const float* target, float* recon,
                                      float* mse_partial, int B, void* stream) {
   return lo_final_conv_fwd((const f16*)a4, w, bias, target, recon, mse_partial, B, S(stream));

@@ -57,15 +57,23 @@ __device__ __forceinline__ f32x4 idg_finish(f32x4 acc, float scale) {
   return r;
 }
 
-// stride 1, 32 channels (teacher): grid (2 * 128 / ROWS, B), 4 waves; wave = 16-column strip x0 .. x0 + 15, rows y0 .. y0 + ROWS - 1
-template <int ROWS>
+// stride 1, 32 channels (teacher): grid (2 * 128 / ROWS, B), 4 waves; wave = 16-column strip x0 .. x0 + 15, rows y0 .. y0 + ROWS - 1.
+// SEED: the store is dx = scale * conv2d_input(dy, w) + c * (recon - target), c = seed.c[0] on the device, recon / target fp32 NCHW
+// read at the address of the store (the same 64-byte rows per wave) -- the last kernel of the teacher's backward then emits the whole
+// d loss / d recon of a reward + MSE objective, with no add pass of its own.  The loads of a row are issued in front of its MFMAs.
+// c == 0 stores the un-seeded value itself (whatever recon / target hold).  SEED = false: the kernel as it was (IdgSeed<false> is empty).
+template <bool SEED> struct IdgSeed { const float *c, *recon, *target; };
+template <> struct IdgSeed<false> {};
+template <int ROWS, bool SEED = false>
 __global__ __launch_bounds__(256) void lo_image_dgrad_s1_kernel(const f16* __restrict__ dy, const float* __restrict__ w, float scale,
-                                                                float* __restrict__ dx) {
+                                                                float* __restrict__ dx, IdgSeed<SEED> seed = {}) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
   const int n = blockIdx.y;
   const int x = ((blockIdx.x & 1) * 4 + wave) * 16 + j;
   const int y0 = (blockIdx.x >> 1) * ROWS;
   __shared__ float ws[32 * 27];
+  float cs = 0.f;
+  if constexpr (SEED) cs = seed.c[0];
   idg_stage_w<32>(w, ws);
   f16x8 A[9];
 #pragma unroll
@@ -80,6 +88,16 @@ __global__ __launch_bounds__(256) void lo_image_dgrad_s1_kernel(const f16* __res
     f16x8 nxt[3];
 #pragma unroll
     for (int kx = 0; kx < 3; ++kx) nxt[kx] = idg_load<128, 32>(dy, n, y + 2, x + 1 - kx, 0, g);
+    float sr[3], stg[3];
+    if constexpr (SEED) {
+      if (g == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          sr[c] = seed.recon[(((size_t)n * 3 + c) * 128 + y) * 128 + x];
+          stg[c] = seed.target[(((size_t)n * 3 + c) * 128 + y) * 128 + x];
+        }
+      }
+    }
     f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ky = 0; ky < 3; ++ky)
@@ -88,7 +106,11 @@ __global__ __launch_bounds__(256) void lo_image_dgrad_s1_kernel(const f16* __res
     const f32x4 o = idg_finish(acc, scale);
     if (g == 0) {
 #pragma unroll
-      for (int c = 0; c < 3; ++c) dx[(((size_t)n * 3 + c) * 128 + y) * 128 + x] = o[c];
+      for (int c = 0; c < 3; ++c) {
+        float v = o[c];
+        if constexpr (SEED) v = cs != 0.f ? fmaf(cs, sr[c] - stg[c], v) : v;
+        dx[(((size_t)n * 3 + c) * 128 + y) * 128 + x] = v;
+      }
     }
 #pragma unroll
     for (int kx = 0; kx < 3; ++kx) { win[0][kx] = win[1][kx]; win[1][kx] = win[2][kx]; win[2][kx] = nxt[kx]; }
@@ -152,17 +174,23 @@ __global__ __launch_bounds__(256) void lo_image_dgrad_s2_kernel(const f16* __res
   }
 }
 
-int lo_image_dgrad(const f16* dy, int cout, int stride, const float* w, int B, float scale, float* dx, hipStream_t st) {
+int lo_image_dgrad(const f16* dy, int cout, int stride, const float* w, int B, float scale, float* dx, hipStream_t st, const LoImgSeed* seed) {
   LO_REQUIRE(dy && w && dx, "lo_image_dgrad: null argument");
+  LO_REQUIRE(!seed || (seed->c && seed->recon && seed->target), "lo_image_dgrad: seed with a null member");
+  LO_REQUIRE(!seed || (stride == 1 && cout == 32), "lo_image_dgrad: the seeded form is built for (stride 1, 32 channels), got (%d, %d)", stride, cout);
   LO_REQUIRE(B > 0 && B <= 65535, "lo_image_dgrad: batch %d outside [1, 65535]", B);
   LO_REQUIRE((stride == 1 && cout == 32) || (stride == 2 && cout == 64),
              "lo_image_dgrad: built for (stride 1, 32 channels) and (stride 2, 64 channels), got (%d, %d)", stride, cout);
   const double ho = 128 / stride;
-  LoProfScope _p(stride == 1 ? "lo_image_dgrad s1" : "lo_image_dgrad s2", 2.0 * B * ho * ho * cout * 27,
-                 (double)B * (ho * ho * cout * 2 + 3 * 16384 * 4), st);
+  LoProfScope _p(seed ? "lo_image_dgrad s1 seeded" : stride == 1 ? "lo_image_dgrad s1" : "lo_image_dgrad s2", 2.0 * B * ho * ho * cout * 27,
+                 (double)B * (ho * ho * cout * 2 + (seed ? 3 : 1) * 3 * 16384 * 4), st);
   if (stride == 1) {
     constexpr int ROWS = 16;
-    hipLaunchKernelGGL((lo_image_dgrad_s1_kernel<ROWS>), dim3(2 * 128 / ROWS, B), dim3(256), 0, st, dy, w, scale, dx);
+    if (seed)
+      hipLaunchKernelGGL((lo_image_dgrad_s1_kernel<ROWS, true>), dim3(2 * 128 / ROWS, B), dim3(256), 0, st, dy, w, scale, dx,
+                         IdgSeed<true>{seed->c, seed->recon, seed->target});
+    else
+      hipLaunchKernelGGL((lo_image_dgrad_s1_kernel<ROWS, false>), dim3(2 * 128 / ROWS, B), dim3(256), 0, st, dy, w, scale, dx, IdgSeed<false>{});
   } else {
     constexpr int MROWS = 8;
     hipLaunchKernelGGL((lo_image_dgrad_s2_kernel<MROWS>), dim3(64 / MROWS, B), dim3(256), 0, st, dy, w, scale, dx);

@@ -19,7 +19,13 @@ int lo_colsum(const float* partial, float* out, int nrow, int ncol, int stride, 
 
 // lo_imgdgrad.hip: data gradient of a 3x3 / padding 1 conv with 3 input channels onto fp32 NCHW [B,3,128,128] images
 // (stride 1 with 32 channels: the teacher's conv1; stride 2 with 64 channels: the VAE's first conv).  dy fp16 NHWC, w fp32 [cout][3][3][3]
-int lo_image_dgrad(const f16* dy, int cout, int stride, const float* w, int B, float scale, float* dx, hipStream_t st);
+// seed (stride 1 / 32 channels only): dx = scale * conv2d_input(dy, w) + c[0] * (recon - target), c on the device, recon / target fp32 NCHW
+struct LoImgSeed { const float* c; const float* recon; const float* target; };
+int lo_image_dgrad(const f16* dy, int cout, int stride, const float* w, int B, float scale, float* dx, hipStream_t st,
+                   const LoImgSeed* seed = nullptr);
+// lo_teacher_heads.hip: the reward-gradient term of the hybrid step behind lo_loss_finalize (lo_vae_reward_term)
+int lo_reward_term(const float* q_eval, int B, float weight, float accum, float loss_scale, const float* coefs, float* losses, float* out2,
+                   float* seed_c, hipStream_t st);
 int lo_final_conv_fwd(const f16* a4, const float* w, const float* bias, const float* target, float* recon,
                       float* mse_partial, int B, hipStream_t st);
 int lo_final_conv_bwd(const f16* a4, const float* w, const float* recon, const float* target, const float* drecon,

@@ -212,6 +212,8 @@ struct TbCtx {
   LoTeacher* h; float* P; void* ws; void* bws; float* G; hipStream_t st; TbPlan pl;
   LoDropCfg d; float gscale, inv_g;
   int frozen = 0;                         // 1: eval mode -- every BatchNorm with its running statistics, differentiated as constants
+  const LoImgSeed* seed = nullptr;        // lo_teacher_eval_backward_seed: the image data gradient stores dx_factor * (d / dx) + seed->c (x - seed->target)
+  float dx_factor = 1.0f;
   LoGeom d1a, d1b, dq, dpc, dsc;          // data gradients of a block's conv 128->F, conv F->F, qkv, proj on the compact rows, shortcut
 };
 // BatchNorm backward of one layer: upstream din -> gradient wrt the conv output (out), parameter gradients into G (dbias: the bias

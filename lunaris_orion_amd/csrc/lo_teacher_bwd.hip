@@ -383,7 +383,7 @@ static int tb_fe_backward(TbCtx& c, const float* x, float* dx) {
     LO_TRYT(lo_colsum(TB(float, c.pl.o_part), TG(fe.conv1_w), B * 128, 864, 864, c.inv_g, st));
     LO_TRYT(lo_colsum(TB(float, c.pl.o_bpart), TG(fe.conv1_b), B * 128, 32, 32, c.inv_g, st));
   }
-  if (dx) LO_TRYT(lo_image_dgrad(ddw, 32, 1, TP(fe.conv1_w), B, c.inv_g, dx, st));
+  if (dx) LO_TRYT(lo_image_dgrad(ddw, 32, 1, TP(fe.conv1_w), B, c.seed ? c.inv_g * c.dx_factor : c.inv_g, dx, st, c.seed));
   return LO_OK;
 }
 
@@ -431,13 +431,14 @@ extern "C" int lo_teacher_forward_keep_eval(LoTeacher* h, const float* x, const 
 // parameter gradient is computed: no weight-gradient GEMM, no column sum, no BatchNorm reduce) and dx alone is produced.
 static int tb_full_backward_impl(LoTeacher* h, const float* x, float* P, void* ws, void* bws, const float* pooled_f, const float* pooled_e,
                                  const float* raw_q, const float* expert_weights, const float* dq_up, const float* dw_up, float coef,
-                                 float drop_p, uint64_t drop_seed, float gscale, float* rows, float* grads, float* dx, void* stream, int frozen = 0) {
+                                 float drop_p, uint64_t drop_seed, float gscale, float* rows, float* grads, float* dx, void* stream, int frozen = 0,
+                                 const LoImgSeed* seed = nullptr, float dx_factor = 1.0f) {
   LO_REQUIRE(h && x && P && ws && bws && expert_weights && rows && (grads || (frozen && dx)), "lo_teacher_full_backward: null argument");
   LO_REQUIRE(gscale > 0.f, "lo_teacher_full_backward: gscale must be positive");
   LO_REQUIRE(h->last_path >= 0, "lo_teacher_full_backward: no forward has run on this engine");
   TbCtx c;
   LO_TRYT(tb_ctx_init(c, h, P, ws, bws, grads, drop_p, drop_seed, gscale, stream));
-  c.frozen = frozen;
+  c.frozen = frozen; c.seed = seed; c.dx_factor = dx_factor;
   hipStream_t st = c.st;
   float* G = grads;
   const int B = h->B, F = h->F, E = h->E;
@@ -558,4 +559,17 @@ extern "C" int lo_teacher_eval_backward(LoTeacher* h, const float* x, const floa
   LO_REQUIRE(pooled_f && pooled_e && raw_q && (d_quality || d_weights) && (grads || dx), "lo_teacher_eval_backward: null argument");
   return tb_full_backward_impl(h, x, const_cast<float*>(P), ws, bws, pooled_f, pooled_e, raw_q, expert_weights, d_quality, d_weights, 0.f, 0.f, 0,
                                gscale, rows, grads, dx, stream, 1);
+}
+// The same with flat_grads = NULL and the SEEDED image data gradient as its last kernel: dx = scale_factor * (d / d images) +
+// seed_coef[0] * (images - target) -- the whole d vae_loss / d recon of the hybrid step's reward-gradient objective (the teacher's
+// input is the reconstruction), with no add pass.  The chain above with one more field in its context
+extern "C" int lo_teacher_eval_backward_seed(LoTeacher* h, const float* x, const float* P, void* ws, void* bws, const float* pooled_f,
+                                             const float* pooled_e, const float* raw_q, const float* expert_weights, const float* d_quality,
+                                             const float* d_weights, float gscale, float* rows, const float* target, const float* seed_coef,
+                                             float scale_factor, float* dx, void* stream) {
+  LO_REQUIRE(pooled_f && pooled_e && raw_q && (d_quality || d_weights) && dx && x && target && seed_coef, "lo_teacher_eval_backward_seed: null argument");
+  LO_REQUIRE(scale_factor > 0.f, "lo_teacher_eval_backward_seed: scale_factor must be positive");
+  const LoImgSeed seed{seed_coef, x, target};
+  return tb_full_backward_impl(h, x, const_cast<float*>(P), ws, bws, pooled_f, pooled_e, raw_q, expert_weights, d_quality, d_weights, 0.f, 0.f, 0,
+                               gscale, rows, nullptr, dx, stream, 1, &seed, scale_factor);
 }

@@ -273,6 +273,31 @@ __global__ void lo_hybrid_reward_kernel(const float* __restrict__ quality, const
   adv_dev[0] = adv;
 }
 
+// The reward-gradient term of the hybrid step (-weight * mean(q_eval) / accum, q_eval = the EVAL-mode teacher's quality_scores on the
+// reconstruction), behind lo_loss_finalize on the same stream: out2 = {term, mean(q_eval)}; losses[2] (vae_loss) += term;
+// seed_c[0] = coefs[0] / loss_scale, the un-scaled multiplier of (recon - target) in d vae_loss / d recon (what the seeded image data
+// gradient adds; lo_vae_backward(fused = 2) applies the loss scale to the whole seed)
+__global__ void lo_reward_term_kernel(const float* __restrict__ q_eval, int B, float weight, float accum, float loss_scale,
+                                      const float* __restrict__ coefs, float* __restrict__ losses, float* __restrict__ out2,
+                                      float* __restrict__ seed_c) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  double sq = 0.0;
+  for (int n = 0; n < B; ++n) sq += ((double)q_eval[n * 4] + q_eval[n * 4 + 1] + q_eval[n * 4 + 2] + q_eval[n * 4 + 3]) * 0.25;
+  const float q_mean = (float)(sq / B);
+  const float term = -weight * q_mean / accum;
+  out2[0] = term;
+  out2[1] = q_mean;
+  losses[2] += term;
+  seed_c[0] = coefs[0] / loss_scale;
+}
+int lo_reward_term(const float* q_eval, int B, float weight, float accum, float loss_scale, const float* coefs, float* losses, float* out2,
+                   float* seed_c, hipStream_t st) {
+  LO_REQUIRE(q_eval && coefs && losses && out2 && seed_c && B > 0 && accum > 0.f && loss_scale > 0.f, "lo_reward_term: bad argument");
+  hipLaunchKernelGGL(lo_reward_term_kernel, dim3(1), dim3(64), 0, st, q_eval, B, weight, accum, loss_scale, coefs, losses, out2, seed_c);
+  LO_LAUNCH_CHECK("reward_term");
+  return LO_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------

@@ -190,6 +190,13 @@ extern "C" int lo_vae_loss(LoVae* h, void* ws, float recon_weight, float kl_weig
   h->loss_done = true;
   return LO_OK;
 }
+// the hybrid step's reward-gradient term behind lo_vae_loss (the kernel sits beside lo_hybrid_reward's)
+extern "C" int lo_vae_reward_term(LoVae* h, void* ws, const float* q_eval, float weight, float accum, float loss_scale, float* losses_dev,
+                                  float* out2, float* seed_coef, void* stream) {
+  LO_REQUIRE(h && ws && q_eval && losses_dev && out2 && seed_coef, "lo_vae_reward_term: null argument");
+  if (!h->loss_done) { lo_set_error("lo_vae_reward_term: lo_vae_loss has not run"); return LO_ERR_STATE; }
+  return lo_reward_term(q_eval, h->B, weight, accum, loss_scale, WSP(float, h->o_coefs), losses_dev, out2, seed_coef, S(stream));
+}
 
 // GroupNorm affine + conv bias gradients of a set of layers in one launch (enc_mask: bit s = encoder stage s)
 static int vae_gn_finalize(LoVae* h, unsigned enc_mask, bool dec, float* G, void* ws, float inv, hipStream_t st) {
@@ -371,11 +378,12 @@ int VaeBackward::dgrad(ConvLayer& c, int k, const f16* dv, f16* din, const f16* 
 // decoder's GroupNorm / bias gradients after their finalize).  dz32 (Decoder.forward's own backward): dz also as fp32
 int VaeBackward::decoder_chain(int fused, const float* recon, const float* target, const float* drecon, bool fac, float* dz32) {
   const int B = h->B, L = h->L;
-  // ---- final conv (+tanh, + fused MSE gradient)
-  if (fused || drecon) {
+  // ---- final conv (+tanh, + fused MSE gradient; fused == 2: the reconstruction's gradient is the explicit drecon, only the latent seeds are lo_vae_loss's)
+  const bool fr = fused == 1;
+  if (fr || drecon) {
     LoHandover ho(h, side && !lo_event_marker());     // rides on the kernel; the dw / db column sums follow it on the side stream
-    LO_TRY(lo_final_conv_bwd(WSP(f16, h->dec[3].o_a), PRM(h->idx_final_w), recon, fused ? target : nullptr, fused ? nullptr : drecon,
-                             fused ? WSP(float, h->o_coefs) : nullptr, loss_scale, Ga, WSP(float, h->o_lc_part),
+    LO_TRY(lo_final_conv_bwd(WSP(f16, h->dec[3].o_a), PRM(h->idx_final_w), recon, fr ? target : nullptr, fr ? nullptr : drecon,
+                             fr ? WSP(float, h->o_coefs) : nullptr, loss_scale, Ga, WSP(float, h->o_lc_part),
                              GRD(h->idx_final_w), GRD(h->idx_final_b), B, inv, st, ho.ev ? h->side : nullptr, ho.ev));
   } else {
     LO_HIP(hipMemsetAsync(Ga, 0, (size_t)B * 128 * 128 * 32 * 2, st));
@@ -508,6 +516,7 @@ int VaeBackward::publish_range(unsigned enc_mask, bool dec) {
 // what every backward entry point checks first (fwd_ran: the forward whose activations it reads)
 int vae_backward_checks(const LoVae* h, bool args_ok, bool fwd_ran, int fused, const float* target, float loss_scale) {
   LO_REQUIRE(args_ok, "lo_vae_backward: null argument");
+  LO_REQUIRE(fused >= 0 && fused <= 2, "lo_vae_backward: fused must be 0 (explicit), 1 (lo_vae_loss) or 2 (lo_vae_loss's latent seeds, explicit drecon), got %d", fused);
   if (!fwd_ran) { lo_set_error("lo_vae_backward: the forward this backward belongs to has not run"); return LO_ERR_STATE; }
   if (fused && (!h->loss_done || !target)) { lo_set_error("lo_vae_backward: fused mode needs lo_vae_loss and a target"); return LO_ERR_STATE; }
   LO_REQUIRE(loss_scale > 0.f, "lo_vae_backward: loss_scale must be positive");
@@ -521,6 +530,7 @@ extern "C" int lo_vae_backward_dx(LoVae* h, const float* x, const float* P, void
                                   float* G, float* dx, void* stream) {
   const bool args_ok = h && P && ws && G && x && recon;
   LO_TRY(vae_backward_checks(h, args_ok, args_ok && h->forward_done, fused, target, loss_scale));
+  LO_REQUIRE(fused != 2 || drecon, "lo_vae_backward: fused = 2 needs the explicit drecon");
   VaeBackward b(h, P, G, ws, loss_scale, stream);
   LO_TRY(b.begin(true));
   // the Linear layers' weight gradients stay factored (lo_lowrank.hip): the fused single-call backward of a stepper only
@@ -554,6 +564,7 @@ extern "C" int lo_vae_backward_phase(LoVae* h, int phase, const float* x, const 
              "3 (encoder stage 4) or 4 (encoder stages 3..1, after 3)");
   const bool args_ok = h && P && ws && G && x && recon;
   LO_TRY(vae_backward_checks(h, args_ok, args_ok && h->forward_done, fused, target, loss_scale));
+  LO_REQUIRE(fused != 2 || drecon, "lo_vae_backward: fused = 2 needs the explicit drecon");
   VaeBackward b(h, P, G, ws, loss_scale, stream);
   LO_TRY(b.begin(phase == 1));
   const bool async = b.side && h->async_handover;

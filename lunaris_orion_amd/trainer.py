@@ -190,12 +190,14 @@ class VAEStepper:
             ev.record()
             self._skip_inflight.append((ev, slot, self.opt_steps))
 
-    def _backward_and_exchange(self, eng, images: torch.Tensor, recon: torch.Tensor, st) -> None:
-        """Native backward of the fused loss into ``self.grads`` (+ the data-parallel exchange, overlapped with it)."""
+    def _backward_and_exchange(self, eng, images: torch.Tensor, recon: torch.Tensor, st, drecon: Optional[torch.Tensor] = None) -> None:
+        """Native backward of the fused loss into ``self.grads`` (+ the data-parallel exchange, overlapped with it).  drecon: the
+        un-scaled d vae_loss / d recon as an explicit seed (``fused = 2``: the latent seeds stay lo_vae_loss's) instead of the MSE
+        gradient the final conv's backward forms itself -- the hybrid step's reward-gradient objective."""
         vae = self.vae
         self._last_engine = eng
-        bargs = (images.data_ptr(), vae._flat.data_ptr(), eng.ws.data_ptr(), recon.data_ptr(), images.data_ptr(), 1, None, None, None,
-                 float(vae.loss_scale), self.grads.data_ptr(), st)
+        bargs = (images.data_ptr(), vae._flat.data_ptr(), eng.ws.data_ptr(), recon.data_ptr(), images.data_ptr(),
+                 1 if drecon is None else 2, _lib.ptr(drecon), None, None, float(vae.loss_scale), self.grads.data_ptr(), st)
         if self.grad_sync is not None and hasattr(self.grad_sync, "begin"):
             self._backward_data_parallel(eng, bargs)
         else:
@@ -420,9 +422,16 @@ class HybridStepper(VAEStepper):
 
     def __init__(self, vae: LunarisCoreVAE, teacher, teacher_lr: float = 1e-4, quality_weight: float = 0.5, reward_scale: float = 0.1,
                  semantic_weight: float = 0.5, baseline_momentum: float = 0.9, run_dead_teacher_call: bool = True,
-                 teacher_full_backward: bool = False, **kw):
+                 teacher_full_backward: bool = False, reward_grad_weight: float = 0.0, **kw):
         super().__init__(vae, **kw)
         self.teacher = teacher
+        # opt-in: the VAE also climbs the frozen (eval-mode) teacher's quality score, vae_loss -= weight * mean(q_eval) / accum with
+        # q_eval = quality_scores of the teacher in eval mode on recon, NOT detached; the teacher's parameters are constants in the term
+        # (DESIGN.md "Reward gradient").  0: the step makes exactly the calls it makes without the argument
+        self.reward_grad_weight = float(reward_grad_weight)
+        if self.reward_grad_weight < 0:
+            raise ValueError("reward_grad_weight must be >= 0")
+        self._rg = None                 # per-batch buffers of the reward pass (_reward_grad_seed)
         # the teacher trained "as documented" -- every parameter on the path of the teacher loss gets its gradient
         # (lo_teacher_full_backward: the reference with non-reentrant checkpoints) and its AdamW update; off = the reference as it
         # executes (gate + quality heads only)
@@ -435,6 +444,8 @@ class HybridStepper(VAEStepper):
         self.reward_state = torch.zeros(2, dtype=torch.float32, device=dev)     # baseline, initialised flag
         self.reward_out = torch.zeros(8, dtype=torch.float32, device=dev)
         self.adv_dev = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.reward_grad_out = torch.zeros(2, dtype=torch.float32, device=dev)   # reward term of vae_loss, mean(q_eval)
+        self.seed_coef = torch.zeros(1, dtype=torch.float32, device=dev)         # un-scaled MSE coefficient of d vae_loss / d recon
         self._t_ready = False
 
     def _teacher_setup(self, batch: int):
@@ -499,21 +510,26 @@ class HybridStepper(VAEStepper):
                                         float(self.accum), float(vae.loss_scale), self.losses.data_ptr(), st), "lo_vae_loss")
         if (batch_idx + 1) % self.accum == 0:
             flat = vae._flat
-            self._backward_and_exchange(eng, images, recon, st)     # data parallel: exchange overlapped with the backward
+            drecon = None
+            if self.reward_grad_weight > 0:
+                # the eval forward below overwrites what the teacher's own backward reads (the kept train-mode tensors in bws, the
+                # pooled features and logits in ws, the call's dropout stream): its gradients are taken first, its update stays last
+                self._teacher_grads(t, h, ws, recon, tout, st)
+                drecon = self._reward_grad_seed(t, eng, images, recon, st)
+            self._backward_and_exchange(eng, images, recon, st, drecon)     # data parallel: exchange overlapped with the backward
             lr = self.lr
             t_lr = cosine_warm_restarts_lr(self.teacher_base_lr, self.min_lr, self.t0, 2, self.opt_steps)
             self.opt_steps += 1
             self._clip_adamw(flat, lr, st, eng)
             self._observe_skipped_updates()
+            if drecon is None:
+                self._teacher_grads(t, h, ws, recon, tout, st)
             if self.teacher_full_backward:
-                self._teacher_full_update(t, recon, tout, t_lr, st)
+                self._teacher_full_update(t, recon, t_lr, st)
                 self.last = (recon, mu, logvar)
                 return recon, mu, logvar
             # teacher: gate + quality heads only (train_hybrid.py:891-904, 914, 922)
             b, e = self.t_range
-            _lib.check(_lib.lib.lo_teacher_heads_backward(h, t._flat.data_ptr(), ws.data_ptr(), tout["expert_weights"].data_ptr(),
-                                                          float(self.quality_weight) / float(self.accum), self._t_rows.data_ptr(),
-                                                          self.t_grads.data_ptr(), st), "lo_teacher_heads_backward")
             if self.grad_sync is not None:
                 self.grad_sync(self.t_grads[b:e])
             _lib.check(_lib.lib.lo_clip_adamw_step(t._flat[b:e].data_ptr(), self.t_grads[b:e].data_ptr(), self.t_m.data_ptr(),
@@ -525,16 +541,62 @@ class HybridStepper(VAEStepper):
         self.last = (recon, mu, logvar)
         return recon, mu, logvar
 
-    def _teacher_full_update(self, t, recon, tout, t_lr, st):
-        """teacher_loss.backward() + clip + AdamW with every teacher parameter live (train_hybrid.py:891-904, 914, 922 under
-        non-reentrant checkpoints): lo_teacher_full_backward on the evaluated images, then lo_teacher_clip_adamw_full."""
+    def _teacher_grads(self, t, h, ws, recon, tout, st):
+        """teacher_loss.backward() into ``self.t_grads`` (train_hybrid.py:891-904): the gate and the quality heads
+        (lo_teacher_heads_backward), or with ``teacher_full_backward`` every parameter on the loss path (lo_teacher_full_backward on
+        the evaluated images, under non-reentrant checkpoints).  Reads what the train-mode teacher(recon) of this step left."""
+        coef = float(self.quality_weight) / float(self.accum)
+        if not self.teacher_full_backward:
+            _lib.check(_lib.lib.lo_teacher_heads_backward(h, t._flat.data_ptr(), ws.data_ptr(), tout["expert_weights"].data_ptr(), coef,
+                                                          self._t_rows.data_ptr(), self.t_grads.data_ptr(), st), "lo_teacher_heads_backward")
+            return
         eng = t._engine(recon.shape[0])
         if getattr(eng, "bws", None) is None:
             eng.bws = _alloc_scratch(_lib.lib.lo_teacher_full_backward_bytes(eng.handle), recon.device)
         gscale = 64.0 * recon.shape[0] * 16384.0
         _lib.check(_lib.lib.lo_teacher_full_backward(eng.handle, recon.data_ptr(), t._flat.data_ptr(), eng.ws.data_ptr(), eng.bws.data_ptr(),
-                                                     tout["expert_weights"].data_ptr(), float(self.quality_weight) / float(self.accum),
+                                                     tout["expert_weights"].data_ptr(), coef,
                                                      gscale, self._t_rows.data_ptr(), self.t_grads.data_ptr(), st), "lo_teacher_full_backward")
+
+    def _reward_grad_seed(self, t, eng, images, recon, st) -> torch.Tensor:
+        """The reward pass of a ``reward_grad_weight`` step, after lo_vae_loss: the teacher in EVAL mode on recon (running statistics,
+        no dropout; lo_teacher_forward_keep_eval moves no byte of its state and not its dropout stream), the term's scalars
+        (lo_vae_reward_term), and its backward with no parameter gradients, whose last kernel stores the complete
+        d vae_loss / d recon = d(-w mean(q_eval) / accum) / d recon + c (recon - images) into the persistent seed buffer returned.
+        The fp16 activation gradients run at the operating point the eval-gradient tests pin (upstream rows of -2, gscale 2**20);
+        the objective's coefficient w / (8 B accum) multiplies the fp32 result."""
+        from .teacher import EVAL_GSCALE
+        B = recon.shape[0]
+        teng = t._engine(B)
+        if getattr(teng, "bws", None) is None:
+            teng.bws = _alloc_scratch(_lib.lib.lo_teacher_full_backward_bytes(teng.handle), recon.device)
+        if self._rg is None or self._rg["B"] != B:
+            f32 = dict(dtype=torch.float32, device=recon.device)
+            offs, elems = (C.c_size_t * 3)(), (C.c_size_t * 3)()
+            _lib.check(_lib.lib.lo_teacher_heads_saved(teng.handle, offs, elems), "lo_teacher_heads_saved")
+            self._rg = {"B": B, "q": torch.zeros(B, 4, **f32), "w": torch.zeros(B, t.num_experts, **f32),
+                        "emb": torch.zeros(2, B, t.embedding_dim, **f32), "sem": torch.zeros(B, 1, **f32),
+                        "up": torch.full((B, 4), -2.0, **f32), "seed": torch.zeros(B, 3, 128, 128, **f32), "saved": [int(o) for o in offs]}
+        rg = self._rg
+        tws = teng.ws.data_ptr()
+        _lib.check(_lib.lib.lo_teacher_forward_keep_eval(teng.handle, recon.data_ptr(), t._flat.data_ptr(), tws, teng.bws.data_ptr(),
+                                                         rg["q"].data_ptr(), rg["w"].data_ptr(), rg["emb"][0].data_ptr(), rg["emb"][1].data_ptr(),
+                                                         rg["sem"].data_ptr(), st), "lo_teacher_forward_keep_eval")
+        _lib.check(_lib.lib.lo_vae_reward_term(eng.handle, eng.ws.data_ptr(), rg["q"].data_ptr(), self.reward_grad_weight, float(self.accum),
+                                               float(self.vae.loss_scale), self.losses.data_ptr(), self.reward_grad_out.data_ptr(),
+                                               self.seed_coef.data_ptr(), st), "lo_vae_reward_term")
+        pf, pe, rq = (tws + o for o in rg["saved"])
+        _lib.check(_lib.lib.lo_teacher_eval_backward_seed(teng.handle, recon.data_ptr(), t._flat.data_ptr(), tws, teng.bws.data_ptr(), pf, pe, rq,
+                                                          rg["w"].data_ptr(), rg["up"].data_ptr(), None, float(EVAL_GSCALE),
+                                                          self._t_rows.data_ptr(), images.data_ptr(), self.seed_coef.data_ptr(),
+                                                          self.reward_grad_weight / (8.0 * B * float(self.accum)), rg["seed"].data_ptr(), st),
+                   "lo_teacher_eval_backward_seed")
+        return rg["seed"]
+
+    def _teacher_full_update(self, t, recon, t_lr, st):
+        """clip + AdamW with every teacher parameter live (train_hybrid.py:914, 922) on the gradients of `_teacher_grads`:
+        lo_teacher_clip_adamw_full."""
+        eng = t._engine(recon.shape[0])
         if self.grad_sync is not None:
             self.grad_sync(self.t_grads)
         _lib.check(_lib.lib.lo_teacher_clip_adamw_full(eng.handle, t._flat.data_ptr(), self.t_grads.data_ptr(), self.t_m.data_ptr(),
@@ -545,7 +607,8 @@ class HybridStepper(VAEStepper):
 
     def metrics(self) -> Dict[str, float]:
         """The 12 scalars of train_hybrid.py:929-942 (+ grad norm / lr); one host copy."""
-        v = torch.cat([self.losses, self.scratch[1024:1027], self.reward_out[:7], self.scratch[1027:1028], self._sync_fail_word()]).cpu().tolist()
+        v = torch.cat([self.losses, self.scratch[1024:1027], self.reward_out[:7], self.scratch[1027:1028], self._sync_fail_word(),
+                       self.reward_grad_out]).cpu().tolist()
         self._check_sync(v[15])
         recon, kl, vae_loss, pg = v[0:4]
         q_loss, sem_r, q_r, baseline, adv, t_loss, q_mean = v[7:14]
@@ -553,4 +616,5 @@ class HybridStepper(VAEStepper):
         return {"recon_loss": recon, "kl_loss": kl, "quality_loss": q_loss, "pg_loss": pg, "semantic_reward": sem_r,
                 "quality_reward": q_r, "baseline": baseline, "advantage": adv, "vae_loss": vae_loss, "teacher_loss": t_loss,
                 "total_loss": vae_loss + t_loss, "quality_scores": q_mean, "grad_norm": v[4], "clip_coef": v[5],
-                "grads_finite": v[6], "lr": self.lr, "skipped_steps": v[14], "loss_scale": self.vae.loss_scale}
+                "grads_finite": v[6], "lr": self.lr, "skipped_steps": v[14], "loss_scale": self.vae.loss_scale,
+                "reward_grad_loss": v[16], "eval_quality": v[17]}

@@ -12,7 +12,8 @@ What differs, deliberately: with the teacher on (the default flags) `HybridStepp
 as the reference executes it, teacher dropout 0.1 included (`--teacher_dropout`, a builder flag, defaults to the reference's
 constructor default; 0 selects the dropout-free fast path); `--feature_dim` 128 (default), 256 or 512 (README High-End recipe); with
 `--reward_scale 0 --quality_weight 0` (or `--vae_only`) the teacher is not run at all (its result cannot influence the
-VAE then) and the teacher-only metrics are reported as 0.  The reference's
+VAE then) and the teacher-only metrics are reported as 0; `--reward_grad_weight W` (a builder flag, default 0)
+also lets the VAE climb the frozen, eval-mode teacher's quality score on the undetached reconstruction.  The reference's
 defects are not inherited: no tensorboard hard dependency, no DataLoader timeout assertion, per-epoch average
 loss is a real number, checkpoints are written.  Launch one process per GPU with torch.distributed.run for DP.
 """
@@ -86,19 +87,35 @@ def build_parser() -> argparse.ArgumentParser:
                    help="train the teacher 'as documented' (SURVEY §8 F2): gradients and AdamW updates for the experts and the feature extractor too, "
                         "i.e. the reference with non-reentrant checkpoints (lunar_evaluator.py:194-197, 266-275, 411-414); off = the reference as it "
                         "executes (only the gate and the quality heads learn)")
+    p.add_argument("--reward_grad_weight", type=float, default=0.0,
+                   help="the VAE also climbs the frozen teacher's quality score: vae_loss -= W * mean(quality_scores of the teacher in eval mode "
+                        "on the reconstruction, not detached) / accumulation steps; the teacher's parameters are constants in the term and its "
+                        "own training is unchanged.  0 = off (the reference's objective).  Needs the teacher: not with --vae_only")
     return p
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    """The parser's result after the checks that need more than one flag (argument errors, not run-time ones)."""
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.reward_grad_weight < 0:
+        parser.error("--reward_grad_weight must be >= 0")
+    if args.vae_only and args.reward_grad_weight > 0:
+        parser.error("--reward_grad_weight needs the teacher (its eval-mode quality score is the reward), and --vae_only does not run one: "
+                     "drop --vae_only, or pass --reward_scale 0 --quality_weight 0 to keep the teacher's own objective out")
+    return args
 
 
 from lunaris_orion_amd.data import SpriteFeeder, SpriteShards, epoch_batches, steps_per_epoch as _steps_per_epoch   # noqa: E402
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     if args.vae_only:
         args.reward_scale, args.quality_weight = 0.0, 0.0
     if args.force_cpu:
         raise SystemExit("--force_cpu: this build has no CPU path (the CPU oracle under oracle/ is test infrastructure only)")
-    teacher_on = args.reward_scale != 0.0 or args.quality_weight != 0.0
+    teacher_on = args.reward_scale != 0.0 or args.quality_weight != 0.0 or args.reward_grad_weight > 0.0
     if teacher_on and args.feature_dim not in (128, 256, 512):
         raise SystemExit(f"--feature_dim {args.feature_dim} is not built: 128 (default), 256 and 512 (README High-End recipe) are")
     torch.manual_seed(args.seed)
@@ -155,7 +172,9 @@ def main(argv=None):
                                   dropout_rate=args.teacher_dropout).to("cuda").train()
         stepper = HybridStepper(vae, teacher, teacher_lr=args.teacher_lr, quality_weight=args.quality_weight, reward_scale=args.reward_scale,
                                 semantic_weight=args.semantic_weight, baseline_momentum=args.baseline_momentum,
-                                teacher_full_backward=args.teacher_full_backward, **common)
+                                teacher_full_backward=args.teacher_full_backward, reward_grad_weight=args.reward_grad_weight, **common)
+        if args.reward_grad_weight > 0:
+            log.info(f"reward gradient on: vae_loss -= {args.reward_grad_weight} * mean(eval-mode quality_scores(recon)) / accumulation steps")
         if args.teacher_full_backward:
             log.info("teacher full backward on: every teacher parameter on the loss path is trained (non-reentrant checkpoint semantics)")
         log.info(f"teacher on: LunarMoETeacher forward as executed by the reference, dropout_rate {args.teacher_dropout} in train mode"
