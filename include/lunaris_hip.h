@@ -362,6 +362,18 @@ int lo_vae_fp8_layers(const LoVae* h, int* layers);
  * (stage s, k = 0 strided conv, 1 / 2 ResBlock convs), 1 = raw decoder transposed-conv output, 2 = encoder stage (ResBlock)
  * output, 3 = decoder layer activation. */
 int lo_vae_debug_tensor(const LoVae* h, int which, int s, int k, size_t* byte_offset, int* dims4);
+/* ... and what a forward followed by a backward leaves in the workspace, for tests that check every layer in situ against a plain
+ * reference of that layer's own stored operands (tests/test_vae_insitu_gpu.py).  which 0..3 as above, and: 4 = activation
+ * (GroupNorm + Mish) of encoder conv (s, k), k = 0 / 1 (the ResBlock tail k = 2 writes the stage output, which = 2); 5 / 6 = saved
+ * GroupNorm statistics of encoder conv (s, k) / decoder layer s, FP32 [B][8][2] = (mean, rstd) per group (dims4 = B, 8, 2, 1);
+ * 7 / 8 = gradient wrt the raw conv output of encoder conv (s, k) / decoder layer s, multiplied by the backward's loss scale;
+ * 9 = the decoder's input h0 (B, 8, 8, 512); 10 = skip gradient s = 0..2 (B, 64 >> s, 64 >> s, 64 << s; loss scale as 7 / 8).
+ * elem_bytes: 2 = fp16, 4 = fp32.  (7, 0, 0) names where the LAST backward left the first conv's gradient. */
+int lo_vae_debug_tensor_ex(const LoVae* h, int which, int s, int k, size_t* byte_offset, int* dims4, int* elem_bytes);
+/* how the plan runs conv + GroupNorm layer (dec != 0: decoder layer s; else encoder conv (s, k)): info4 = { forward conv on e4m3
+ * operands (0 / 1; their count is lo_vae_fp8_layers), GroupNorm partial-sum rows per sample the conv epilogue writes, K splits of the
+ * forward conv, K splits of the data gradient (0 = one-launch kernel) }. */
+int lo_vae_layer_plan(const LoVae* h, int dec, int s, int k, int* info4);
 
 /* ---- LunarMoETeacher.forward as executed (lunar_evaluator.py:408-462; feature_dim 128) ---------------------------- */
 typedef struct LoTeacher LoTeacher;

@@ -16,7 +16,14 @@ const int kEncCh[5] = {3, 64, 128, 256, 512};
 const int kDecCh[5] = {512, 256, 128, 64, 32};
 }  // namespace
 
-static int setup_conv_layer(ConvLayer& c, int kind, int B, int H, int W, int Cin, int Cout, int p_w, Arena& ar, bool first) {
+// The ONE place that decides whether a layer's forward conv takes e4m3 operands in the fp8 mode: the e4m3 implicit GEMM covers the
+// geometry (Cin % 128 == 0, Cout % 64 == 0) and no patch-resident fp16 kernel owns the layer (the 128 -> 64 transposed conv)
+static bool layer_takes_f8(const LoGeom& gf) {
+  if (lo_conv_choose(gf, {.bias = true, .gn_partial = true, .f8 = true}).kernel == LO_CK_NONE) return false;
+  return lo_conv_choose(gf, {.bias = true, .gn_partial = true}).kernel != LO_CK_CONVT4_PATCH;
+}
+
+static int setup_conv_layer(ConvLayer& c, int kind, int B, int H, int W, int Cin, int Cout, int p_w, Arena& ar, bool first, bool fp8_fwd) {
   c.kind = kind; c.H = H; c.W = W; c.Cin = Cin; c.Cout = Cout;
   c.p_w = p_w; c.p_b = p_w + 1; c.p_gw = p_w + 2; c.p_gb = p_w + 3;
   if (!first) {
@@ -27,14 +34,10 @@ static int setup_conv_layer(ConvLayer& c, int kind, int B, int H, int W, int Cin
     LO_TRY(lo_make_geom(&c.gd, dk, B, c.Ho, c.Wo, Cout, Cin));
     c.o_wp_f = ar.take(lo_packed_weight_elems(c.gf) * 2);
     c.o_wp_d = ar.take(lo_packed_weight_elems(c.gd) * 2);
-    // conv_gn's fp16 launch (lo_vae_step.hip).
-    // TODO(fp8 mode, batch >= 64; owner: whoever next touches the fp8 forward -- before any other fp8 work): take c.MT and o_part
-    // from the use the layer really has.  A layer that plan_splitk_and_fp8 later moves to e4m3 operands runs lo_igemm_nt's tiles, and
-    // where lo_conv3x3_pp owns the fp16 form (the 128-channel ResBlock convs from batch 64 up, the 256-channel ones at batch 128)
-    // that launch writes {.f8 = true}.mts rows per sample, not these: it overruns o_part into o_stats / o_P1 of the same layer (both
-    // rewritten before they are read) and lo_gn_fwd misreads the row layout.  Kept as the parent had it here because the fix changes
-    // a workspace size and the fp8 results (profiles/conv_select_ab.md, disagreement 1).
-    c.MT = lo_conv_choose(c.gf, {.bias = true, .gn_partial = true}).mts;
+    // partial-sum rows per sample of conv_gn's launch (lo_vae_step.hip), asked with the use that launch really has: the e4m3 launch
+    // runs lo_igemm_nt's tiles whatever fp16 kernel owns the geometry (conv_gn checks the count against the launch's own answer)
+    c.f8 = fp8_fwd && layer_takes_f8(c.gf);
+    c.MT = lo_conv_choose(c.gf, {.bias = true, .gn_partial = true, .f8 = c.f8}).mts;
   } else {
     c.Ho = H / 2; c.Wo = W / 2;
     c.MT = 64;
@@ -99,18 +102,18 @@ static int plan_forward_buffers(LoVae* h, Arena& ar, int dec_first) {
   int pidx = 0;
   for (int s = 0; s < 4; ++s) {
     int ci = kEncCh[s], co = kEncCh[s + 1];
-    LO_TRY(setup_conv_layer(h->enc[s][0], LO_CONV3_S2, B, Hs, Hs, ci, co, pidx, ar, s == 0));
+    LO_TRY(setup_conv_layer(h->enc[s][0], LO_CONV3_S2, B, Hs, Hs, ci, co, pidx, ar, s == 0, h->fp8_fwd));
     pidx += 4;
     Hs /= 2;
-    LO_TRY(setup_conv_layer(h->enc[s][1], LO_CONV3_S1, B, Hs, Hs, co, co, pidx, ar, false));
+    LO_TRY(setup_conv_layer(h->enc[s][1], LO_CONV3_S1, B, Hs, Hs, co, co, pidx, ar, false, h->fp8_fwd));
     pidx += 4;
-    LO_TRY(setup_conv_layer(h->enc[s][2], LO_CONV3_S1, B, Hs, Hs, co, co, pidx, ar, false));
+    LO_TRY(setup_conv_layer(h->enc[s][2], LO_CONV3_S1, B, Hs, Hs, co, co, pidx, ar, false, h->fp8_fwd));
     pidx += 4;
     h->o_eout[s] = ar.take((size_t)B * Hs * Hs * co * 2);
   }
   Hs = 8;
   for (int s = 0; s < 4; ++s) {
-    LO_TRY(setup_conv_layer(h->dec[s], LO_CONVT4_S2, B, Hs, Hs, kDecCh[s], kDecCh[s + 1], dec_first + 4 * s, ar, false));
+    LO_TRY(setup_conv_layer(h->dec[s], LO_CONVT4_S2, B, Hs, Hs, kDecCh[s], kDecCh[s + 1], dec_first + 4 * s, ar, false, h->fp8_fwd));
     Hs *= 2;
   }
   for (int k = 0; k < 3; ++k) h->o_skipin[k] = ar.take((size_t)B * (64 >> k) * (64 >> k) * (64 << k) * 2);
@@ -195,10 +198,8 @@ static void plan_splitk_and_fp8(LoVae* h, Arena& ar) {
     });
   h->o_skslab = ar.take(slab > 0 ? slab : 256);
   if (!h->fp8_fwd) return;
-  auto enable = [&](ConvLayer& c, size_t* producer_copy) {
-    if (lo_conv_choose(c.gf, {.bias = true, .gn_partial = true, .f8 = true}).kernel == LO_CK_NONE) return;
-    if (lo_conv_choose(c.gf, {.bias = true, .gn_partial = true}).kernel == LO_CK_CONVT4_PATCH) return;   // a patch-resident fp16 kernel owns the layer (and its partial-sum rows)
-    c.f8 = true;
+  auto enable = [&](ConvLayer& c, size_t* producer_copy) {      // operands of an e4m3 layer: weights, scales, the producer's e4m3 copy of its input
+    if (!c.f8) return;      // decided with the layer's row count (setup_conv_layer)
     c.o_wp8 = ar.take(lo_packed_weight_elems(c.gf));
     c.o_wscale = ar.take((size_t)c.gf.n_phase * c.Cout * 4);
     if (!*producer_copy) *producer_copy = ar.take((size_t)B * c.H * c.W * c.Cin);
@@ -415,6 +416,45 @@ extern "C" int lo_vae_debug_tensor(const LoVae* h, int which, int s, int k, size
   LO_REQUIRE(c, "lo_vae_debug_tensor: unknown tensor kind %d", which);
   *byte_offset = which == 2 ? h->o_eout[s] : (which == 3 ? c->o_a : c->o_v);
   dims4[0] = h->B; dims4[1] = c->Ho; dims4[2] = c->Wo; dims4[3] = c->Cout;
+  return LO_OK;
+}
+
+// ... and what a forward plus a backward leave behind, for tests that check every layer IN SITU (each layer against a plain reference of
+// its own stored operands, at the batch size and with the kernels the step really selected; tests/test_vae_insitu_gpu.py).  which 0..3
+// as above; 4 = activation (GroupNorm + Mish) of encoder conv (s, k) -- k = 2 has none, the ResBlock tail writes the stage output (2);
+// 5 / 6 = saved GroupNorm statistics of encoder conv (s, k) / decoder layer s: FP32 [B][8][2] (mean, rstd), dims4 = B, 8, 2, 1;
+// 7 / 8 = gradient wrt the raw conv output of encoder conv (s, k) / decoder layer s (carries the backward's loss scale); 9 = the
+// decoder's input h0 [B][8][8][512]; 10 = skip gradient s (0: 64 x 64 x 64, 1: 32 x 32 x 128, 2: 16 x 16 x 256; loss scale as 7 / 8).
+// elem_bytes: 2 = fp16, 4 = fp32.  The first conv's dv has no fixed home (the ping-pong buffer, unless conv1's data gradient wrote it):
+// the answer for (7, 0, 0) holds for the backward that ran last.
+extern "C" int lo_vae_debug_tensor_ex(const LoVae* h, int which, int s, int k, size_t* byte_offset, int* dims4, int* elem_bytes) {
+  LO_REQUIRE(h && byte_offset && dims4 && elem_bytes && s >= 0 && s < 4 && k >= 0 && k < 3, "lo_vae_debug_tensor_ex: bad argument");
+  *elem_bytes = 2;
+  if (which >= 0 && which <= 3) return lo_vae_debug_tensor(h, which, s, k, byte_offset, dims4);
+  dims4[0] = h->B;
+  if (which == 9) { *byte_offset = h->o_h0; dims4[1] = dims4[2] = 8; dims4[3] = 512; return LO_OK; }
+  if (which == 10) {
+    LO_REQUIRE(s < 3, "lo_vae_debug_tensor_ex: three skip gradients, asked for %d", s);
+    *byte_offset = h->o_skipg[s]; dims4[1] = dims4[2] = 64 >> s; dims4[3] = 64 << s;
+    return LO_OK;
+  }
+  LO_REQUIRE(which >= 4 && which <= 8 && !(which == 4 && k == 2), "lo_vae_debug_tensor_ex: unknown tensor kind %d (k = %d)", which, k);
+  const ConvLayer* c = (which == 6 || which == 8) ? &h->dec[s] : &h->enc[s][k];
+  if (which == 5 || which == 6) {
+    *byte_offset = c->o_stats; *elem_bytes = 4;
+    dims4[1] = 8; dims4[2] = 2; dims4[3] = 1;
+    return LO_OK;
+  }
+  *byte_offset = which == 4 ? c->o_a : ((c == &h->enc[0][0] && !c->dv_done) ? h->o_G[3] : c->o_dv);
+  dims4[1] = c->Ho; dims4[2] = c->Wo; dims4[3] = c->Cout;
+  return LO_OK;
+}
+// how the plan runs conv + GroupNorm layer (dec ? up(s+1) : encoder conv (s, k)): info4 = forward conv on e4m3 operands (0 / 1),
+// GroupNorm partial-sum rows per sample its epilogue writes, K splits of the forward, of the data gradient (0 = one-launch kernel)
+extern "C" int lo_vae_layer_plan(const LoVae* h, int dec, int s, int k, int* info4) {
+  LO_REQUIRE(h && info4 && s >= 0 && s < 4 && k >= 0 && k < 3, "lo_vae_layer_plan: bad argument");
+  const ConvLayer& c = dec ? h->dec[s] : h->enc[s][k];
+  info4[0] = c.f8 ? 1 : 0; info4[1] = c.MT; info4[2] = c.sk_fwd; info4[3] = c.sk_dgrad;
   return LO_OK;
 }
 

@@ -41,17 +41,22 @@ static int conv_gn(LoVae* h, ConvLayer& c, const f16* in, const f16* other, f16*
     gf.fail = WSP(unsigned int, h->o_sync_fail);
   }
   int r_;
+  LoConvChoice ran{};       // the choice the launch made: its partial-sum rows are what lo_gn_forward reads below
   if (c.f8) {
     LO_REQUIRE(o_in8, "fp8 mode: no e4m3 copy of the input of a conv %d->%d", c.Cin, c.Cout);
     r_ = lo_conv_run_f8(c.gf, WSP(uint8_t, o_in8), WSP(uint8_t, c.o_wp8), WSP(float, c.o_wscale),
-                        {.bias = PRM(c.p_b), .out = WSP(f16, c.o_v), .gn_partial = WSP(float, c.o_part)}, st);
+                        {.bias = PRM(c.p_b), .out = WSP(f16, c.o_v), .gn_partial = WSP(float, c.o_part)}, st, &ran);
   } else {
     r_ = lo_conv_run(c.gf, {.in = in, .w = WSP(f16, c.o_wp_f), .bias = PRM(c.p_b), .out = WSP(f16, c.o_v),
-                            .gn_partial = fuse ? nullptr : WSP(float, c.o_part), .gf = fuse ? &gf : nullptr}, st);
+                            .gn_partial = fuse ? nullptr : WSP(float, c.o_part), .gf = fuse ? &gf : nullptr}, st, &ran);
   }
   tag.end();
   if (r_ != LO_OK) { if (fuse) --c.gnf_epoch; return r_; }
   if (fuse) return LO_OK;
+  // o_part is sized for c.MT rows per sample and lo_gn_fwd sums c.MT rows: a launch that wrote another count has overrun the one and
+  // is misread by the other (the plan and the launch asked lo_conv_choose with different uses)
+  LO_REQUIRE(ran.mts == c.MT, "conv + GroupNorm %dx%d %d->%d: the conv launch wrote %d partial-sum rows per sample, the plan has %d",
+             c.Ho, c.Wo, c.Cin, c.Cout, ran.mts, c.MT);
   return lo_gn_forward(vae_gn_layer(h, c, P, ws), {.partial = WSP(float, c.o_part), .MT = c.MT, .other = other, .mode = mode, .y = y,
                                                    .y8 = o_y8 ? WSP(uint8_t, o_y8) : nullptr}, st);
 }
@@ -368,8 +373,12 @@ int VaeBackward::dgrad(ConvLayer& c, int k, const f16* dv, f16* din, const f16* 
   const bool writes_dv = gbp && gbp->dv;      // this launch writes prod's dv: it carries prod's event
   LoProfTag tag("dgrad L%02d kind%d %dx%d %d->%d", k, c.kind, c.Ho, c.Wo, c.gd.Cin, c.gd.Cout);
   LoHandover ho(h, side && writes_dv);
-  int r_ = lo_conv_run(c.gd, {.in = dv, .w = WSP(f16, c.o_wp_d), .add_src = add_src, .out = din, .gb = gbp}, st);
+  LoConvChoice ran{};
+  int r_ = lo_conv_run(c.gd, {.in = dv, .w = WSP(f16, c.o_wp_d), .add_src = add_src, .out = din, .gb = gbp}, st, &ran);
   if (r_ != LO_OK) { if (writes_dv) { --prod->gba_epoch; prod->dv_done = false; } return r_; }
+  // the P1 (and P2) rows recorded above are the ones this launch wrote
+  if (gbp) LO_REQUIRE(ran.mts == prod->np1, "data gradient %dx%d %d->%d: the launch wrote %d P1 rows per sample, %d were recorded",
+                      c.Ho, c.Wo, c.gd.Cin, c.gd.Cout, ran.mts, prod->np1);
   if (writes_dv) { LO_TRY(ho.finish(st)); prod->ev_ready = ho.ev; }
   return LO_OK;
 }

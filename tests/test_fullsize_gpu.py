@@ -8,6 +8,7 @@ The oracle needs minutes per step at this size, so the full-size runs are tied t
   * the same step twice gives the same bits;
   * the teacher in eval mode (running statistics) is per-sample too: batch 64 vs batch 2; in train mode the sparse
     expert path must reproduce the dense path (every convolution in full) at batch 64.
+The direct tie at batch 64 is tests/test_vae_insitu_gpu.py: every layer of one batch-64 step against an fp64 reference of its own operands.
 Tolerances: mu / logvar / recon 5e-3 abs (different tile shapes are picked at different batch sizes, so
 the fp32 accumulation order differs), losses 1e-4 abs, gradients 2e-3 relative L2 (fp16 activations).
 """
