@@ -18,7 +18,7 @@ shortcut path.  ``quality_scores`` and ``expert_weights`` are autograd-visible o
 autograd node over the gate / quality-head parameters — the only ones that receive gradients in the reference, whose reentrant
 checkpoints cut the experts and the feature extractor from the graph — so the reference's own
 ``teacher_loss.backward()`` (train_hybrid.py:891-904) fills their ``.grad`` (``lo_teacher_heads_backward_ex``, replaying the
-call's dropout masks).  ``trainer.HybridStepper`` drives the same kernel directly (``lo_teacher_heads_backward``).  In-place
+call's dropout masks).  ``trainer.HybridStepper`` takes the same gradients in coefficient form (``heads_backward``).  In-place
 parameter updates by any optimizer are noticed through the parameters' version counters (re-pack before the next forward).
 
 ``feature_dim``: 128 (the CLI default: folded attention + constant-field shortcuts when no dropout is active) or 256 / 512 (the
@@ -33,7 +33,7 @@ from __future__ import annotations
 
 import ctypes as C
 import warnings
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -91,6 +91,18 @@ class ExpertBlock(nn.Module):
 # MI355X: both 4.168e-3 from it (16x16-pooled 8.5e-4) and 5.8e-5 from each other -- no underflow at 2**20, which keeps 16x more
 # headroom below fp16's maximum for larger upstream gradients, so the train path's value stays.
 EVAL_GSCALE = 2 ** 20
+TRAIN_GSCALE = 2 ** 20          # gscale of lo_teacher_full_backward_dx: upstream gradients of order 1 (normalised on the device first)
+
+
+def loss_gscale(B: int) -> float:
+    """gscale of the coefficient-form backward (upstream = coef / (4 B) per element): a power of two for power-of-two batches; any
+    positive value is exact enough."""
+    return 64.0 * B * 16384.0
+
+
+def _call(name: str, *args) -> None:
+    """One checked call of a library entry point, named once."""
+    _lib.check(getattr(_lib.lib, name)(*args), name)
 
 
 def _alloc_workspace(nbytes: int, device: torch.device) -> torch.Tensor:
@@ -99,19 +111,58 @@ def _alloc_workspace(nbytes: int, device: torch.device) -> torch.Tensor:
     return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
+class TeacherRoute(NamedTuple):
+    backward: str       # "heads" | "train_full" | "eval_full": which native backward the call's autograd node takes
+    want_dx: bool       # the images get their gradient
+    live_set: str       # "heads" (gate.*, quality_heads.*) | "path" (all but semantic_head, style_net, prompt_net)
+    warn: bool          # eval mode without eval_input_grad: the input requires grad and gets none
+
+
+def teacher_route(training: bool, eval_input_grad: bool, all_parameters_live: bool, x_requires_grad: bool) -> TeacherRoute:
+    """The one decision of `LunarMoETeacher.forward` (its docstring has the table); pure, no tensors."""
+    if not training and not eval_input_grad:
+        return TeacherRoute("heads", False, "path" if all_parameters_live else "heads", bool(x_requires_grad))
+    if not (all_parameters_live or x_requires_grad):
+        return TeacherRoute("heads", False, "heads", False)
+    return TeacherRoute("train_full" if training else "eval_full", bool(x_requires_grad), "path", False)
+
+
 class _TeacherEngine:
-    """Native plan + workspace for one batch size; the handle is released with the object (lo_teacher_destroy)."""
+    """Native plan + everything that is per batch size: the workspace, the full-backward scratch, the head-gradient rows and the engine's
+    constants (head gradient range, where a forward leaves the heads' inputs).  The handle is released with the object (lo_teacher_destroy)."""
 
     def __init__(self, model: "LunarMoETeacher", batch: int):
         h = C.c_void_p()
         _lib.check(_lib.lib.lo_teacher_create_ex(batch, model.num_experts, model.feature_dim, model.embedding_dim,
                                                  1 if model.mfma_precision == "fp8" else 0, C.byref(h)), "lo_teacher_create_ex")
-        self.handle = h
+        self.handle, self.batch = h, batch
         self.ws = _alloc_workspace(_lib.lib.lo_teacher_workspace_bytes(h), model._flat.device)
+        self.bws: Optional[torch.Tensor] = None
+        self._rows: Optional[torch.Tensor] = None
         self.packed_version = None
+        b, e = C.c_size_t(), C.c_size_t()
+        _call("lo_teacher_grad_range", h, C.byref(b), C.byref(e))
+        self.heads_range = (b.value, e.value)
+        offs, elems = (C.c_size_t * 3)(), (C.c_size_t * 3)()
+        _call("lo_teacher_heads_saved", h, offs, elems)
+        self.saved_offsets, self.saved_elems = tuple(int(o) for o in offs), tuple(int(n) for n in elems)
+        self._saved = tuple(self.ws[o:o + 4 * n].view(torch.float32) for o, n in zip(self.saved_offsets, self.saved_elems))
 
-    def __iter__(self):          # (handle, workspace, packed version): the tuple form older call sites unpack
-        return iter((self.handle, self.ws, self.packed_version))
+    def backward_scratch(self) -> torch.Tensor:
+        """`bws` of the kept forwards and the full backwards (26 GB at batch 64, feature_dim 128), made on first use."""
+        if self.bws is None:
+            self.bws = _alloc_workspace(_lib.lib.lo_teacher_full_backward_bytes(self.handle), self.ws.device)
+        return self.bws
+
+    def rows(self) -> torch.Tensor:
+        """The [B][heads range] fp32 scratch of every backward's head part, made on first use."""
+        if self._rows is None:
+            self._rows = _alloc_workspace(self.batch * (self.heads_range[1] - self.heads_range[0]) * 4, self.ws.device).view(torch.float32)
+        return self._rows
+
+    def saved_views(self):
+        """Where a forward leaves the heads' inputs in `ws`: pooled features, pooled expert features, pre-weighting logits."""
+        return self._saved
 
     def __del__(self):
         h, self.handle = getattr(self, "handle", None), None
@@ -123,81 +174,49 @@ class _TeacherEngine:
 
 
 class _TeacherFunction(torch.autograd.Function):
-    """LunarMoETeacher.forward as an autograd node over the gate / quality-head parameters (lunar_evaluator.py:353-373, 417,
-    431-432): differentiable outputs quality_scores [B,4] and expert_weights [B,E]; the embeddings and the semantic score are
-    returned without a graph (nothing in the reference step differentiates them).  The head inputs of THIS call (pooled
-    features, pre-weighting logits, dropout stream) are copied out of the workspace, so later forward calls do not disturb it.
-    want_dx (train mode, input requires grad): the full backward with the images' gradient (lo_teacher_full_backward_dx).
-    Eval mode with ``eval_input_grad=True`` and (want_dx or full_backward): the eval kept forward + lo_teacher_eval_backward (frozen
-    BatchNorm, no dropout); without a live parameter its flat gradient is NULL and only the images' gradient is computed."""
+    """LunarMoETeacher.forward as an autograd node (lunar_evaluator.py:353-373, 417, 431-432): differentiable outputs quality_scores
+    [B,4] and expert_weights [B,E]; the embeddings and the semantic score are returned without a graph (nothing in the reference
+    step differentiates them).  The `TeacherRoute` it is given names the forward it runs and the backward it takes.  The head inputs
+    of THIS call (pooled features, pre-weighting logits, dropout stream) are copied out of the workspace, so later forward calls do
+    not disturb it."""
+    FORWARD_MODE = {"heads": "auto", "train_full": "keep", "eval_full": "keep_eval"}
 
     @staticmethod
-    def forward(ctx, model, want_dx, x, *live):
-        frozen = (not model.training) and model.eval_input_grad and bool(model.all_parameters_live or want_dx)
-        full = ((model.all_parameters_live or want_dx) and model.training) or frozen
+    def forward(ctx, model, route, x, *live):
         xd = x.detach().contiguous().float()
-        out, eng, p, seed = model._native_forward(xd, keep=full and not frozen, keep_eval=frozen)
-        ctx.full, ctx.x, ctx.want_dx, ctx.x_dtype, ctx.frozen = full, (xd if full else None), bool(want_dx and full), x.dtype, frozen
-        offs, elems = (C.c_size_t * 3)(), (C.c_size_t * 3)()
-        _lib.check(_lib.lib.lo_teacher_heads_saved(eng.handle, offs, elems), "lo_teacher_heads_saved")
-        saved = [eng.ws[offs[i]:offs[i] + 4 * elems[i]].view(torch.float32).clone() for i in range(3)]
+        out, eng, p, seed = model._native_forward(xd, mode=_TeacherFunction.FORWARD_MODE[route.backward])
+        ctx.route, ctx.x, ctx.x_dtype = route, (xd if route.backward != "heads" else None), x.dtype
         ctx.model, ctx.eng, ctx.drop = model, eng, (p, seed)
         ctx.live_offsets = [(t.data_ptr() - model._flat.data_ptr()) // 4 for t in live]
         ctx.live_shapes = [t.shape for t in live]
-        ctx.save_for_backward(out["expert_weights"], *saved)
+        ctx.save_for_backward(out["expert_weights"], *(v.clone() for v in eng.saved_views()))
         ctx.mark_non_differentiable(out["style_embedding"], out["prompt_embedding"], out["semantic_score"])
         return out["quality_scores"], out["expert_weights"], out["style_embedding"], out["prompt_embedding"], out["semantic_score"]
 
     @staticmethod
     def backward(ctx, gq, gw, *_):
-        model, eng = ctx.model, ctx.eng
-        w, pooled_f, pooled_e, raw_q = ctx.saved_tensors
+        model, route = ctx.model, ctx.route
+        w, *saved = ctx.saved_tensors
         cont = lambda t: None if t is None else t.contiguous().float()
         gq, gw = cont(gq), cont(gw)
-        b, e = C.c_size_t(), C.c_size_t()
-        _lib.check(_lib.lib.lo_teacher_grad_range(eng.handle, C.byref(b), C.byref(e)), "lo_teacher_grad_range")
-        rows = _alloc_workspace(w.shape[0] * (e.value - b.value) * 4, w.device).view(torch.float32)
+        full = route.backward != "heads"
         # (the eval backward with no live parameter computes no parameter gradient: its flat buffer is NULL)
-        grads = torch.zeros_like(model._flat) if (ctx.live_offsets or not ctx.frozen) else None
-        dx = None
-        if ctx.full and (gq is not None or gw is not None):
-            # every parameter on the path (lo_teacher_full_backward_dx; dx = NULL unless the images require grad).  A foreign loss scale (GradScaler: 65 536) is divided out on the
-            # device first, like at the VAE's boundary, so that the fp16 activation gradients see upstream values of order 1
-            from .vae import _normalise_upstream
-            scr, (gq, gw) = _normalise_upstream([gq, gw])
-            B = w.shape[0]
-            if getattr(eng, "bws", None) is None:
-                eng.bws = _alloc_workspace(_lib.lib.lo_teacher_full_backward_bytes(eng.handle), w.device)
-            dx = torch.empty_like(ctx.x) if ctx.want_dx and ctx.needs_input_grad[2] else None
-            if ctx.frozen and (grads is not None or dx is not None):
-                _lib.check(_lib.lib.lo_teacher_eval_backward(eng.handle, ctx.x.data_ptr(), model._flat.data_ptr(), eng.ws.data_ptr(), eng.bws.data_ptr(),
-                                                             pooled_f.data_ptr(), pooled_e.data_ptr(), raw_q.data_ptr(), w.data_ptr(), _lib.ptr(gq),
-                                                             _lib.ptr(gw), float(EVAL_GSCALE), rows.data_ptr(), _lib.ptr(grads), _lib.ptr(dx),
-                                                             _lib.stream_ptr()), "lo_teacher_eval_backward")
-            elif not ctx.frozen:
-                _lib.check(_lib.lib.lo_teacher_full_backward_dx(
-                    eng.handle, ctx.x.data_ptr(), model._flat.data_ptr(), eng.ws.data_ptr(), eng.bws.data_ptr(),
-                    pooled_f.data_ptr(), pooled_e.data_ptr(), raw_q.data_ptr(), w.data_ptr(), _lib.ptr(gq),
-                    _lib.ptr(gw), float(ctx.drop[0]), int(ctx.drop[1]), float(2 ** 20), rows.data_ptr(),
-                    grads.data_ptr(), _lib.ptr(dx), _lib.stream_ptr()), "lo_teacher_full_backward_dx")
+        grads = torch.zeros_like(model._flat) if (ctx.live_offsets or route.backward != "eval_full") else None
+        dx = torch.empty_like(ctx.x) if full and route.want_dx and ctx.needs_input_grad[2] and (gq is not None or gw is not None) else None
+        if (gq is not None or gw is not None) and (grads is not None or dx is not None):
+            scr = None
+            if full:
+                # a foreign loss scale (GradScaler: 65 536) is divided out on the device first, like at the VAE's boundary, so that the
+                # fp16 activation gradients see upstream values of order 1
+                from .vae import _normalise_upstream
+                scr, (gq, gw) = _normalise_upstream([gq, gw])
+            model._native_backward(ctx.eng, route.backward, ctx.x, saved, w, gq, gw, ctx.drop, grads, dx)
             for t in (grads, dx):
-                if t is not None:
-                    _lib.check(_lib.lib.lo_grad_unscale_dev(t.data_ptr(), t.numel(), scr.data_ptr() + 4, None, _lib.stream_ptr()),
-                               "lo_grad_unscale_dev")
-        elif gq is not None or gw is not None:
-            _lib.check(_lib.lib.lo_teacher_heads_backward_ex(eng.handle, model._flat.data_ptr(), pooled_f.data_ptr(), pooled_e.data_ptr(),
-                                                             raw_q.data_ptr(), w.data_ptr(), _lib.ptr(gq), _lib.ptr(gw), float(ctx.drop[0]),
-                                                             int(ctx.drop[1]), rows.data_ptr(), grads.data_ptr(), _lib.stream_ptr()),
-                       "lo_teacher_heads_backward_ex")
-        out = []
-        for o, shape in zip(ctx.live_offsets, ctx.live_shapes):
-            n = 1
-            for d in shape:
-                n *= int(d)
-            out.append(grads[o:o + n].view(shape))
+                if scr is not None and t is not None:
+                    _call("lo_grad_unscale_dev", t.data_ptr(), t.numel(), scr.data_ptr() + 4, None, _lib.stream_ptr())
         if dx is not None and ctx.x_dtype != torch.float32:
             dx = dx.to(ctx.x_dtype)
-        return (None, None, dx) + tuple(out)
+        return (None, None, dx) + tuple(grads[o:o + shape.numel()].view(shape) for o, shape in zip(ctx.live_offsets, ctx.live_shapes))
 
 
 class LunarMoETeacher(nn.Module):
@@ -252,6 +271,7 @@ class LunarMoETeacher(nn.Module):
         self._engines: Dict[int, "_TeacherEngine"] = {}
         self._weights_version = 0
         self._drop_seed: Optional[int] = None     # counter-RNG stream of the dropout masks; derived at the first train-mode forward
+        self._drop_exact = False                   # set_dropout_stream(exact_next=True): the next call seed is the stream seed itself
         self.drop_calls = 0                        # train-mode forwards drawn from the stream so far (checkpointed)
         self.last_drop_seed: Optional[int] = None  # the seed the last forward ran with (tests regenerate its masks from it)
 
@@ -341,10 +361,10 @@ class LunarMoETeacher(nn.Module):
     def live_parameters(self):
         """The parameters that receive gradients in the reference step (gate.*, quality_heads.*: SURVEY §3.2), state_dict order; with
         ``LunarMoETeacher(full_backward=True)`` every parameter on the path of quality_scores / expert_weights (all but the style / prompt / semantic heads)."""
-        return self._live_parameters(False)
+        return self._live_parameters("path" if self.all_parameters_live else "heads")
 
-    def _live_parameters(self, full: bool):
-        if self.all_parameters_live or full:
+    def _live_parameters(self, live_set: str):
+        if live_set == "path":
             return [p for k, p in self.named_parameters() if k.split(".")[0] not in ("semantic_head", "style_net", "prompt_net")]
         return [p for k, p in self.named_parameters() if k.startswith("gate.") or k.startswith("quality_heads.")]
 
@@ -364,7 +384,7 @@ class LunarMoETeacher(nn.Module):
             self._drop_seed = (torch.initial_seed() * 0x9E3779B97F4A7C15 + 0xD209 + 0xD1B54A32D192ED03 * rank) & 0xFFFFFFFFFFFFFFFF
             from .vae import lcg_advance
             self._drop_seed = lcg_advance(self._drop_seed, self.drop_calls)     # > 0 after a resume: same stream, same position
-        if getattr(self, "_drop_exact", False):
+        if self._drop_exact:
             self._drop_exact = False
         else:
             self._drop_seed = (self._drop_seed * 6364136223846793005 + 1442695040888963407) & 0xFFFFFFFFFFFFFFFF
@@ -381,79 +401,83 @@ class LunarMoETeacher(nn.Module):
         """The side effects of `forward(x)` in train mode without its outputs: every BatchNorm layer sees the batch
         (running statistics, `num_batches_tracked`), the pooling of the last ExpertBlocks and the heads are skipped.
         `_process_batch` calls the teacher once this way (train_hybrid.py:853-855: the result is overwritten unused)."""
-        if not self.training:
-            return
-        if x.dim() != 4 or tuple(x.shape[1:]) != (3, 128, 128):
-            raise ValueError(f"expected input of shape [B, 3, 128, 128], got {tuple(x.shape)}")
-        x = x.detach().contiguous().float()
-        eng = self._engine(x.shape[0])
-        p = float(self.dropout_rate)
-        _lib.check(_lib.lib.lo_teacher_forward(eng.handle, x.data_ptr(), self._flat.data_ptr(), eng.ws.data_ptr(), 1, p,
-                                               self._next_drop_seed() if p > 0 else 0, None, None, None, None, None,
-                                               _lib.stream_ptr()), "lo_teacher_forward(statistics only)")
-        with torch.no_grad():
-            self._nbt += 1
+        if self.training:
+            self._native_forward(x, out=(None,) * 5)
 
-    def _native_forward(self, x: torch.Tensor, keep: bool = False, keep_eval: bool = False):
-        """One `lo_teacher_forward` (keep: `lo_teacher_forward_keep`, the train-mode forward of a step that ends in `full_backward`: every
-        block's output stays in the backward's scratch; keep_eval: `lo_teacher_forward_keep_eval`, the same for an eval-mode module and
-        `lo_teacher_eval_backward`, which moves no state).  Returns (outputs, engine, dropout_p, call seed)."""
+    def _native_forward(self, x: torch.Tensor, mode: str = "auto", out=None, keep: bool = False):
+        """The one call site of the three forwards.  mode "auto": `lo_teacher_forward` in the module's mode.  "keep" (spelled `keep=True`
+        by older callers): `lo_teacher_forward_keep`, the train-mode forward of a step that ends in a full backward -- every block's
+        output stays in the backward's scratch; on an eval-mode module it is "auto".  "keep_eval": `lo_teacher_forward_keep_eval`, the
+        same for `lo_teacher_eval_backward`; it runs at the running statistics without dropout whatever the module's mode and moves
+        no state (no BatchNorm counter, no dropout-seed draw).  out: caller-owned (quality_scores, expert_weights, style_embedding,
+        prompt_embedding, semantic_score), None entries passed as NULL (skipped).  Returns (outputs, engine, dropout_p, call seed)."""
         if x.dim() != 4 or tuple(x.shape[1:]) != (3, 128, 128):
             raise ValueError(f"expected input of shape [B, 3, 128, 128], got {tuple(x.shape)}")
         x = x.detach().contiguous().float()
         B = x.shape[0]
         eng = self._engine(B)
-        dev = x.device
-        q = torch.empty(B, 4, dtype=torch.float32, device=dev)
-        w = torch.empty(B, self.num_experts, dtype=torch.float32, device=dev)
-        st = torch.empty(B, self.embedding_dim, dtype=torch.float32, device=dev)
-        pr = torch.empty(B, self.embedding_dim, dtype=torch.float32, device=dev)
-        sem = torch.empty(B, 1, dtype=torch.float32, device=dev)
-        p = float(self.dropout_rate) if self.training else 0.0
-        seed = self._next_drop_seed() if p > 0 else 0
-        if keep and self.training:
-            if getattr(eng, "bws", None) is None:
-                eng.bws = _alloc_workspace(_lib.lib.lo_teacher_full_backward_bytes(eng.handle), dev)
-            _lib.check(_lib.lib.lo_teacher_forward_keep(eng.handle, x.data_ptr(), self._flat.data_ptr(), eng.ws.data_ptr(), eng.bws.data_ptr(),
-                                                        p, seed, q.data_ptr(), w.data_ptr(), st.data_ptr(), pr.data_ptr(), sem.data_ptr(),
-                                                        _lib.stream_ptr()), "lo_teacher_forward_keep")
-        elif keep_eval and not self.training:
-            if getattr(eng, "bws", None) is None:
-                eng.bws = _alloc_workspace(_lib.lib.lo_teacher_full_backward_bytes(eng.handle), dev)
-            _lib.check(_lib.lib.lo_teacher_forward_keep_eval(eng.handle, x.data_ptr(), self._flat.data_ptr(), eng.ws.data_ptr(), eng.bws.data_ptr(),
-                                                             q.data_ptr(), w.data_ptr(), st.data_ptr(), pr.data_ptr(), sem.data_ptr(),
-                                                             _lib.stream_ptr()), "lo_teacher_forward_keep_eval")
+        if out is None:
+            out = tuple(torch.empty(B, n, dtype=torch.float32, device=x.device) for n in (4, self.num_experts, self.embedding_dim, self.embedding_dim, 1))
+        outs = tuple(_lib.ptr(t) for t in out)
+        head = (eng.handle, x.data_ptr(), self._flat.data_ptr(), eng.ws.data_ptr())
+        if mode == "keep_eval":
+            p, seed = 0.0, 0
+            _call("lo_teacher_forward_keep_eval", *head, eng.backward_scratch().data_ptr(), *outs, _lib.stream_ptr())
         else:
-            _lib.check(_lib.lib.lo_teacher_forward(eng.handle, x.data_ptr(), self._flat.data_ptr(), eng.ws.data_ptr(), 1 if self.training else 0,
-                                                   p, seed, q.data_ptr(), w.data_ptr(), st.data_ptr(), pr.data_ptr(), sem.data_ptr(),
-                                                   _lib.stream_ptr()), "lo_teacher_forward")
-        if self.training:
-            with torch.no_grad():
-                self._nbt += 1
-        return ({"quality_scores": q, "expert_weights": w, "style_embedding": st, "prompt_embedding": pr,
-                 "semantic_score": sem, "feature_maps": None}, eng, p, seed)
+            p = float(self.dropout_rate) if self.training else 0.0
+            seed = self._next_drop_seed() if p > 0 else 0
+            if (keep or mode == "keep") and self.training:
+                _call("lo_teacher_forward_keep", *head, eng.backward_scratch().data_ptr(), p, seed, *outs, _lib.stream_ptr())
+            else:
+                _call("lo_teacher_forward", *head, 1 if self.training else 0, p, seed, *outs, _lib.stream_ptr())
+            if self.training:
+                with torch.no_grad():
+                    self._nbt += 1
+        q, w, st, pr, sem = out
+        return ({"quality_scores": q, "expert_weights": w, "style_embedding": st, "prompt_embedding": pr, "semantic_score": sem, "feature_maps": None}, eng, p, seed)
 
-    def full_backward(self, x: torch.Tensor, expert_weights: torch.Tensor, coef: float, gscale: float = None) -> torch.Tensor:
+    def _native_backward(self, eng, backward: str, x, saved, weights, gq, gw, drop, grads, dx, seed=None) -> None:
+        """The one call site of the four backwards that take upstream gradients gq [B,4] / gw [B,E] (either may be None).  backward: a
+        `TeacherRoute.backward`; saved: the forward's three head inputs (`eng.saved_views()` or clones of them); drop: the forward's
+        (dropout_p, call seed); grads: flat gradient in the layout of `_flat`, or None (eval_full: no parameter gradient is computed);
+        dx: the images' gradient or None.  seed = (target, coef, factor), eval_full only: `lo_teacher_eval_backward_seed`, whose last
+        kernel stores factor * dx + coef[0] * (x - target) into dx."""
+        heads = tuple(t.data_ptr() for t in saved) + (weights.data_ptr(), _lib.ptr(gq), _lib.ptr(gw))
+        rows, st = eng.rows().data_ptr(), _lib.stream_ptr()
+        if backward == "heads":
+            _call("lo_teacher_heads_backward_ex", eng.handle, self._flat.data_ptr(), *heads, float(drop[0]), int(drop[1]), rows, grads.data_ptr(), st)
+            return
+        trunk = (eng.handle, x.data_ptr(), self._flat.data_ptr(), eng.ws.data_ptr(), eng.backward_scratch().data_ptr()) + heads
+        if backward == "train_full":
+            _call("lo_teacher_full_backward_dx", *trunk, float(drop[0]), int(drop[1]), float(TRAIN_GSCALE), rows, grads.data_ptr(), _lib.ptr(dx), st)
+        elif seed is None:
+            _call("lo_teacher_eval_backward", *trunk, float(EVAL_GSCALE), rows, _lib.ptr(grads), _lib.ptr(dx), st)
+        else:
+            target, coef, factor = seed
+            _call("lo_teacher_eval_backward_seed", *trunk, float(EVAL_GSCALE), rows, target.data_ptr(), coef.data_ptr(), float(factor), dx.data_ptr(), st)
+
+    def full_backward(self, x: torch.Tensor, expert_weights: torch.Tensor, coef: float, gscale: float = None, out: torch.Tensor = None) -> torch.Tensor:
         """SURVEY §8 row F2, second half: gradients of ``coef * -mean(quality_scores)`` (train_hybrid.py:891-892, coef =
         quality_weight / accumulation steps) for EVERY teacher parameter on the loss path -- what ``teacher_loss.backward()``
         yields when the model's three ``checkpoint`` calls (lunar_evaluator.py:194-197, 266-275, 411-414) are non-reentrant.
         Must follow the train-mode ``forward(x)`` whose loss it differentiates (same images; the call's dropout stream and head
-        inputs are replayed).  Returns the flat gradient in the layout of ``self._flat`` (``parameter_grad_views`` slices it)."""
+        inputs are replayed).  Returns the flat gradient in the layout of ``self._flat`` (``parameter_grad_views`` slices it); with
+        ``out`` it is written there and nothing is allocated."""
         x = x.detach().contiguous().float()
-        B = x.shape[0]
-        eng = self._engine(B)
-        if getattr(eng, "bws", None) is None:
-            eng.bws = _alloc_workspace(_lib.lib.lo_teacher_full_backward_bytes(eng.handle), x.device)
-        b, e = C.c_size_t(), C.c_size_t()
-        _lib.check(_lib.lib.lo_teacher_grad_range(eng.handle, C.byref(b), C.byref(e)), "lo_teacher_grad_range")
-        rows = _alloc_workspace(B * (e.value - b.value) * 4, x.device).view(torch.float32)
-        grads = torch.empty_like(self._flat)
-        if gscale is None:
-            gscale = 64.0 * B * 16384.0                      # a power of two for power-of-two batches; any positive value is exact enough
-        _lib.check(_lib.lib.lo_teacher_full_backward(eng.handle, x.data_ptr(), self._flat.data_ptr(), eng.ws.data_ptr(), eng.bws.data_ptr(),
-                                                     expert_weights.contiguous().float().data_ptr(), float(coef), float(gscale), rows.data_ptr(),
-                                                     grads.data_ptr(), _lib.stream_ptr()), "lo_teacher_full_backward")
+        eng = self._engine(x.shape[0])
+        grads = torch.empty_like(self._flat) if out is None else out
+        _call("lo_teacher_full_backward", eng.handle, x.data_ptr(), self._flat.data_ptr(), eng.ws.data_ptr(), eng.backward_scratch().data_ptr(),
+              expert_weights.contiguous().float().data_ptr(), float(coef), float(loss_gscale(x.shape[0]) if gscale is None else gscale),
+              eng.rows().data_ptr(), grads.data_ptr(), _lib.stream_ptr())
         return grads
+
+    def heads_backward(self, expert_weights: torch.Tensor, coef: float, out: torch.Tensor) -> torch.Tensor:
+        """The same loss for the gate and the quality heads only, the parameters the reference step trains (lo_teacher_heads_backward:
+        reads what the last forward of this batch size left in the workspace), into the head range of ``out``."""
+        eng = self._engine(expert_weights.shape[0])
+        _call("lo_teacher_heads_backward", eng.handle, self._flat.data_ptr(), eng.ws.data_ptr(), expert_weights.data_ptr(), float(coef),
+              eng.rows().data_ptr(), out.data_ptr(), _lib.stream_ptr())
+        return out
 
     def parameter_grad_views(self, flat_grads: torch.Tensor):
         """name -> view of ``flat_grads`` (layout of ``self._flat``) for every parameter."""
@@ -462,37 +486,36 @@ class LunarMoETeacher(nn.Module):
 
     def forward(self, x: torch.Tensor, prompt_embedding=None):
         """lunar_evaluator.py:408-462.  ``prompt_embedding`` is accepted and ignored exactly like the reference does
-        (it is overwritten at :438 before any use).  With gradients enabled, ``quality_scores`` / ``expert_weights`` carry a
-        graph over the gate / quality-head parameters (see `_TeacherFunction`).
+        (it is overwritten at :438 before any use).  With gradients enabled, ``quality_scores`` / ``expert_weights`` carry a graph
+        (`_TeacherFunction`) whose backward `teacher_route` picks; ``full`` = the constructor's ``full_backward``, ``x_rg`` = the input
+        requires grad (the teacher as a differentiable reward: ``teacher(recon)`` with ``recon`` not detached):
 
-        An input that requires grad (the teacher as a differentiable reward: ``teacher(recon)`` with ``recon`` not detached) gets
-        ``x.grad`` in train mode.  There the reference's reentrant checkpoints see an input that requires grad and differentiate the
-        whole trunk, so this call takes the full backward whatever ``full_backward`` says: every parameter on the path of
-        ``quality_scores`` / ``expert_weights`` receives its gradient (the ones ``full_backward=True`` gives), through the kept forward
-        (its scratch is 26 GB at batch 64, feature_dim 128).  The BatchNorm running statistics move once per forward, as in the full
-        backward (nothing is recomputed); the reference's reentrant recompute would advance them a second time.  In eval mode an input
-        that requires grad gets no gradient (a UserWarning says so) and the outputs are those of the eval forward.
+        | mode  | ``eval_input_grad`` | backward                                        | ``x.grad`` | parameters with gradients           |
+        |-------|---------------------|-------------------------------------------------|------------|-------------------------------------|
+        | train | any                 | ``train_full`` if full or x_rg, else ``heads``  | if x_rg    | path if full or x_rg, else heads    |
+        | eval  | False               | ``heads``                                       | no, warns  | path if full (trunk: zeros), else heads |
+        | eval  | True                | ``eval_full`` if full or x_rg, else ``heads``   | if x_rg    | path if full or x_rg, else heads    |
 
-        ``LunarMoETeacher(eval_input_grad=True)`` in eval mode (the frozen reward model: deterministic, independent of the other
-        samples of the batch, running statistics untouched) mirrors the train-mode rule with every BatchNorm differentiated at its
-        running statistics and no dropout.  An input that requires grad gets ``x.grad`` without a warning (eval kept forward +
-        ``lo_teacher_eval_backward``) and every parameter on the path that requires grad its gradient, whatever ``full_backward``
-        says; if none does (``teacher.requires_grad_(False)``) no parameter gradient is computed at all and ``x.grad`` has the same
-        bits.  An input that does not require grad with ``full_backward=True``: the same backward without the images' gradient
-        (fine-tuning with frozen BatchNorm); with ``full_backward=False``: the default eval forward and the heads-only backward.  The
-        outputs of such a call come from the plain-form eval forward: they differ from the default (folded at feature_dim 128) eval
-        forward at the fp16 rounding level, like any two paths of ``lo_teacher_forward``.  Running statistics, ``num_batches_tracked``
-        and the dropout stream (``drop_calls``) do not move; the three other outputs stay non-differentiable."""
+        heads = ``gate.*``, ``quality_heads.*`` (``lo_teacher_heads_backward_ex``: the reference as it executes); path = all
+        but the semantic / style / prompt heads.  No graph at all when none of those parameters requires grad and ``x.grad`` is not due.
+        ``train_full`` (kept forward + ``lo_teacher_full_backward_dx``; its scratch is 26 GB at batch 64, feature_dim 128): the reference's
+        reentrant checkpoints see an input that requires grad and differentiate the whole trunk, whatever ``full_backward`` says.  The
+        BatchNorm running statistics move once per forward (nothing is recomputed); the reference's reentrant recompute would advance
+        them a second time.  ``eval_full`` (eval kept forward + ``lo_teacher_eval_backward``; the frozen reward model: deterministic,
+        independent of the other samples of the batch): every BatchNorm differentiated at its running statistics, no dropout; running
+        statistics, ``num_batches_tracked`` and the dropout stream (``drop_calls``) do not move.  If no parameter on the path requires
+        grad (``teacher.requires_grad_(False)``) no parameter gradient is computed at all and ``x.grad`` has the same bits.  Its outputs
+        come from the plain-form eval forward: they differ from the default (folded at feature_dim 128) eval forward at the fp16
+        rounding level, like any two paths of ``lo_teacher_forward``.  The three other outputs stay non-differentiable."""
         self._ensure_flat()
         if torch.is_grad_enabled():
-            ev = self.eval_input_grad and not self.training
-            want_dx = bool(x.requires_grad) and (self.training or ev)
-            if x.requires_grad and not self.training and not ev:
+            route = teacher_route(self.training, self.eval_input_grad, self.all_parameters_live, x.requires_grad)
+            if route.warn:
                 warnings.warn("LunarMoETeacher in eval mode: the input requires grad but gets no gradient (its input gradient is built "
                               "for train mode only); outputs are the eval-mode forward's", UserWarning, stacklevel=2)
-            live = [p for p in self._live_parameters(want_dx) if p.requires_grad]
-            if live or want_dx:
-                q, w, st, pr, sem = _TeacherFunction.apply(self, want_dx, x if want_dx else x.detach(), *live)
+            live = [p for p in self._live_parameters(route.live_set) if p.requires_grad]
+            if live or route.want_dx:
+                q, w, st, pr, sem = _TeacherFunction.apply(self, route, x if route.want_dx else x.detach(), *live)
                 return {"quality_scores": q, "expert_weights": w, "style_embedding": st, "prompt_embedding": pr,
                         "semantic_score": sem, "feature_maps": None}
         return self._native_forward(x)[0]

@@ -28,8 +28,8 @@ from .vae import LunarisCoreVAE
 
 
 def _alloc_scratch(nbytes: int, device: torch.device) -> torch.Tensor:
-    """Device memory the steppers hand to kernels as pure scratch (the head backward's `rows`, the teacher's full-backward `bws`):
-    contents unspecified.  The poisoned-workspace tests swap this function; state the kernels accumulate into (the 1028-float
+    """Device memory the steppers hand to kernels as pure scratch (the Gram scratch of the data-parallel norm; the teacher's scratch is
+    its engine's): contents unspecified.  The poisoned-workspace tests swap this function; state the kernels accumulate into (the 1028-float
     optimizer scratch with its skipped-update counter, AdamW moments) is zero-initialised where it is created and is not scratch."""
     return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
@@ -446,39 +446,32 @@ class HybridStepper(VAEStepper):
         self.adv_dev = torch.zeros(1, dtype=torch.float32, device=dev)
         self.reward_grad_out = torch.zeros(2, dtype=torch.float32, device=dev)   # reward term of vae_loss, mean(q_eval)
         self.seed_coef = torch.zeros(1, dtype=torch.float32, device=dev)         # un-scaled MSE coefficient of d vae_loss / d recon
-        self._t_ready = False
+        self._t_ready = False                    # t_range, t_grads, t_m, t_v, t_scratch exist (_teacher_setup)
+        self._pending_teacher_opt = None         # a checkpoint's teacher optimizer state until then (hostside.restore_checkpoint)
+        self.last_teacher_out = None             # outputs of the last train-mode teacher(recon)
 
-    def _teacher_setup(self, batch: int):
+    def _teacher_setup(self, batch: int) -> None:
+        """What the stepper owns of the teacher's update, made at the first step: the flat gradient, AdamW moments over `t_range`, the
+        optimizer scratch.  Everything per batch size (workspaces, rows, ranges) is the teacher engine's."""
+        if self._t_ready:
+            return
         t = self.teacher
-        h, ws, _ = t._engine(batch)
-        b, e = C.c_size_t(), C.c_size_t()
-        _lib.check(_lib.lib.lo_teacher_grad_range(h, C.byref(b), C.byref(e)), "lo_teacher_grad_range")
-        if not self._t_ready:
-            self.t_heads_range = (b.value, e.value)
-            self.t_range = (0, t._flat.numel()) if self.teacher_full_backward else (b.value, e.value)
-            b, e = C.c_size_t(self.t_range[0]), C.c_size_t(self.t_range[1])
-            n = e.value - b.value
-            self.t_grads = torch.zeros_like(t._flat)
-            self.t_m = torch.zeros(n, dtype=torch.float32, device=t._flat.device)
-            self.t_v = torch.zeros(n, dtype=torch.float32, device=t._flat.device)
-            self.t_scratch = torch.zeros(1028, dtype=torch.float32, device=t._flat.device)
-            self._t_ready = True
-            pending = getattr(self, "_pending_teacher_opt", None)
-            if pending is not None:                       # optimizer state of a checkpoint (hostside.restore_checkpoint)
-                from collections import OrderedDict
-                from .hostside import flat_offsets, load_adamw_state_dict
-                tp = OrderedDict(t.named_parameters())
-                offs = flat_offsets(tp, t._flat)
-                rel = {k: (o - b.value if b.value <= o < e.value else 0) for k, o in offs.items()}
-                names = list(tp.keys())
-                live = {"state": {i: st for i, st in pending.get("state", {}).items() if b.value <= offs[names[int(i)]] < e.value}}
-                load_adamw_state_dict(live, tp, self.t_m, self.t_v, rel)
-                self._pending_teacher_opt = None
-        hb, he = self.t_heads_range
-        rows = getattr(self, "_t_rows", None)
-        if rows is None or rows.numel() != batch * (he - hb):
-            self._t_rows = _alloc_scratch(batch * (he - hb) * 4, t._flat.device).view(torch.float32)
-        return h, ws
+        b, e = self.t_range = (0, t._flat.numel()) if self.teacher_full_backward else t._engine(batch).heads_range
+        self.t_grads = torch.zeros_like(t._flat)
+        self.t_m = torch.zeros(e - b, dtype=torch.float32, device=t._flat.device)
+        self.t_v = torch.zeros(e - b, dtype=torch.float32, device=t._flat.device)
+        self.t_scratch = torch.zeros(1028, dtype=torch.float32, device=t._flat.device)
+        self._t_ready = True
+        pending, self._pending_teacher_opt = self._pending_teacher_opt, None
+        if pending is not None:                       # optimizer state of a checkpoint (hostside.restore_checkpoint)
+            from collections import OrderedDict
+            from .hostside import flat_offsets, load_adamw_state_dict
+            tp = OrderedDict(t.named_parameters())
+            offs = flat_offsets(tp, t._flat)
+            rel = {k: (o - b if b <= o < e else 0) for k, o in offs.items()}
+            names = list(tp.keys())
+            live = {"state": {i: st for i, st in pending.get("state", {}).items() if b <= offs[names[int(i)]] < e}}
+            load_adamw_state_dict(live, tp, self.t_m, self.t_v, rel)
 
     def step(self, images: torch.Tensor, batch_idx: int = 0, eps: Optional[torch.Tensor] = None, **_):
         vae, t = self.vae, self.teacher
@@ -490,9 +483,9 @@ class HybridStepper(VAEStepper):
             t.update_statistics_only(images)            # train_hybrid.py:853-855 (side effects only)
         # train_hybrid.py:865 (no autograd node: the head gradients are taken below).  Full-backward mode: the plain forward that keeps
         # every block's output for lo_teacher_full_backward (only on the micro-batch whose gradients are used)
-        tout = t._native_forward(recon, keep=self.teacher_full_backward and (batch_idx + 1) % self.accum == 0)[0]
+        tout = t._native_forward(recon, mode="keep" if self.teacher_full_backward and (batch_idx + 1) % self.accum == 0 else "auto")[0]
         self.last_teacher_out = tout
-        h, ws = self._teacher_setup(B)
+        self._teacher_setup(B)
         q_rows, s_rows, n_rows = tout["quality_scores"], tout["semantic_score"], B
         if self.grad_sync is not None and (getattr(self.grad_sync, "world", 1) > 1 or getattr(self.grad_sync, "force", False)):
             # data parallel: the baseline / advantage are functions of the batch means only (train_hybrid.py:870-883);
@@ -514,7 +507,7 @@ class HybridStepper(VAEStepper):
             if self.reward_grad_weight > 0:
                 # the eval forward below overwrites what the teacher's own backward reads (the kept train-mode tensors in bws, the
                 # pooled features and logits in ws, the call's dropout stream): its gradients are taken first, its update stays last
-                self._teacher_grads(t, h, ws, recon, tout, st)
+                self._teacher_grads(t, recon, tout)
                 drecon = self._reward_grad_seed(t, eng, images, recon, st)
             self._backward_and_exchange(eng, images, recon, st, drecon)     # data parallel: exchange overlapped with the backward
             lr = self.lr
@@ -523,7 +516,7 @@ class HybridStepper(VAEStepper):
             self._clip_adamw(flat, lr, st, eng)
             self._observe_skipped_updates()
             if drecon is None:
-                self._teacher_grads(t, h, ws, recon, tout, st)
+                self._teacher_grads(t, recon, tout)
             if self.teacher_full_backward:
                 self._teacher_full_update(t, recon, t_lr, st)
                 self.last = (recon, mu, logvar)
@@ -541,56 +534,37 @@ class HybridStepper(VAEStepper):
         self.last = (recon, mu, logvar)
         return recon, mu, logvar
 
-    def _teacher_grads(self, t, h, ws, recon, tout, st):
+    def _teacher_grads(self, t, recon, tout) -> None:
         """teacher_loss.backward() into ``self.t_grads`` (train_hybrid.py:891-904): the gate and the quality heads
-        (lo_teacher_heads_backward), or with ``teacher_full_backward`` every parameter on the loss path (lo_teacher_full_backward on
-        the evaluated images, under non-reentrant checkpoints).  Reads what the train-mode teacher(recon) of this step left."""
+        (`heads_backward`), or with ``teacher_full_backward`` every parameter on the loss path (`full_backward` on the evaluated images,
+        under non-reentrant checkpoints).  Reads what the train-mode teacher(recon) of this step left."""
         coef = float(self.quality_weight) / float(self.accum)
-        if not self.teacher_full_backward:
-            _lib.check(_lib.lib.lo_teacher_heads_backward(h, t._flat.data_ptr(), ws.data_ptr(), tout["expert_weights"].data_ptr(), coef,
-                                                          self._t_rows.data_ptr(), self.t_grads.data_ptr(), st), "lo_teacher_heads_backward")
-            return
-        eng = t._engine(recon.shape[0])
-        if getattr(eng, "bws", None) is None:
-            eng.bws = _alloc_scratch(_lib.lib.lo_teacher_full_backward_bytes(eng.handle), recon.device)
-        gscale = 64.0 * recon.shape[0] * 16384.0
-        _lib.check(_lib.lib.lo_teacher_full_backward(eng.handle, recon.data_ptr(), t._flat.data_ptr(), eng.ws.data_ptr(), eng.bws.data_ptr(),
-                                                     tout["expert_weights"].data_ptr(), coef,
-                                                     gscale, self._t_rows.data_ptr(), self.t_grads.data_ptr(), st), "lo_teacher_full_backward")
+        if self.teacher_full_backward:
+            t.full_backward(recon, tout["expert_weights"], coef, out=self.t_grads)
+        else:
+            t.heads_backward(tout["expert_weights"], coef, out=self.t_grads)
 
     def _reward_grad_seed(self, t, eng, images, recon, st) -> torch.Tensor:
         """The reward pass of a ``reward_grad_weight`` step, after lo_vae_loss: the teacher in EVAL mode on recon (running statistics,
-        no dropout; lo_teacher_forward_keep_eval moves no byte of its state and not its dropout stream), the term's scalars
-        (lo_vae_reward_term), and its backward with no parameter gradients, whose last kernel stores the complete
-        d vae_loss / d recon = d(-w mean(q_eval) / accum) / d recon + c (recon - images) into the persistent seed buffer returned.
+        no dropout; `_native_forward(mode="keep_eval")` moves no byte of its state and not its dropout stream), the term's scalars
+        (lo_vae_reward_term), and its backward with no parameter gradients (`_native_backward` with a seed), whose last kernel stores the
+        complete d vae_loss / d recon = d(-w mean(q_eval) / accum) / d recon + c (recon - images) into the persistent seed buffer returned.
         The fp16 activation gradients run at the operating point the eval-gradient tests pin (upstream rows of -2, gscale 2**20);
         the objective's coefficient w / (8 B accum) multiplies the fp32 result."""
-        from .teacher import EVAL_GSCALE
         B = recon.shape[0]
-        teng = t._engine(B)
-        if getattr(teng, "bws", None) is None:
-            teng.bws = _alloc_scratch(_lib.lib.lo_teacher_full_backward_bytes(teng.handle), recon.device)
         if self._rg is None or self._rg["B"] != B:
             f32 = dict(dtype=torch.float32, device=recon.device)
-            offs, elems = (C.c_size_t * 3)(), (C.c_size_t * 3)()
-            _lib.check(_lib.lib.lo_teacher_heads_saved(teng.handle, offs, elems), "lo_teacher_heads_saved")
-            self._rg = {"B": B, "q": torch.zeros(B, 4, **f32), "w": torch.zeros(B, t.num_experts, **f32),
-                        "emb": torch.zeros(2, B, t.embedding_dim, **f32), "sem": torch.zeros(B, 1, **f32),
-                        "up": torch.full((B, 4), -2.0, **f32), "seed": torch.zeros(B, 3, 128, 128, **f32), "saved": [int(o) for o in offs]}
+            emb = torch.zeros(2, B, t.embedding_dim, **f32)
+            self._rg = {"B": B, "q": torch.zeros(B, 4, **f32), "w": torch.zeros(B, t.num_experts, **f32), "emb": emb,
+                        "sem": torch.zeros(B, 1, **f32), "up": torch.full((B, 4), -2.0, **f32), "seed": torch.zeros(B, 3, 128, 128, **f32)}
+            self._rg["out"] = (self._rg["q"], self._rg["w"], emb[0], emb[1], self._rg["sem"])
         rg = self._rg
-        tws = teng.ws.data_ptr()
-        _lib.check(_lib.lib.lo_teacher_forward_keep_eval(teng.handle, recon.data_ptr(), t._flat.data_ptr(), tws, teng.bws.data_ptr(),
-                                                         rg["q"].data_ptr(), rg["w"].data_ptr(), rg["emb"][0].data_ptr(), rg["emb"][1].data_ptr(),
-                                                         rg["sem"].data_ptr(), st), "lo_teacher_forward_keep_eval")
+        teng = t._native_forward(recon, mode="keep_eval", out=rg["out"])[1]
         _lib.check(_lib.lib.lo_vae_reward_term(eng.handle, eng.ws.data_ptr(), rg["q"].data_ptr(), self.reward_grad_weight, float(self.accum),
                                                float(self.vae.loss_scale), self.losses.data_ptr(), self.reward_grad_out.data_ptr(),
                                                self.seed_coef.data_ptr(), st), "lo_vae_reward_term")
-        pf, pe, rq = (tws + o for o in rg["saved"])
-        _lib.check(_lib.lib.lo_teacher_eval_backward_seed(teng.handle, recon.data_ptr(), t._flat.data_ptr(), tws, teng.bws.data_ptr(), pf, pe, rq,
-                                                          rg["w"].data_ptr(), rg["up"].data_ptr(), None, float(EVAL_GSCALE),
-                                                          self._t_rows.data_ptr(), images.data_ptr(), self.seed_coef.data_ptr(),
-                                                          self.reward_grad_weight / (8.0 * B * float(self.accum)), rg["seed"].data_ptr(), st),
-                   "lo_teacher_eval_backward_seed")
+        t._native_backward(teng, "eval_full", recon, teng.saved_views(), rg["w"], rg["up"], None, (0.0, 0), None, rg["seed"],
+                           seed=(images, self.seed_coef, self.reward_grad_weight / (8.0 * B * float(self.accum))))
         return rg["seed"]
 
     def _teacher_full_update(self, t, recon, t_lr, st):

@@ -83,7 +83,8 @@ def test_teacher_head_gradients_match_autograd_of_oracle():
     m = m.to("cuda").train()
     x = R.normalise_sprites(R.closed_form_sprites(B))
     out = m(x.cuda())
-    h, ws, _ = m._engine(B)
+    eng = m._engine(B)
+    h, ws = eng.handle, eng.ws
     b, e = C.c_size_t(), C.c_size_t()
     _lib.check(_lib.lib.lo_teacher_grad_range(h, C.byref(b), C.byref(e)))
     n = e.value - b.value
@@ -394,7 +395,8 @@ def test_teacher_head_gradients_with_dropout_match_autograd_of_oracle():
     m.set_dropout_stream(seed, exact_next=True)
     x = R.normalise_sprites(R.closed_form_sprites(B))
     out = m(x.cuda())
-    h, ws, _ = m._engine(B)
+    eng = m._engine(B)
+    h, ws = eng.handle, eng.ws
     b, e = C.c_size_t(), C.c_size_t()
     _lib.check(_lib.lib.lo_teacher_grad_range(h, C.byref(b), C.byref(e)))
     rows = torch.empty(B * (e.value - b.value), device="cuda")
@@ -506,7 +508,8 @@ def test_wide_teacher_head_gradients_and_hybrid_step():
     m.set_dropout_stream(seed, exact_next=True)
     x = R.normalise_sprites(R.closed_form_sprites(B))
     out = m(x.cuda())
-    h, ws, _ = m._engine(B)
+    eng = m._engine(B)
+    h, ws = eng.handle, eng.ws
     b, e = C.c_size_t(), C.c_size_t()
     _lib.check(_lib.lib.lo_teacher_grad_range(h, C.byref(b), C.byref(e)))
     rows = torch.empty(B * (e.value - b.value), device="cuda")
