@@ -374,6 +374,28 @@ int lo_vae_debug_tensor_ex(const LoVae* h, int which, int s, int k, size_t* byte
  * operands (0 / 1; their count is lo_vae_fp8_layers), GroupNorm partial-sum rows per sample the conv epilogue writes, K splits of the
  * forward conv, K splits of the data gradient (0 = one-launch kernel) }. */
 int lo_vae_layer_plan(const LoVae* h, int dec, int s, int k, int* info4);
+/* ... and every launch of that layer in the fused single-call step (lo_vae_forward; lo_vae_backward with fused = 1), as the executor
+ * will make it: each field is the answer of the chooser the executor asks, with the use the executor asks it with, and the executor
+ * refuses (-3) a launch whose own choice differs.  Needs no device.  info[0 .. LO_VAE_PLAN_FIELDS), cap >= LO_VAE_PLAN_FIELDS:
+ *    0.. 8  forward conv on fp16 operands: kernel (0 none -- the layer's forward runs on e4m3 operands, or it is the first conv, which
+ *           has a kernel of its own; 1 lo_igemm_nt, 2 its split-K form, 3 its e4m3 form, 4 lo_conv3x3_pp, 5 / 6 the patch-resident
+ *           transposed conv / stride-2 data gradient), bm, bn, bk (lo_igemm_nt tile; lo_conv3x3_pp: bn channels), th, tw (lo_conv3x3_pp
+ *           pixel tile), partial-sum rows per sample, n tiles, K splits (0 = one launch)
+ *    9..17  the same for the forward conv on e4m3 operands (all 0: the layer takes none)
+ *   18..26  the same for the data gradient (all 0: the first conv, whose input gradient the step does not form)
+ *   27      that launch also applies the GroupNorm backward of the layer before it in its epilogue (0 / 1)
+ *   28..30  GroupNorm backward: form (0 slab sum + one pass, 1 apply only -- the consuming layer's data gradient has reduced, 2 one
+ *           pass, 3 reduce + apply; -1: no launch of its own, the consuming layer's data gradient applied it), rows of P1, of P2 per sample
+ *   31..38  weight gradient: kernel (0 lo_wgrad3x3_mt, 1 lo_wgrad_s2_mt, 2 lo_wgrad_tn; -1: the first conv's own), chunk width tw,
+ *           transposed-conv form, splits launched, slabs provided, K units per split, direct (no slab, no reduce), reduce form
+ *           (0 none, 1 rows, 2 transposed conv, 3 scatter)
+ *   39      K units of the whole weight gradient: the last split has units - (splits - 1) * units per split of them */
+#define LO_VAE_PLAN_FIELDS 40
+int lo_vae_layer_plan_ex(const LoVae* h, int dec, int s, int k, int* info, int cap);
+/* A handle made in a process without a device plans no launch whose workgroups wait for each other, which every device does plan:
+ * this tells such a handle how many compute units to plan for (256: MI355X, SPX), so that lo_vae_layer_plan_ex answers as it would
+ * there.  -3 on a handle that was made on a device. */
+int lo_vae_plan_assume_cus(LoVae* h, int n_cu);
 
 /* ---- LunarMoETeacher.forward as executed (lunar_evaluator.py:408-462; feature_dim 128) ---------------------------- */
 typedef struct LoTeacher LoTeacher;

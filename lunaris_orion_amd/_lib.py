@@ -131,6 +131,8 @@ SIGNATURES = {
     "lo_vae_debug_tensor": (i32, [vp, i32, i32, i32, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "lo_vae_debug_tensor_ex": (i32, [vp, i32, i32, i32, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "lo_vae_layer_plan": (i32, [vp, i32, i32, i32, C.POINTER(C.c_int)]),
+    "lo_vae_layer_plan_ex": (i32, [vp, i32, i32, i32, C.POINTER(C.c_int), i32]),
+    "lo_vae_plan_assume_cus": (i32, [vp, i32]),
     "lo_dp_pack_f16": (i32, [f32p, vp, sz, flt, vp]),
     "lo_dp_unpack_f16": (i32, [vp, f32p, sz, flt, vp]),
     "lo_dp_unpack_f16_sumsq": (i32, [vp, f32p, sz, flt, f32p, vp]),

@@ -32,6 +32,8 @@ struct ConvLayer {           // conv + GroupNorm + Mish
   // rows of P1 / P2 per sample: what the buffers hold (setup_conv_layer) and what this backward has left in them so far (0 = nothing
   // yet; written by vae_record_rows alone, reset by VaeBackward::begin, summed by vae_gn_finalize)
   int prow_cap = 0, np1 = 0, np2 = 0;
+  int gnb_ran = -2;          // how this backward ran the layer's GroupNorm backward: LoGnBwdForm; -1: the consuming layer's data gradient
+                             // applied it in its epilogue; -2: not yet
   int MT = 0;
   size_t o_dv = 0;           // gradient wrt the raw conv output (GroupNorm backward -> data / weight gradient); one per layer, so the
                              // side-stream weight gradient of layer k never shares a buffer with what the main stream writes next
@@ -128,6 +130,7 @@ struct LoVae {
   int Bp = 0;
   size_t o_fac_dmlT = 0, o_fac_xT = 0, o_fac_gfcT = 0, o_fac_zT = 0, o_gram = 0;
   int n_cu = 0;              // compute units of the device (partition) this plan was made on; 0 = no device: nothing that waits across workgroups is planned
+  bool n_cu_assumed = false; // lo_vae_plan_assume_cus: a host-only handle planning for a device it was told about
   const void* sync_for_ws = nullptr;
   // fp8 operand mode of the forward convs (lo_vae_create_ex flag LO_VAE_FP8_FWD)
   bool fp8_fwd = false;
@@ -157,6 +160,118 @@ static inline int vae_record_rows(ConvLayer& c, LoGnRows r) {
   if (r.p1 > 0) c.np1 = r.p1;
   if (r.p2 > 0) c.np2 = r.p2;
   return LO_OK;
+}
+
+// ---- what a layer launches: the uses the choosers are asked with -----------------------------------------------------------------
+// The executor (lo_vae_step.hip) and the plan query (lo_vae_layer_plan_ex, lo_vae_plan.hip) both come here: a choice is made once, by
+// lo_conv_choose / lo_gn_bwd_choose / lo_wgrad_choose, with the use these helpers build, and the executor holds every launch that
+// reports its choice to the one the helper returned (vae_require_planned).
+
+// the chain's topology: the layer whose activation gradient the data gradient of c writes directly, so that its GroupNorm backward can
+// ride on that launch (null: the data gradient of c feeds a stage output / h0 / nothing), and the layer whose data gradient does that for c
+static inline const ConvLayer* vae_dgrad_prod(const LoVae* h, const ConvLayer& c) {
+  for (int s = 1; s < 4; ++s) if (&c == &h->dec[s]) return &h->dec[s - 1];
+  for (int s = 0; s < 4; ++s) {
+    if (&c == &h->enc[s][2]) return &h->enc[s][1];
+    if (&c == &h->enc[s][1]) return &h->enc[s][0];
+  }
+  return nullptr;
+}
+static inline ConvLayer* vae_dgrad_prod(LoVae* h, ConvLayer& c) {
+  return const_cast<ConvLayer*>(vae_dgrad_prod(static_cast<const LoVae*>(h), static_cast<const ConvLayer&>(c)));
+}
+static inline const ConvLayer* vae_dgrad_consumer(const LoVae* h, const ConvLayer& c) {
+  for (int s = 0; s < 3; ++s) if (&c == &h->dec[s]) return &h->dec[s + 1];
+  for (int s = 0; s < 4; ++s) {
+    if (&c == &h->enc[s][0]) return &h->enc[s][1];
+    if (&c == &h->enc[s][1]) return &h->enc[s][2];
+  }
+  return nullptr;
+}
+// the data gradient of c adds a second gradient to its output: the ResBlock's identity branch (conv1), the decoder's skip gradient
+// (the strided convs of stages 2..4)
+static inline bool vae_dgrad_adds(const LoVae* h, const ConvLayer& c) {
+  for (int s = 0; s < 4; ++s)
+    if (&c == &h->enc[s][1] || (s > 0 && &c == &h->enc[s][0])) return true;
+  return false;
+}
+
+// forward conv of layer c as conv_gn launches it.  y8: the layer's GroupNorm pass also leaves an e4m3 copy of its output
+struct VaeFwdPlan { bool splitk, fuse; LoConvUse use; LoConvChoice choice; };
+static inline VaeFwdPlan vae_fwd_plan(const ConvLayer& c, bool y8) {
+  VaeFwdPlan p{};
+  p.splitk = c.sk_fwd && !c.f8 && !y8;      // few output rows: K-split GEMM into fp32 slabs + one (sample, group)-local pass
+  p.fuse = !p.splitk && c.gnf && !c.f8 && !y8;
+  if (p.splitk) p.use.nsplit = c.sk_fwd;
+  else { p.use.bias = true; p.use.gn_partial = !p.fuse; p.use.gf = p.fuse; p.use.f8 = c.f8; }
+  p.choice = lo_conv_choose(c.gf, p.use);
+  return p;
+}
+// data gradient of layer c.  prod: vae_dgrad_prod (null also where the caller wants no fusion); add: a second gradient is added.
+// splitk: K-split GEMM + the slab form of prod's GroupNorm backward; else one launch with prod's GroupNorm-backward reduction in its
+// epilogue (reduce; rows = P1 rows per sample it leaves) and, where the whole grid is resident at once, the apply pass too (apply)
+struct VaeDgradPlan { bool splitk, reduce, apply; int rows; LoConvUse use; LoConvChoice choice; };
+static inline VaeDgradPlan vae_dgrad_plan(const LoVae* h, const ConvLayer& c, const ConvLayer* prod, bool add) {
+  VaeDgradPlan p{};
+  p.splitk = prod && c.sk_dgrad && lo_gn_bwd_choose(prod->Ho * prod->Wo, prod->Cout, {.slab = true}).form == LO_GNB_SLAB_LOCAL;
+  if (p.splitk) {
+    p.use.nsplit = c.sk_dgrad;
+  } else {
+    p.use.add = add;
+    if (prod && h->fuse_gnb) {
+      // asked with the apply form: the same rows of P1 per sample either way (the apply form does not change the kernel)
+      const LoConvChoice ch = lo_conv_choose(c.gd, {.add = add, .gb = true, .gb_apply = true});
+      p.reduce = true;
+      p.rows = ch.mts;
+      // ... only where the whole grid is resident at once (one workgroup per CU): on the 64-channel 64 x 64 layers (1 024 tiles at
+      // batch 64, two rounds of 512) the fused launch is 32-34 us longer than the 27 us pass it replaces, and the step is 0.6 %
+      // faster without it there (22 309-22 332 against 22 185-22 202; nowhere: 22 238-22 316)
+      p.apply = h->fuse_gna && ch.gnb_apply && h->B * ch.mts * ch.nt <= h->n_cu;
+      p.use.gb = true; p.use.gb_apply = p.apply;
+    }
+  }
+  p.choice = lo_conv_choose(c.gd, p.use);
+  return p;
+}
+// GroupNorm backward of layer c as a launch of its own: from split-K slabs, or with rows_in_P1 rows per sample already in P1
+static inline LoGnChoice vae_gn_bwd_choice(const LoVae* h, const ConvLayer& c, bool slab, int rows_in_P1) {
+  return lo_gn_bwd_choose(c.Ho * c.Wo, c.Cout, {slab, rows_in_P1, h->gn_local});
+}
+// What the backward leaves of layer c's GroupNorm backward, replayed from the chain's topology: the executor keeps the P1 rows a
+// data-gradient epilogue has written as state (ConvLayer::np1) and decides the form when it gets to the layer; the same helpers, asked
+// in the order of the chain, give the plan query its answer, and a single-call backward ends by comparing the two (vae_check_gn_replay).
+// form: LoGnBwdForm, or -1 = no launch of its own (the consuming layer's data gradient applied it)
+struct VaeGnBwdPlan { int form, p1, p2; };
+static inline VaeGnBwdPlan vae_gn_bwd_replay(const LoVae* h, const ConvLayer& c) {
+  const ConvLayer* q = vae_dgrad_consumer(h, c);
+  VaeDgradPlan d{};
+  if (q) d = vae_dgrad_plan(h, *q, &c, vae_dgrad_adds(h, *q));
+  if (q && d.apply) return {-1, d.rows, d.rows};
+  const LoGnChoice g = vae_gn_bwd_choice(h, c, q && d.splitk, (q && d.reduce) ? d.rows : 0);
+  return {(int)g.form, g.rows.p1 > 0 ? g.rows.p1 : d.rows, g.rows.p2};      // vae_record_rows: a count of 0 leaves what the epilogue recorded
+}
+static inline int vae_check_gn_replay(const LoVae* h) {
+  int bad = 0;
+  for_each_layer(h, [&](const ConvLayer& c) {
+    const VaeGnBwdPlan p = vae_gn_bwd_replay(h, c);
+    if (bad || (c.gnb_ran == p.form && c.np1 == p.p1 && c.np2 == p.p2)) return;
+    lo_set_error("GroupNorm backward %dx%dx%d: the backward ran form %d and left %d / %d rows of P1 / P2 per sample, the plan has form %d, %d / %d",
+                 c.Ho, c.Wo, c.Cout, c.gnb_ran, c.np1, c.np2, p.form, p.p1, p.p2);
+    bad = 1;
+  });
+  return bad ? LO_ERR_STATE : LO_OK;
+}
+// a launch that reports its choice must have made the one the plan names, field by field
+static inline int vae_require_planned(const LoConvChoice& ran, const LoConvChoice& plan, const char* what, const LoGeom& g) {
+  if (ran.kernel == plan.kernel && ran.bm == plan.bm && ran.bn == plan.bn && ran.bk == plan.bk && ran.th == plan.th && ran.tw == plan.tw &&
+      ran.grid == plan.grid && ran.mts == plan.mts && ran.rows == plan.rows && ran.nt == plan.nt && ran.gn_fuse == plan.gn_fuse &&
+      ran.gnb_apply == plan.gnb_apply)
+    return LO_OK;
+  lo_set_error("%s %dx%d %d->%d: the launch chose kernel %d, tile %dx%dx%d / %dx%d, grid %d, rows %d / %d, n tiles %d, fusions %d %d; the plan has "
+               "kernel %d, tile %dx%dx%d / %dx%d, grid %d, rows %d / %d, n tiles %d, fusions %d %d", what, g.Hout, g.Wout, g.Cin, g.Cout,
+               ran.kernel, ran.bm, ran.bn, ran.bk, ran.th, ran.tw, ran.grid, ran.mts, ran.rows, ran.nt, (int)ran.gn_fuse, (int)ran.gnb_apply,
+               plan.kernel, plan.bm, plan.bn, plan.bk, plan.th, plan.tw, plan.grid, plan.mts, plan.rows, plan.nt, (int)plan.gn_fuse, (int)plan.gnb_apply);
+  return LO_ERR_STATE;
 }
 
 // ---- stream plumbing -------------------------------------------------------------------------------------------------------------

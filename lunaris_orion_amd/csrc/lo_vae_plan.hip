@@ -458,6 +458,62 @@ extern "C" int lo_vae_layer_plan(const LoVae* h, int dec, int s, int k, int* inf
   return LO_OK;
 }
 
+// A handle made where no device is visible (n_cu = 0) plans nothing that waits across workgroups, so its answers are not those of any
+// real device.  This names the device to plan for instead; such a handle can launch nothing.  Refused on a handle that has a device.
+extern "C" int lo_vae_plan_assume_cus(LoVae* h, int n_cu) {
+  LO_REQUIRE(h && n_cu >= 1, "lo_vae_plan_assume_cus: bad argument");
+  if (h->n_cu != 0 && !h->n_cu_assumed) {
+    lo_set_error("lo_vae_plan_assume_cus: the handle was made on a device with %d compute units", h->n_cu);
+    return LO_ERR_STATE;
+  }
+  h->n_cu = n_cu;
+  h->n_cu_assumed = true;
+  return LO_OK;
+}
+
+// The launches of conv + GroupNorm layer (dec, s, k) in the fused single-call step (lo_vae_forward, lo_vae_backward with fused = 1),
+// field order as documented in include/lunaris_hip.h.  Every choice comes from the helper the executor asks (lo_vae.h); what the
+// executor keeps as state between launches -- the P1 rows a data-gradient epilogue has left for the GroupNorm backward of the layer
+// before it -- is replayed here from the chain's topology.
+extern "C" int lo_vae_layer_plan_ex(const LoVae* h, int dec, int s, int k, int* info, int cap) {
+  LO_REQUIRE(h && info && s >= 0 && s < 4 && k >= 0 && k < 3 && !(dec && k), "lo_vae_layer_plan_ex: bad argument");
+  LO_REQUIRE(cap >= LO_VAE_PLAN_FIELDS, "lo_vae_layer_plan_ex: room for %d fields, the plan has %d", cap, LO_VAE_PLAN_FIELDS);
+  const ConvLayer& c = dec ? h->dec[s] : h->enc[s][k];
+  const bool first = &c == &h->enc[0][0];      // its conv, weight gradient and (image) data gradient are kernels of their own
+  for (int i = 0; i < LO_VAE_PLAN_FIELDS; ++i) info[i] = 0;
+  auto put_conv = [&](int at, const LoConvChoice& ch, int ksplit) {
+    const int f[9] = {ch.kernel, ch.bm, ch.bn, ch.bk, ch.th, ch.tw, ch.mts, ch.nt, ksplit};
+    for (int i = 0; i < 9; ++i) info[at + i] = f[i];
+  };
+  // ---- forward
+  if (first) info[6] = c.MT;
+  else {
+    bool y8 = c.o_a8 != 0;      // conv_gn's o_y8: the ResBlock tail writes the stage output and its e4m3 copy
+    for (int t = 0; t < 4; ++t) if (&c == &h->enc[t][2]) y8 = h->o_eout8[t] != 0;
+    const VaeFwdPlan f = vae_fwd_plan(c, y8);
+    put_conv(c.f8 ? 9 : 0, f.choice, f.splitk ? c.sk_fwd : 0);
+  }
+  // ---- data gradient
+  if (!first) {
+    const VaeDgradPlan d = vae_dgrad_plan(h, c, vae_dgrad_prod(h, c), vae_dgrad_adds(h, c));
+    put_conv(18, d.choice, d.splitk ? c.sk_dgrad : 0);
+    info[27] = d.apply ? 1 : 0;
+  }
+  // ---- GroupNorm backward: what the data gradient of the consuming layer has left decides the form
+  {
+    const VaeGnBwdPlan g = vae_gn_bwd_replay(h, c);      // every single-call backward ends by checking this replay against what it did
+    info[28] = g.form; info[29] = g.p1; info[30] = g.p2;
+  }
+  // ---- weight gradient
+  if (first) info[31] = -1;
+  else {
+    const LoWgradChoice w = lo_wgrad_choose(c.gf);
+    const int f[9] = {w.kernel, w.tw, w.convt ? 1 : 0, w.nsplit, w.slabs, w.units_per_split, w.direct ? 1 : 0, w.reduce, w.units};
+    for (int i = 0; i < 9; ++i) info[31 + i] = f[i];
+  }
+  return LO_OK;
+}
+
 // byte offset (inside the workspace) of the word a fused-GroupNorm workgroup sets when its rendezvous poll ran out; 0 = never
 extern "C" int lo_vae_sync_fail_word(const LoVae* h, size_t* byte_offset, int* fused_layers) {
   LO_REQUIRE(h && byte_offset, "lo_vae_sync_fail_word: null argument");

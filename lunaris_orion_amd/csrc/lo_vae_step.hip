@@ -23,14 +23,17 @@ static int conv_gn(LoVae* h, ConvLayer& c, const f16* in, const f16* other, f16*
   LoProfTag tag("fwd kind%d %dx%d %d->%d", c.kind, c.Ho, c.Wo, c.gf.Cin, c.gf.Cout);     // names the conv launch below
   // GroupNorm + Mish inside the conv's own epilogue (the workgroups of a sample exchange their sums: LoGnFuse) where the kernel that
   // owns this geometry supports it; the separate lo_gn_fwd pass below is then not run.  Same statistics, same arithmetic, same bits.
-  if (c.sk_fwd && !c.f8 && !o_y8) {
+  const VaeFwdPlan plan = vae_fwd_plan(c, o_y8 != 0);
+  LoConvChoice ran{};       // the choice the launch made: the plan's, and its partial-sum rows are what lo_gn_forward reads below
+  if (plan.splitk) {
     // few output rows: K-split GEMM into fp32 slabs, then ONE (sample, group)-local pass: slab sum + bias -> v, statistics, GroupNorm + Mish
-    LO_TRY(lo_conv_run(c.gf, {.in = in, .w = WSP(f16, c.o_wp_f), .slab = WSP(float, h->o_skslab), .nsplit = c.sk_fwd}, st));
+    LO_TRY(lo_conv_run(c.gf, {.in = in, .w = WSP(f16, c.o_wp_f), .slab = WSP(float, h->o_skslab), .nsplit = c.sk_fwd}, st, &ran));
     tag.end();
+    LO_TRY(vae_require_planned(ran, plan.choice, "forward conv (split-K)", c.gf));
     return lo_gn_forward(vae_gn_layer(h, c, P, ws),
                          {.slab = WSP(float, h->o_skslab), .nsplit = c.sk_fwd, .bias = PRM(c.p_b), .other = other, .mode = mode, .y = y}, st);
   }
-  const bool fuse = c.gnf && !c.f8 && !o_y8;
+  const bool fuse = plan.fuse;
   LoGnFuse gf;
   if (fuse) {
     memset(&gf, 0, sizeof(gf));
@@ -41,7 +44,6 @@ static int conv_gn(LoVae* h, ConvLayer& c, const f16* in, const f16* other, f16*
     gf.fail = WSP(unsigned int, h->o_sync_fail);
   }
   int r_;
-  LoConvChoice ran{};       // the choice the launch made: its partial-sum rows are what lo_gn_forward reads below
   if (c.f8) {
     LO_REQUIRE(o_in8, "fp8 mode: no e4m3 copy of the input of a conv %d->%d", c.Cin, c.Cout);
     r_ = lo_conv_run_f8(c.gf, WSP(uint8_t, o_in8), WSP(uint8_t, c.o_wp8), WSP(float, c.o_wscale),
@@ -52,6 +54,7 @@ static int conv_gn(LoVae* h, ConvLayer& c, const f16* in, const f16* other, f16*
   }
   tag.end();
   if (r_ != LO_OK) { if (fuse) --c.gnf_epoch; return r_; }
+  LO_TRY(vae_require_planned(ran, plan.choice, c.f8 ? "forward conv (e4m3)" : "forward conv", c.gf));
   if (fuse) return LO_OK;
   // o_part is sized for c.MT rows per sample and lo_gn_fwd sums c.MT rows: a launch that wrote another count has overrun the one and
   // is misread by the other (the plan and the launch asked lo_conv_choose with different uses)
@@ -265,8 +268,10 @@ struct VaeBackward {
   int gn_backward(ConvLayer& c, const LoGnBwd& op);
   int layer(ConvLayer& c, const f16* dy, const f16* other, int mode, const f16* layer_in, f16* ds, f16* din, const f16* add_src,
             ConvLayer* prod = nullptr, bool din_has_other_readers = false);
-  int dgrad_splitk(ConvLayer& c, int k, const f16* dv, f16* din, const f16* add_src, ConvLayer& prod, bool din_has_other_readers);
-  int dgrad(ConvLayer& c, int k, const f16* dv, f16* din, const f16* add_src, ConvLayer* prod, bool din_has_other_readers);
+  int dgrad_splitk(ConvLayer& c, int k, const VaeDgradPlan& plan, const f16* dv, f16* din, const f16* add_src, ConvLayer& prod,
+                   bool din_has_other_readers);
+  int dgrad(ConvLayer& c, int k, const VaeDgradPlan& plan, const f16* dv, f16* din, const f16* add_src, ConvLayer* prod,
+            bool din_has_other_readers);
   int decoder_chain(int fused, const float* recon, const float* target, const float* drecon, bool fac, float* dz32);
   int latent_and_heads(int fused, const float* gmu, const float* glv, bool fac, bool beside, bool hand_to_side);
   int early_norm(bool fac1);
@@ -283,7 +288,7 @@ int VaeBackward::begin(bool first_call) {
   LO_TRY(vae_wait_level(h, st, 5));
   if (!first_call) return LO_OK;
   h->bwd_layer = 0;
-  for_each_layer(h, [](ConvLayer& c) { c.np1 = 0; c.dv_done = false; c.np2 = 0; c.ev_ready = nullptr; });
+  for_each_layer(h, [](ConvLayer& c) { c.np1 = 0; c.dv_done = false; c.np2 = 0; c.ev_ready = nullptr; c.gnb_ran = -2; });
   return LO_OK;
 }
 
@@ -292,8 +297,17 @@ int VaeBackward::gn_backward(ConvLayer& c, const LoGnBwd& op_in) {
   LoGnBwd op = op_in;
   op.P1 = WSP(float, c.o_P1); op.P2 = WSP(float, c.o_P2);
   op.rows_in_P1 = c.np1; op.allow_local = h->gn_local;
-  LO_TRY(vae_record_rows(c, lo_gn_bwd_choose(c.Ho * c.Wo, c.Cout, lo_gn_use(op)).rows));
-  return lo_gn_backward(vae_gn_layer(h, c, P, ws), op, st);
+  const LoGnChoice plan = vae_gn_bwd_choice(h, c, op.slab != nullptr, c.np1);
+  LO_TRY(vae_record_rows(c, plan.rows));
+  c.gnb_ran = (int)plan.form;
+  LoGnRows left{};
+  LO_TRY(lo_gn_backward(vae_gn_layer(h, c, P, ws), op, st, &left));
+  if (left.p1 != plan.rows.p1 || left.p2 != plan.rows.p2) {
+    lo_set_error("GroupNorm backward %dx%dx%d: the launch left %d / %d rows of P1 / P2 per sample, the plan has %d / %d", c.Ho, c.Wo, c.Cout,
+                 left.p1, left.p2, plan.rows.p1, plan.rows.p2);
+    return LO_ERR_STATE;
+  }
+  return LO_OK;
 }
 
 // backward of one conv+GN+Mish layer.  dy: gradient wrt the layer's activation output (after mish, before any skip add).
@@ -325,17 +339,23 @@ int VaeBackward::layer(ConvLayer& c, const f16* dy, const f16* other, int mode, 
     LO_TRY(lo_wgrad_run(c.gf, layer_in, dv, WSP(float, h->o_wslab), GRD(c.p_w), inv, side ? h->side : st));
   }
   if (!din) return LO_OK;
-  if (prod && c.sk_dgrad && lo_gn_bwd_choose(prod->Ho * prod->Wo, prod->Cout, {.slab = true}).form == LO_GNB_SLAB_LOCAL)
-    return dgrad_splitk(c, k, dv, din, add_src, *prod, din_has_other_readers);
-  return dgrad(c, k, dv, din, add_src, prod, din_has_other_readers);
+  // the plan query describes this launch from the chain's topology alone: what the caller passed must be that
+  LO_REQUIRE(prod == vae_dgrad_prod(h, c) && (add_src != nullptr) == vae_dgrad_adds(h, c),
+             "data gradient %dx%d %d->%d: producer / added gradient differ from the chain's topology (lo_vae.h)", c.Ho, c.Wo, c.gd.Cin, c.gd.Cout);
+  const VaeDgradPlan plan = vae_dgrad_plan(h, c, prod, add_src != nullptr);
+  if (plan.splitk) return dgrad_splitk(c, k, plan, dv, din, add_src, *prod, din_has_other_readers);
+  return dgrad(c, k, plan, dv, din, add_src, prod, din_has_other_readers);
 }
 
 // few output rows: the data gradient as a K-split GEMM into fp32 slabs, then ONE (sample, group)-local pass that sums them
 // (+ the residual gradient) and runs the whole GroupNorm backward of the producing layer: dv, one P1 / P2 row per sample
-int VaeBackward::dgrad_splitk(ConvLayer& c, int k, const f16* dv, f16* din, const f16* add_src, ConvLayer& prod, bool din_has_other_readers) {
+int VaeBackward::dgrad_splitk(ConvLayer& c, int k, const VaeDgradPlan& plan, const f16* dv, f16* din, const f16* add_src, ConvLayer& prod,
+                              bool din_has_other_readers) {
   {
     LoProfTag tag("dgrad L%02d kind%d %dx%d %d->%d", k, c.kind, c.Ho, c.Wo, c.gd.Cin, c.gd.Cout);
-    LO_TRY(lo_conv_run(c.gd, {.in = dv, .w = WSP(f16, c.o_wp_d), .slab = WSP(float, h->o_skslab), .nsplit = c.sk_dgrad}, st));
+    LoConvChoice ran{};
+    LO_TRY(lo_conv_run(c.gd, {.in = dv, .w = WSP(f16, c.o_wp_d), .slab = WSP(float, h->o_skslab), .nsplit = c.sk_dgrad}, st, &ran));
+    LO_TRY(vae_require_planned(ran, plan.choice, "data gradient (split-K)", c.gd));
   }
   LoHandover ho(h, side);       // the pass below writes prod's dv: its launch carries prod's hand-over event
   LO_TRY(gn_backward(prod, {.slab = WSP(float, h->o_skslab), .nsplit = c.sk_dgrad, .add_src = add_src,
@@ -347,18 +367,15 @@ int VaeBackward::dgrad_splitk(ConvLayer& c, int k, const f16* dv, f16* din, cons
 }
 
 // the data gradient on its one-launch kernel, with the GroupNorm backward of the producing layer in its epilogue where that applies
-int VaeBackward::dgrad(ConvLayer& c, int k, const f16* dv, f16* din, const f16* add_src, ConvLayer* prod, bool din_has_other_readers) {
+int VaeBackward::dgrad(ConvLayer& c, int k, const VaeDgradPlan& plan, const f16* dv, f16* din, const f16* add_src, ConvLayer* prod,
+                       bool din_has_other_readers) {
   LoGnBwdFuse gb, *gbp = nullptr;
-  if (prod && h->fuse_gnb) {
+  if (plan.reduce) {
     gb.v = WSP(f16, prod->o_v); gb.stats = WSP(float, prod->o_stats); gb.gamma = PRM(prod->p_gw); gb.beta = PRM(prod->p_gb);
     gb.P1 = WSP(float, prod->o_P1);
-    // the launch below, asked with the apply form: np1 rows of P1 per sample either way (the apply form does not change the kernel)
-    const LoConvChoice ch = lo_conv_choose(c.gd, {.add = add_src != nullptr, .gb = true, .gb_apply = true});
-    const int mts = ch.mts, nt = ch.nt;
-    // ... only where the whole grid is resident at once (one workgroup per CU): on the 64-channel 64 x 64 layers (1 024 tiles at
-    // batch 64, two rounds of 512) the fused launch is 32-34 us longer than the 27 us pass it replaces, and the step is 0.6 %
-    // faster without it there (22 309-22 332 against 22 185-22 202; nowhere: 22 238-22 316)
-    const bool apply = h->fuse_gna && ch.gnb_apply && h->B * mts * nt <= h->n_cu;
+    // plan.rows rows of P1 per sample; the apply form where the plan has it (vae_dgrad_plan)
+    const int mts = plan.rows;
+    const bool apply = plan.apply;
     LO_TRY(vae_record_rows(*prod, {mts, apply ? mts : 0}));      // without the apply this launch leaves P2 alone: prod's own layer() runs that pass
     if (apply) {
       gb.dv = WSP(f16, prod->o_dv); gb.P2 = WSP(float, prod->o_P2);
@@ -367,6 +384,7 @@ int VaeBackward::dgrad(ConvLayer& c, int k, const f16* dv, f16* din, const f16* 
       gb.fail = WSP(unsigned int, h->o_sync_fail);
       gb.keep_out = din_has_other_readers;      // the decoder's data gradients are also the encoder's skip gradients
       prod->dv_done = true;
+      prod->gnb_ran = -1;
     }
     gbp = &gb;
   }
@@ -376,6 +394,7 @@ int VaeBackward::dgrad(ConvLayer& c, int k, const f16* dv, f16* din, const f16* 
   LoConvChoice ran{};
   int r_ = lo_conv_run(c.gd, {.in = dv, .w = WSP(f16, c.o_wp_d), .add_src = add_src, .out = din, .gb = gbp}, st, &ran);
   if (r_ != LO_OK) { if (writes_dv) { --prod->gba_epoch; prod->dv_done = false; } return r_; }
+  LO_TRY(vae_require_planned(ran, plan.choice, "data gradient", c.gd));
   // the P1 (and P2) rows recorded above are the ones this launch wrote
   if (gbp) LO_REQUIRE(ran.mts == prod->np1, "data gradient %dx%d %d->%d: the launch wrote %d P1 rows per sample, %d were recorded",
                       c.Ho, c.Wo, c.gd.Cin, c.gd.Cout, ran.mts, prod->np1);
@@ -403,7 +422,7 @@ int VaeBackward::decoder_chain(int fused, const float* recon, const float* targe
     const f16* layer_in = s > 0 ? WSP(f16, h->dec[s - 1].o_a) : WSP(f16, h->o_h0);
     f16* din = s > 0 ? WSP(f16, h->o_skipg[3 - s]) : Ga;   // up4->skipg[0] (wrt up3 out), up3->skipg[1], up2->skipg[2], up1->Ga
     // mode 1 (skip add) has the same du as mode 0; the skip branch receives gout unchanged (kept in skipg)
-    LO_TRY(layer(h->dec[s], gout, nullptr, 0, layer_in, nullptr, din, nullptr, s > 0 ? &h->dec[s - 1] : nullptr, true));
+    LO_TRY(layer(h->dec[s], gout, nullptr, 0, layer_in, nullptr, din, nullptr, vae_dgrad_prod(h, h->dec[s]), true));
     gout = din;
   }
   // gout == Ga: gradient wrt h0 [B,8,8,512] NHWC
@@ -491,12 +510,12 @@ int VaeBackward::encoder_stages(int s_hi, int s_lo, const float* x, float* dx) {
     ConvLayer& c1 = h->enc[s][1];
     ConvLayer& c2 = h->enc[s][2];
     // ResBlock tail + conv2:  dy = Ga -> ds = Gb (identity branch) ; dgrad -> Gd (grad wrt conv1 activation)
-    LO_TRY(layer(c2, Ga, WSP(f16, c0.o_a), 2, WSP(f16, c1.o_a), Gb, Gd, nullptr, &c1));
+    LO_TRY(layer(c2, Ga, WSP(f16, c0.o_a), 2, WSP(f16, c1.o_a), Gb, Gd, nullptr, vae_dgrad_prod(h, c2)));
     // conv1: dy = Gd ; dgrad (+ ds) -> Gc (grad wrt the block input = c0 activation)
-    LO_TRY(layer(c1, Gd, nullptr, 0, WSP(f16, c0.o_a), nullptr, Gc, Gb, &c0));
+    LO_TRY(layer(c1, Gd, nullptr, 0, WSP(f16, c0.o_a), nullptr, Gc, Gb, vae_dgrad_prod(h, c1)));
     if (s > 0) {
       // strided conv: dy = Gc ; dgrad (+ decoder skip gradient) -> Ga (grad wrt the previous stage output)
-      LO_TRY(layer(c0, Gc, nullptr, 0, WSP(f16, h->o_eout[s - 1]), nullptr, Ga, WSP(f16, h->o_skipg[s - 1])));
+      LO_TRY(layer(c0, Gc, nullptr, 0, WSP(f16, h->o_eout[s - 1]), nullptr, Ga, WSP(f16, h->o_skipg[s - 1]), vae_dgrad_prod(h, c0)));
       continue;
     }
     // (the first conv's weight gradient on the side stream with the finalize beside it: neutral in round 2 and again in round 3
@@ -556,7 +575,8 @@ extern "C" int lo_vae_backward_dx(LoVae* h, const float* x, const float* P, void
   // GroupNorm affine + conv bias gradients of all 16 layers in one launch.  Reads P1 / P2 rows only (all written on this stream):
   // before the join, beside the side stream's last weight gradients
   LO_TRY(b.finalize(0xFu, !early, b.st));
-  return b.join();
+  LO_TRY(b.join());
+  return vae_check_gn_replay(h);      // what lo_vae_layer_plan_ex reports of the GroupNorm backwards is what this backward did
 }
 extern "C" int lo_vae_backward(LoVae* h, const float* x, const float* P, void* ws, const float* recon, const float* target,
                                int fused, const float* drecon, const float* gmu, const float* glv, float loss_scale,
