@@ -150,6 +150,16 @@ int lo_selfattn2d_backward(const float* x, const float* wq, const float* wk, con
                            const float* q, const float* k, const float* v, const float* dy, float* scratch, float* dx,
                            float* dwq, float* dbq, float* dwk, float* dbk, float* dwv, float* dbv, float* dgamma, int B,
                            int C, int N, void* stream);
+/* The same block at the VAE's bottleneck (C = 512, N = 64 positions, q / k width 64) as the step executor runs it (LO_VAE_ATTN), on
+ * fp16 NHWC tensors: x, y, dy [B][64][512]; qkv, dqkv [B][64][640] = per position the 64 query, 64 key and 512 value channels
+ * (qkv = x Wqkv^T + b, one GEMM of the conv family); gamma: one fp32 on the device.  Forward: y = gamma * softmax_j(q_i . k_j) v_j
+ * + x.  Backward: from dy (any loss scale that keeps it finite in fp16) the gradient dqkv wrt qkv, recomputing the softmax from qkv,
+ * and dgamma_part [B] fp32 = per-sample sum dy . O (same loss scale).  The residual's share of dx is NOT in dqkv: the executor adds
+ * dy where it forms dx = dy + dqkv Wqkv; x is not read by the backward and may be NULL.  Both products of either direction run on
+ * v_mfma_f32_16x16x32_f16; no 64 x 64 tensor reaches global memory; sums have a fixed order (bitwise reproducible). */
+int lo_attn8_forward(const void* x, const void* qkv, const float* gamma, void* y, int B, void* stream);
+int lo_attn8_backward(const void* x, const void* qkv, const float* gamma, const void* dy, void* dqkv, float* dgamma_part, int B,
+                      void* stream);
 
 /* clip_grad_norm_ + AdamW over one flat fp32 buffer (train_hybrid.py:913,921; :504-509).  scratch: 1024+4 floats;
  * scratch[1024..1026] = (grad norm, clip coef, finite flag) afterwards; scratch[1027] counts the calls whose gradient norm was
@@ -184,6 +194,13 @@ int lo_vae_create(int batch, int latent_dim, LoVae** out);
  * operands).  No reference counterpart: the reference's low-precision mode is torch.cuda.amp fp16 autocast
  * (train_hybrid.py:850).  Unknown flag bits are an error. */
 #define LO_VAE_FP8_FWD 1u
+/* LO_VAE_ATTN: the model has the reference's SelfAttention2d(512) (lunar_generate.py:56-78) at both ends of the bottleneck: on the
+ * encoder's stage-4 output before the flatten, and on decoder.fc's output before up1.  14 more parameter tensors (86): in state_dict
+ * order encoder.attn.{gamma, query_conv.weight, .bias, key_conv.weight, .bias, value_conv.weight, .bias} between down4 and fc_mu,
+ * the same under decoder.attn between decoder.fc and up1.  In the flat buffer each site is gamma | Wq | Wk | Wv | bq | bk | bv (one
+ * [640][512] matrix and one [640] bias); the encoder site sits before fc_mu.weight, the decoder site behind decoder.fc.bias.
+ * Not combinable with LO_VAE_FP8_FWD (up1 would read an e4m3 copy of the attention's output): that is an error. */
+#define LO_VAE_ATTN 2u
 int lo_vae_create_ex(int batch, int latent_dim, unsigned flags, LoVae** out);
 void lo_vae_destroy(LoVae* h);
 /* Early gradient norm: with a scratch set (the 1028-float scratch of lo_clip_adamw_step), a single-call lo_vae_backward takes the
@@ -368,7 +385,10 @@ int lo_vae_debug_tensor(const LoVae* h, int which, int s, int k, size_t* byte_of
  * GroupNorm statistics of encoder conv (s, k) / decoder layer s, FP32 [B][8][2] = (mean, rstd) per group (dims4 = B, 8, 2, 1);
  * 7 / 8 = gradient wrt the raw conv output of encoder conv (s, k) / decoder layer s, multiplied by the backward's loss scale;
  * 9 = the decoder's input h0 (B, 8, 8, 512); 10 = skip gradient s = 0..2 (B, 64 >> s, 64 >> s, 64 << s; loss scale as 7 / 8).
- * elem_bytes: 2 = fp16, 4 = fp32.  (7, 0, 0) names where the LAST backward left the first conv's gradient. */
+ * elem_bytes: 2 = fp16, 4 = fp32.  (7, 0, 0) names where the LAST backward left the first conv's gradient.
+ * With LO_VAE_ATTN (s = k = 0; odd = encoder site, even = decoder site): 11 / 12 = qkv (B, 8, 8, 640); 13 / 14 = the site's input x,
+ * 15 / 16 = its output y, 17 / 18 = the gradient dy wrt y, 21 / 22 = the gradient dx wrt x (B, 8, 8, 512); 19 / 20 = dqkv
+ * (B, 8, 8, 640); 17 .. 22 carry the loss scale as 7 / 8. */
 int lo_vae_debug_tensor_ex(const LoVae* h, int which, int s, int k, size_t* byte_offset, int* dims4, int* elem_bytes);
 /* how the plan runs conv + GroupNorm layer (dec != 0: decoder layer s; else encoder conv (s, k)): info4 = { forward conv on e4m3
  * operands (0 / 1; their count is lo_vae_fp8_layers), GroupNorm partial-sum rows per sample the conv epilogue writes, K splits of the

@@ -56,6 +56,8 @@ SIGNATURES = {
     "lo_selfattn2d_forward": (i32, [f32p] * 12 + [i32, i32, i32, vp]),
     "lo_selfattn2d_backward_scratch_elems": (C.c_size_t, [i32, i32, i32]),
     "lo_selfattn2d_backward": (i32, [f32p] * 18 + [i32, i32, i32, vp]),
+    "lo_attn8_forward": (i32, [vp, vp, f32p, vp, i32, vp]),
+    "lo_attn8_backward": (i32, [vp, vp, f32p, vp, vp, f32p, i32, vp]),
     "lo_clip_adamw_step": (i32, [f32p, f32p, f32p, f32p, sz, flt, flt, flt, flt, flt, flt, i32, f32p, vp]),
     "lo_teacher_create": (i32, [i32, i32, i32, i32, C.POINTER(C.c_void_p)]),
     "lo_teacher_create_ex": (i32, [i32, i32, i32, i32, C.c_uint, C.POINTER(C.c_void_p)]),

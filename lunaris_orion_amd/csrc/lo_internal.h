@@ -76,6 +76,12 @@ int lo_selfattn2d_bwd(const float* x, const float* wq, const float* wk, const fl
                       float* dwk, float* dbk, float* dwv, float* dbv, float* dgamma, int B, int C, int N, hipStream_t st);
 int lo_decode_sprites(const uint8_t* u8, float* out, int B, hipStream_t st);
 
+// lo_attn8.hip: the VAE's bottleneck self-attention (8 x 8 x 512, q / k width 64) on fp16 NHWC tensors.  x, y, dy [B][64][512];
+// qkv, dqkv [B][64][640] (q | k | v per position); dgamma_part [B]: per-sample shares of sum dy . O (they carry dy's loss scale)
+int lo_attn8_fwd(const f16* x, const f16* qkv, const float* gamma, f16* y, int B, hipStream_t st);
+int lo_attn8_bwd(const f16* qkv, const float* gamma, const f16* dy, f16* dqkv, float* dgamma_part, int B, hipStream_t st);
+int lo_attn8_dgamma(const float* part, int B, float scale, float* out, hipStream_t st);     // out[0] = scale * sum, fixed order
+
 // lo_lowrank.hip: rank-B Linear-layer weight gradients as factors (Gram-matrix norm, AdamW that forms the gradient tiles itself)
 int lo_lowrank_bp(int B);                          // batch rounded up to the MFMA K step (32)
 bool lo_lowrank_applies(int B, int N, int K);

@@ -69,6 +69,15 @@ enum class LoLinearMode : int {
 // lo_vae_gathered_early_norm was given (the caller keeps them alive and unchanged until the step that follows has read them)
 struct LoFactorStep { bool ready = false; float scale = 1.f; const f16* gathered = nullptr; int world = 0; };
 
+// One site of the bottleneck self-attention (LO_VAE_ATTN).  Parameters: gamma, then Wq | Wk | Wv and bq | bk | bv, each group contiguous
+// in the flat buffer (one [640][512] matrix, one [640] bias).  Workspace: fp16 copy of the matrix and its transpose; qkv, the output y,
+// the gradients dy (wrt y), dqkv, dx (wrt the site's input), the per-sample shares of dgamma
+struct LoAttnSite {
+  int p_gamma = 0, p_w = 0, p_b = 0;      // parameter indices of gamma, query_conv.weight, query_conv.bias (key: + 2, value: + 4)
+  size_t o_w = 0, o_wt = 0;
+  size_t o_qkv = 0, o_y = 0, o_dy = 0, o_dqkv = 0, o_dx = 0, o_dgpart = 0;
+};
+
 struct LoVae {
   int B = 0, L = 0;
   // parameters
@@ -132,6 +141,13 @@ struct LoVae {
   int n_cu = 0;              // compute units of the device (partition) this plan was made on; 0 = no device: nothing that waits across workgroups is planned
   bool n_cu_assumed = false; // lo_vae_plan_assume_cus: a host-only handle planning for a device it was told about
   const void* sync_for_ws = nullptr;
+  // bottleneck self-attention (lo_vae_create_ex flag LO_VAE_ATTN): site 0 on the encoder's stage-4 output (before the flatten), site 1
+  // on decoder.fc's output h0 (before up1).  g_att_qkv: qkv = x Wqkv^T + b (M = B * 64, K = 512, N = 640; also the geometry of the
+  // weight gradient); g_att_dx: dx = dy + dqkv Wqkv on the transposed copy.  The weight-gradient slab is the sites' own.
+  bool attn = false;
+  LoAttnSite att[2];
+  LoGeom g_att_qkv{}, g_att_dx{};
+  size_t o_att_wslab = 0;
   // fp8 operand mode of the forward convs (lo_vae_create_ex flag LO_VAE_FP8_FWD)
   bool fp8_fwd = false;
   size_t o_eout8[4] = {}, o_h08 = 0, o_packjobs8 = 0;
@@ -339,3 +355,5 @@ static inline const f16* vae_fac_in_block(const LoVae* h, const f16* gathered, s
 // ---- across the units ------------------------------------------------------------------------------------------------------------
 int vae_flush_deferred(LoVae* h, hipStream_t after_main);    // lo_vae_opt.hip: enqueue a pipelined optimizer step's tail
 int vae_wait_level(LoVae* h, hipStream_t st, int lvl);       // lo_vae_opt.hip: `st` waits for operand-refresh level lvl
+// where the site's input lives: the encoder's stage-4 output / the decoder's h0
+static inline size_t vae_attn_input(const LoVae* h, int site) { return site == 0 ? h->o_eout[3] : h->o_h0; }

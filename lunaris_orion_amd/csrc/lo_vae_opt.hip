@@ -61,6 +61,19 @@ static int vae_linear_transposes(LoVae* h, void* ws, hipStream_t st) {
   return lo_nhwc_to_nchw_f16(WSP(f16, h->o_wp_dfc), WSP(f16, h->o_wp_dfc_t), 1, 32768, L, st);          // [32768][L] -> [L][32768]
 }
 
+// Operands of the attention sites (LO_VAE_ATTN): the fp16 copy of a site's [640][512] matrix (q | k | v rows, contiguous in the flat
+// buffer) belongs to the level the forward waits for before the site -- 2 for the encoder's, 4 for the decoder's -- and the transposed
+// copies, which only the backward reads, to level 5
+static int vae_attn_cast(LoVae* h, int site, const float* P, void* ws, hipStream_t st) {
+  if (!h->attn) return LO_OK;
+  return lo_cast_f32_f16(PRM(h->att[site].p_w), WSP(f16, h->att[site].o_w), (size_t)640 * 512, st);
+}
+static int vae_attn_transposes(LoVae* h, void* ws, hipStream_t st) {
+  if (!h->attn) return LO_OK;
+  for (const LoAttnSite& a : h->att) LO_TRY(lo_nhwc_to_nchw_f16(WSP(f16, a.o_w), WSP(f16, a.o_wt), 1, 640, 512, st));   // [640][512] -> [512][640]
+  return LO_OK;
+}
+
 // Where the two big Linear weights sit in the flat buffer (fc_mu | fc_logvar: nh elements from bh; decoder.fc: nd elements from bd;
 // 82 % of the parameters), and the table the factored AdamW pass (lo_adamw_lowrank) takes for them.  casts: that pass also writes
 // the fp16 forward operands and their transposed copies.
@@ -101,6 +114,7 @@ int vae_flush_deferred(LoVae* h, hipStream_t after_main) {
   };
   // level 2: encoder stage 4 (10 % of the parameters): first consumer ~0.45 ms into the forward
   LO_TRY(adam(b4, bh));
+  LO_TRY(vae_attn_cast(h, 0, P, ws, sd));
   LO_TRY(lo_pack_all(jobs + h->n_packjobs_enc, h->n_packjobs_s4 - h->n_packjobs_enc, h->pack_blocks_s4 - h->pack_blocks_enc, sd, h->pack_blocks_enc));
   if (h->fp8_fwd)
     LO_TRY(lo_pack_f8_all(jobs8 + h->n_packjobs8_enc, h->n_packjobs8_s4 - h->n_packjobs8_enc, h->pack_blocks8_s4 - h->pack_blocks8_enc, sd, h->pack_blocks8_enc));
@@ -117,12 +131,14 @@ int vae_flush_deferred(LoVae* h, hipStream_t after_main) {
   // level 4: decoder.fc (unless it went with the encoder heads), the decoder and final convs
   if (!vae_opt_from_factors(h)) LO_TRY(adam(bd, bd + nd, WSP(f16, h->o_wp_dfc)));
   LO_TRY(adam(bd + nd, n));
+  LO_TRY(vae_attn_cast(h, 1, P, ws, sd));
   LO_TRY(lo_pack_all(jobs + h->n_packjobs_s4, h->n_packjobs - h->n_packjobs_s4, h->pack_blocks - h->pack_blocks_s4, sd, h->pack_blocks_s4));
   if (h->fp8_fwd)
     LO_TRY(lo_pack_f8_all(jobs8 + h->n_packjobs8_s4, h->n_packjobs8 - h->n_packjobs8_s4, h->pack_blocks8 - h->pack_blocks8_s4, sd, h->pack_blocks8_s4));
   LO_TRY(vae_side_record(h, 4, sd));
   // level 5: the transposed copies (data gradients of the Linear layers: backward only); the factored AdamW pass has written them
   if (!vae_opt_from_factors(h)) LO_TRY(vae_linear_transposes(h, ws, sd));
+  LO_TRY(vae_attn_transposes(h, ws, sd));
   return vae_side_record(h, 5, sd);
 }
 
@@ -154,14 +170,17 @@ extern "C" int lo_vae_pack(LoVae* h, const float* P, void* ws, void* stream) {
   }
   LO_TRY(lo_pack_all(WSP(LoPackJob, h->o_packjobs), h->n_packjobs, h->pack_blocks, cs));
   if (h->fp8_fwd) LO_TRY(lo_pack_f8_all(WSP(LoPackF8Job, h->o_packjobs8), h->n_packjobs8, h->pack_blocks8, cs));
+  LO_TRY(vae_attn_cast(h, 0, P, ws, cs));
   if (cs != st) { LO_TRY(vae_side_record(h, 1, cs)); LO_TRY(vae_side_record(h, 2, cs)); }
   const int L = h->L;
   // encoder head: [fc_mu.weight ; fc_logvar.weight] is one contiguous [2L][32768] fp32 matrix in the flat buffer
   LO_REQUIRE(h->p_off[h->idx_fc_lv_w] == h->p_off[h->idx_fc_mu_w] + (size_t)L * 32768, "flat layout: head weights not adjacent");
   LO_TRY(lo_cast_f32_f16(PRM(h->idx_fc_mu_w), WSP(f16, h->o_wp_head), (size_t)2 * L * 32768, cs));
   LO_TRY(lo_cast_f32_f16(PRM(h->idx_dfc_w), WSP(f16, h->o_wp_dfc), (size_t)32768 * L, cs));
+  LO_TRY(vae_attn_cast(h, 1, P, ws, cs));
   if (cs != st) { LO_TRY(vae_side_record(h, 3, cs)); LO_TRY(vae_side_record(h, 4, cs)); }
   LO_TRY(vae_linear_transposes(h, ws, cs));
+  LO_TRY(vae_attn_transposes(h, ws, cs));
   if (cs != st) LO_TRY(vae_side_record(h, 5, cs));
   return LO_OK;
 }

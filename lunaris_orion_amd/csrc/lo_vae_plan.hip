@@ -67,12 +67,23 @@ static int plan_parameters(LoVae* h) {
     numel.push_back(co * ci * 9); numel.push_back(co); numel.push_back(co); numel.push_back(co);
     for (int k = 0; k < 2; ++k) { numel.push_back(co * co * 9); numel.push_back(co); numel.push_back(co); numel.push_back(co); }
   }
+  // SelfAttention2d(512) in state_dict order: the module's own parameter (gamma) first, then the three 1x1 convs (weight, bias)
+  auto push_attn = [&](LoAttnSite& a) {
+    if (!h->attn) return;
+    a.p_gamma = (int)numel.size(); numel.push_back(1);
+    a.p_w = (int)numel.size(); a.p_b = a.p_w + 1;
+    numel.push_back(64 * 512); numel.push_back(64);
+    numel.push_back(64 * 512); numel.push_back(64);
+    numel.push_back(512 * 512); numel.push_back(512);
+  };
+  push_attn(h->att[0]);
   h->idx_fc_mu_w = (int)numel.size(); numel.push_back((size_t)L * 32768);
   h->idx_fc_mu_b = (int)numel.size(); numel.push_back(L);
   h->idx_fc_lv_w = (int)numel.size(); numel.push_back((size_t)L * 32768);
   h->idx_fc_lv_b = (int)numel.size(); numel.push_back(L);
   h->idx_dfc_w = (int)numel.size(); numel.push_back((size_t)32768 * L);
   h->idx_dfc_b = (int)numel.size(); numel.push_back(32768);
+  push_attn(h->att[1]);
   const int dec_first = (int)numel.size();
   for (int s = 0; s < 4; ++s) {
     size_t ci = kDecCh[s], co = kDecCh[s + 1];
@@ -84,12 +95,25 @@ static int plan_parameters(LoVae* h) {
   h->p_off.assign(h->nparam, 0);
   // flat layout: state_dict order, except that fc_logvar.weight directly follows fc_mu.weight and the two head
   // biases are adjacent, so the encoder head is ONE [2L, 32768] matrix; every tensor starts on a 64-element boundary.
+  // An attention site is gamma | Wq | Wk | Wv | bq | bk | bv (the three weights one [640][512] matrix, the biases one [640] vector: all
+  // multiples of 64, no padding between them).  The encoder's site sits before fc_mu.weight -- inside the encoder range, which the
+  // serial norm tail and the optimizer's stage-4 level cover -- and the decoder's behind decoder.fc.bias, inside "everything behind
+  // decoder.fc.weight" of the early norm and the optimizer's decoder level: no range of lo_vae_opt.hip / early_norm needs a new case.
   size_t off = 0;
   auto place = [&](int i) { h->p_off[i] = off; off += (numel[i] + 63) & ~(size_t)63; };
+  auto place_attn = [&](const LoAttnSite& a) {
+    if (!h->attn) return;
+    place(a.p_gamma);
+    for (int k = 0; k < 3; ++k) place(a.p_w + 2 * k);
+    for (int k = 0; k < 3; ++k) place(a.p_b + 2 * k);
+  };
+  auto in_attn = [&](int i) { return h->attn && ((i >= h->att[0].p_gamma && i < h->att[0].p_gamma + 7) || (i >= h->att[1].p_gamma && i < h->att[1].p_gamma + 7)); };
   for (int i = 0; i < h->nparam; ++i) {
-    if (i == h->idx_fc_mu_b || i == h->idx_fc_lv_w || i == h->idx_fc_lv_b) continue;
+    if (i == h->idx_fc_mu_b || i == h->idx_fc_lv_w || i == h->idx_fc_lv_b || in_attn(i)) continue;
+    if (i == h->idx_fc_mu_w) place_attn(h->att[0]);
     place(i);
     if (i == h->idx_fc_mu_w) { place(h->idx_fc_lv_w); place(h->idx_fc_mu_b); place(h->idx_fc_lv_b); }
+    if (i == h->idx_dfc_b) place_attn(h->att[1]);
   }
   h->flat_elems = off;
   return dec_first;
@@ -214,6 +238,27 @@ static void plan_splitk_and_fp8(LoVae* h, Arena& ar) {
   h->o_packjobs8 = ar.take(sizeof(LoPackF8Job) * 32);
 }
 
+// bottleneck self-attention: the two GEMM geometries and, per site, the operand copies and the workspace of both directions
+static int plan_attention(LoVae* h, Arena& ar) {
+  if (!h->attn) return LO_OK;
+  const int B = h->B;
+  LO_TRY(lo_make_geom(&h->g_att_qkv, LO_LINEAR, B, 8, 8, 512, 640));     // qkv = x Wqkv^T + b
+  LO_TRY(lo_make_geom(&h->g_att_dx, LO_LINEAR, B, 8, 8, 640, 512));      // dx = dy + dqkv Wqkv  (the transposed copy as the operand)
+  for (LoAttnSite& a : h->att) {
+    a.o_w = ar.take((size_t)640 * 512 * 2);
+    a.o_wt = ar.take((size_t)640 * 512 * 2);
+    a.o_qkv = ar.take((size_t)B * 64 * 640 * 2);
+    a.o_y = ar.take((size_t)B * 64 * 512 * 2);
+    a.o_dy = ar.take((size_t)B * 64 * 512 * 2);
+    a.o_dqkv = ar.take((size_t)B * 64 * 640 * 2);
+    a.o_dx = ar.take((size_t)B * 64 * 512 * 2);
+    a.o_dgpart = ar.take((size_t)B * 4);
+  }
+  const size_t slab = lo_wgrad_slab_bytes(h->g_att_qkv);
+  h->o_att_wslab = ar.take(slab > 0 ? slab : 256);
+  return LO_OK;
+}
+
 // which GroupNorm passes are fused into conv epilogues
 static void plan_gn_fusions(LoVae* h) {
   // GroupNorm-backward reduction fused into the producing data-gradient epilogue (+1.4 % on the step; LO_GNB_FUSE=0 runs the
@@ -287,16 +332,20 @@ extern "C" int lo_vae_create(int B, int L, LoVae** out) { return lo_vae_create_e
 
 extern "C" int lo_vae_create_ex(int B, int L, unsigned flags, LoVae** out) {
   LO_REQUIRE(out, "lo_vae_create: null out");
-  LO_REQUIRE((flags & ~(unsigned)LO_VAE_FP8_FWD) == 0, "lo_vae_create_ex: unknown flag bits 0x%x", flags);
+  LO_REQUIRE((flags & ~(unsigned)(LO_VAE_FP8_FWD | LO_VAE_ATTN)) == 0, "lo_vae_create_ex: unknown flag bits 0x%x", flags);
+  LO_REQUIRE((flags & (LO_VAE_FP8_FWD | LO_VAE_ATTN)) != (LO_VAE_FP8_FWD | LO_VAE_ATTN),
+             "lo_vae_create_ex: LO_VAE_ATTN cannot be combined with LO_VAE_FP8_FWD (up1 would read an e4m3 copy of the attention's output)");
   LO_REQUIRE(B >= 1 && B <= 4096, "lo_vae_create: batch %d out of range", B);
   LO_REQUIRE(L >= 64 && L % 64 == 0 && L <= 4096, "lo_vae_create: latent_dim %d must be a multiple of 64", L);
   std::unique_ptr<LoVae> h(new LoVae());      // freed again if the plan fails
   h->B = B; h->L = L;
   h->fp8_fwd = (flags & LO_VAE_FP8_FWD) != 0;
+  h->attn = (flags & LO_VAE_ATTN) != 0;
   Arena ar;
   LO_TRY(plan_forward_buffers(h.get(), ar, plan_parameters(h.get())));
   plan_backward_buffers(h.get(), ar);
   plan_splitk_and_fp8(h.get(), ar);
+  LO_TRY(plan_attention(h.get(), ar));
   h->ws_bytes = ar.off;
   plan_gn_fusions(h.get());
   create_side_stream(h.get());
@@ -436,6 +485,15 @@ extern "C" int lo_vae_debug_tensor_ex(const LoVae* h, int which, int s, int k, s
   if (which == 10) {
     LO_REQUIRE(s < 3, "lo_vae_debug_tensor_ex: three skip gradients, asked for %d", s);
     *byte_offset = h->o_skipg[s]; dims4[1] = dims4[2] = 64 >> s; dims4[3] = 64 << s;
+    return LO_OK;
+  }
+  if (which >= 11 && which <= 22) {      // the attention sites: odd = encoder, even = decoder
+    LO_REQUIRE(h->attn, "lo_vae_debug_tensor_ex: tensor kind %d needs a plan made with LO_VAE_ATTN", which);
+    const int site = (which & 1) ? 0 : 1, what = (which - 11) / 2;
+    const LoAttnSite& a = h->att[site];
+    const size_t o[6] = {a.o_qkv, vae_attn_input(h, site), a.o_y, a.o_dy, a.o_dqkv, a.o_dx};
+    *byte_offset = o[what];
+    dims4[1] = dims4[2] = 8; dims4[3] = (what == 0 || what == 4) ? 640 : 512;
     return LO_OK;
   }
   LO_REQUIRE(which >= 4 && which <= 8 && !(which == 4 && k == 2), "lo_vae_debug_tensor_ex: unknown tensor kind %d (k = %d)", which, k);

@@ -64,6 +64,16 @@ static int conv_gn(LoVae* h, ConvLayer& c, const f16* in, const f16* other, f16*
                                                    .y8 = o_y8 ? WSP(uint8_t, o_y8) : nullptr}, st);
 }
 
+// bottleneck self-attention, forward of one site: qkv = x Wqkv^T + b on the GEMM family, then the fused core (lo_attn8.hip)
+static int vae_attn_forward(LoVae* h, int site, const f16* x, const float* P, void* ws, hipStream_t st) {
+  const LoAttnSite& a = h->att[site];
+  {
+    LoProfTag tag("attn%d qkv", site);
+    LO_TRY(lo_conv_run(h->g_att_qkv, {.in = x, .w = WSP(f16, a.o_w), .bias = PRM(a.p_b), .out = WSP(f16, a.o_qkv)}, st));
+  }
+  return lo_attn8_fwd(x, WSP(f16, a.o_qkv), PRM(a.p_gamma), WSP(f16, a.o_y), h->B, st);
+}
+
 // decoder (lunar_generate.py:194-229) from the latent z (fp16, in the workspace); use_skips=false is the `skips=[]`
 // call of LunarisCoreVAE.sample (:278-291)
 // skips[k] (fp16 NHWC, k = 0: 64 x 64 x 64, 1: 32 x 32 x 128, 2: 16 x 16 x 256) is added after up(3-k); NULL = not added
@@ -76,6 +86,10 @@ static int vae_decoder_forward(LoVae* h, const f16* const skips[3], const float*
   LO_TRY(lo_nchw_to_nhwc_f16(WSP(f16, h->o_yfc), WSP(f16, h->o_h0), B, 64, 512, st, h->o_h08 ? WSP(uint8_t, h->o_h08) : nullptr));
   const f16* cur = WSP(f16, h->o_h0);
   size_t cur8 = h->o_h08;
+  if (h->attn) {      // up1 reads the attention's output in place of h0 (level 4 has refreshed the site's operand)
+    LO_TRY(vae_attn_forward(h, 1, cur, P, ws, st));
+    cur = WSP(f16, h->att[1].o_y);
+  }
   for (int s = 0; s < 4; ++s) {
     ConvLayer& c = h->dec[s];
     const f16* skip = s < 3 ? skips[2 - s] : nullptr;
@@ -132,6 +146,10 @@ static int vae_encoder_forward(LoVae* h, const float* x, const float* eps, uint6
     LO_TRY(conv_gn(h, c2, WSP(f16, c1.o_a), WSP(f16, c0.o_a), WSP(f16, h->o_eout[s]), 2, P, ws, st, c1.o_a8, h->o_eout8[s]));
     cur = WSP(f16, h->o_eout[s]);
     cur8 = h->o_eout8[s];
+  }
+  if (h->attn) {      // the flatten reads the attention's output in place of the stage-4 output (level 2 has refreshed the site's operand)
+    LO_TRY(vae_attn_forward(h, 0, cur, P, ws, st));
+    cur = WSP(f16, h->att[0].o_y);
   }
   // ---- heads + reparameterisation (lunar_generate.py:150-152, 259-261)
   LO_TRY(lo_nhwc_to_nchw_f16(cur, WSP(f16, h->o_xflat), B, 64, 512, st));
@@ -231,7 +249,7 @@ static int vae_gn_finalize(LoVae* h, unsigned enc_mask, bool dec, float* G, void
 
 // the alignment gaps of the flat gradient buffer (every tensor starts on a 64-element boundary): the only elements no gradient
 // kernel writes.  One small launch instead of a 244 MB memset per step.
-struct LoGapTable { unsigned long long off[80]; int len[80]; int n; };
+struct LoGapTable { unsigned long long off[96]; int len[96]; int n; };
 __global__ void lo_zero_gaps_kernel(float* G, LoGapTable t) {
   const int i = blockIdx.x;
   if (i < t.n && (int)threadIdx.x < t.len[i]) G[t.off[i] + threadIdx.x] = 0.f;
@@ -239,7 +257,7 @@ __global__ void lo_zero_gaps_kernel(float* G, LoGapTable t) {
 static int vae_zero_gaps(LoVae* h, float* G, hipStream_t st) {
   LoGapTable t;
   t.n = 0;
-  LO_REQUIRE(h->nparam <= 80, "gap table too small");
+  LO_REQUIRE(h->nparam <= 96, "gap table too small");
   for (int i = 0; i < h->nparam; ++i) {
     const size_t n = h->p_numel[i], padded = (n + 63) & ~(size_t)63;
     if (padded > n) { t.off[t.n] = h->p_off[i] + n; t.len[t.n] = (int)(padded - n); ++t.n; }
@@ -274,6 +292,7 @@ struct VaeBackward {
             bool din_has_other_readers);
   int decoder_chain(int fused, const float* recon, const float* target, const float* drecon, bool fac, float* dz32);
   int latent_and_heads(int fused, const float* gmu, const float* glv, bool fac, bool beside, bool hand_to_side);
+  int attention(int site, const f16* dy, f16* dx, bool beside);
   int early_norm(bool fac1);
   int encoder_stages(int s_hi, int s_lo, const float* x, float* dx);
   int finalize(unsigned enc_mask, bool dec, hipStream_t on) { return vae_gn_finalize(h, enc_mask, dec, G, ws, inv, on); }
@@ -402,6 +421,33 @@ int VaeBackward::dgrad(ConvLayer& c, int k, const VaeDgradPlan& plan, const f16*
   return LO_OK;
 }
 
+// Backward of one attention site from dy = gradient wrt its output (fp16, loss-scaled): the fused core leaves dqkv and the per-sample
+// shares of dgamma; dx = dy + dqkv Wqkv (the residual's gradient is the GEMM's added tensor) continues the chain; dgamma, the three
+// bias gradients (one column sum) and dWqkv = dqkv^T x run beside it, where the Linear layers' own do.  Shared by every entry point:
+// decoder_chain runs site 1, latent_and_heads site 0.  beside: the parameter gradients go to the side stream (if there is one), as the
+// caller's own Linear-layer gradients do; else everything stays on the caller's stream.
+int VaeBackward::attention(int site, const f16* dy, f16* dx, bool beside) {
+  const LoAttnSite& a = h->att[site];
+  const int B = h->B;
+  beside = beside && side;
+  hipStream_t gs = beside ? h->side : st;
+  f16* dqkv = WSP(f16, a.o_dqkv);
+  {
+    LoHandover ho(h, beside);
+    LO_TRY(lo_attn8_bwd(WSP(f16, a.o_qkv), PRM(a.p_gamma), dy, dqkv, WSP(float, a.o_dgpart), B, st));
+    LO_TRY(ho.finish(st));
+    if (beside) LO_HIP(hipStreamWaitEvent(h->side, ho.ev, 0));
+  }
+  {
+    LoProfTag tag("attn%d params", site);
+    LO_TRY(lo_attn8_dgamma(WSP(float, a.o_dgpart), B, inv, GRD(a.p_gamma), gs));
+    LO_TRY(lo_colsum_f16(dqkv, GRD(a.p_b), B * 64, 640, inv, gs));
+    LO_TRY(lo_wgrad_run(h->g_att_qkv, WSP(f16, vae_attn_input(h, site)), dqkv, WSP(float, h->o_att_wslab), GRD(a.p_w), inv, gs));
+  }
+  LoProfTag tag("attn%d dx", site);
+  return lo_conv_run(h->g_att_dx, {.in = dqkv, .w = WSP(f16, a.o_wt), .add_src = dy, .out = dx}, st);
+}
+
 // Final conv, up4..up1, decoder.fc, dz: the gradients from decoder.fc.weight to the end of the buffer are complete afterwards (the
 // decoder's GroupNorm / bias gradients after their finalize).  dz32 (Decoder.forward's own backward): dz also as fp32
 int VaeBackward::decoder_chain(int fused, const float* recon, const float* target, const float* drecon, bool fac, float* dz32) {
@@ -419,13 +465,18 @@ int VaeBackward::decoder_chain(int fused, const float* recon, const float* targe
   // ---- decoder: up4..up1.  Ga holds the gradient wrt the stage's (activation [+ skip]) output.
   const f16* gout = Ga;
   for (int s = 3; s >= 0; --s) {
-    const f16* layer_in = s > 0 ? WSP(f16, h->dec[s - 1].o_a) : WSP(f16, h->o_h0);
-    f16* din = s > 0 ? WSP(f16, h->o_skipg[3 - s]) : Ga;   // up4->skipg[0] (wrt up3 out), up3->skipg[1], up2->skipg[2], up1->Ga
+    // with the attention site, up1 read its output y, and the gradient wrt y gets a buffer of its own (it stays inspectable)
+    const f16* layer_in = s > 0 ? WSP(f16, h->dec[s - 1].o_a) : WSP(f16, h->attn ? h->att[1].o_y : h->o_h0);
+    f16* din = s > 0 ? WSP(f16, h->o_skipg[3 - s]) : (h->attn ? WSP(f16, h->att[1].o_dy) : Ga);   // up4->skipg[0] (wrt up3 out), up3->skipg[1], up2->skipg[2], up1->Ga
     // mode 1 (skip add) has the same du as mode 0; the skip branch receives gout unchanged (kept in skipg)
     LO_TRY(layer(h->dec[s], gout, nullptr, 0, layer_in, nullptr, din, nullptr, vae_dgrad_prod(h, h->dec[s]), true));
     gout = din;
   }
-  // gout == Ga: gradient wrt h0 [B,8,8,512] NHWC
+  // gout == Ga: gradient wrt h0 [B,8,8,512] NHWC (with the attention site: wrt its output; its backward leaves the one wrt h0)
+  if (h->attn) {
+    LO_TRY(attention(1, gout, WSP(f16, h->att[1].o_dx), true));
+    gout = WSP(f16, h->att[1].o_dx);
+  }
   // ---- decoder.fc
   // The bias and weight gradients of the two Linear layers feed nothing on the dependent chain (72 us of it in round 2): with a
   // side stream they run there, behind an event that rides on the launch producing their operand (LO_LAUNCH_STOP).  o_wslab_lin
@@ -434,7 +485,7 @@ int VaeBackward::decoder_chain(int fused, const float* recon, const float* targe
   f16* Gfc = WSP(f16, h->o_gfc);
   {
     LoHandover ho(h, side);
-    LO_TRY(lo_nhwc_to_nchw_f16(Ga, Gfc, B, 64, 512, st));                   // Gfc = dy of decoder.fc, [B][32768] c-major
+    LO_TRY(lo_nhwc_to_nchw_f16(gout, Gfc, B, 64, 512, st));                 // Gfc = dy of decoder.fc, [B][32768] c-major
     LO_TRY(ho.finish(st));
     if (side) LO_HIP(hipStreamWaitEvent(h->side, ho.ev, 0));
   }
@@ -471,10 +522,16 @@ int VaeBackward::latent_and_heads(int fused, const float* gmu, const float* glv,
     LO_TRY(lo_wgrad_run(h->g_head, WSP(f16, h->o_xflat), WSP(f16, h->o_dml), WSP(float, h->o_wslab_lin), GRD(h->idx_fc_mu_w), inv, gs));
   }
   LO_TRY(lo_conv_run(h->g_head_d, {.in = WSP(f16, h->o_dml), .w = WSP(f16, h->o_wp_head_t), .out = Gb}, st));
-  LoHandover ho(h->ev_pre, beside && hand_to_side);
-  LO_TRY(lo_nchw_to_nhwc_f16(Gb, Ga, B, 64, 512, st));                    // Ga = gradient wrt enc4 output, NHWC
-  LO_TRY(ho.finish(st));
-  if (ho.ev) LO_HIP(hipStreamWaitEvent(h->side, ho.ev, 0));
+  // with the attention site this is the gradient wrt ITS output; its backward leaves the one wrt the stage-4 output in the site's dx,
+  // where encoder_stages picks it up
+  f16* genc = h->attn ? WSP(f16, h->att[0].o_dy) : Ga;
+  {
+    LoHandover ho(h->ev_pre, beside && hand_to_side);
+    LO_TRY(lo_nchw_to_nhwc_f16(Gb, genc, B, 64, 512, st));                // Ga = gradient wrt enc4 output, NHWC
+    LO_TRY(ho.finish(st));
+    if (ho.ev) LO_HIP(hipStreamWaitEvent(h->side, ho.ev, 0));
+  }
+  if (h->attn) LO_TRY(attention(0, genc, WSP(f16, h->att[0].o_dx), beside));
   return LO_OK;
 }
 
@@ -510,7 +567,8 @@ int VaeBackward::encoder_stages(int s_hi, int s_lo, const float* x, float* dx) {
     ConvLayer& c1 = h->enc[s][1];
     ConvLayer& c2 = h->enc[s][2];
     // ResBlock tail + conv2:  dy = Ga -> ds = Gb (identity branch) ; dgrad -> Gd (grad wrt conv1 activation)
-    LO_TRY(layer(c2, Ga, WSP(f16, c0.o_a), 2, WSP(f16, c1.o_a), Gb, Gd, nullptr, vae_dgrad_prod(h, c2)));
+    const f16* gtop = (s == 3 && h->attn) ? WSP(f16, h->att[0].o_dx) : Ga;      // stage 4 behind the attention site: see latent_and_heads
+    LO_TRY(layer(c2, gtop, WSP(f16, c0.o_a), 2, WSP(f16, c1.o_a), Gb, Gd, nullptr, vae_dgrad_prod(h, c2)));
     // conv1: dy = Gd ; dgrad (+ ds) -> Gc (grad wrt the block input = c0 activation)
     LO_TRY(layer(c1, Gd, nullptr, 0, WSP(f16, c0.o_a), nullptr, Gc, Gb, vae_dgrad_prod(h, c1)));
     if (s > 0) {

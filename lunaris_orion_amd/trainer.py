@@ -93,6 +93,10 @@ class VAEStepper:
                  grad_sync: Optional[Callable[[torch.Tensor], None]] = None, pipeline_optimizer: bool = False,
                  dp_factored_adamw: Optional[bool] = None):
         _lib.require_gpu()
+        if getattr(vae, "attention", False) and grad_sync is not None and int(getattr(grad_sync, "world", 1)) > 1:
+            # the exchange ranges, the factor all-gather and the gathered-factor optimizer have never been run with the 86-tensor
+            # layout: not offered untested
+            raise NotImplementedError("data parallel (grad_sync with world > 1) is not built for LunarisCoreVAE(attention=True)")
         self.vae = vae
         # pipeline_optimizer: the update of the Linear / decoder parameters (87 % of AdamW's 1.7 GB) and their operand refresh run
         # on the library's side stream beside the NEXT step's encoder forward (lo_vae_optimizer_step).  Parameters may then still

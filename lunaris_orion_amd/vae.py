@@ -11,6 +11,10 @@ Drop-in contract (reference: /root/reference/lunar_generate.py):
     a single fused kernel and a data-parallel gradient exchange is one contiguous buffer); any
     optimizer that works on ``model.parameters()`` still works.
 
+``LunarisCoreVAE(latent_dim, attention=True)`` (opt-in) adds the reference's ``SelfAttention2d(512)`` (lunar_generate.py:56-78) as
+``encoder.attn`` (on the stage-4 output, before the flatten) and ``decoder.attn`` (on ``fc(z)``, before ``up1``): 86 keys.  Both sites run
+inside the native calls below (plan flag LO_VAE_ATTN); the modules only hold their parameters.
+
 ``LunarisCoreVAE.forward`` hands the flat parameter buffer to the native step executor
 (``lo_vae_forward`` / ``lo_vae_backward``: one call each), which enqueues every kernel of the pass on
 PyTorch's current HIP stream.  ``model.encoder(x) -> (mu, logvar, skips)`` and ``model.decoder(z, skips)``
@@ -153,11 +157,13 @@ class Encoder(_OwnedByVAE, nn.Module):
     skips)`` (:127-153) is one native call (``lo_vae_encode``); with gradients enabled it is an autograd node whose backward is
     ``lo_vae_encoder_backward``."""
 
-    def __init__(self, latent_dim: int = 256):
+    def __init__(self, latent_dim: int = 256, attention: bool = False):
         super().__init__()
         for i, (cin, cout) in enumerate(_ENC, start=1):
             stage = _conv_gn_mish(cin, cout, kernel_size=3, stride=2, padding=1) + [ResBlock(cout, cout)]
             setattr(self, f"down{i}", nn.Sequential(*stage))
+        if attention:       # on the stage-4 output, before the flatten; a parameter container here, run inside the native encoder
+            self.attn = SelfAttention2d(512)
         self.flatten = nn.Flatten()
         self.fc_mu = nn.Linear(512 * 8 * 8, latent_dim)
         self.fc_logvar = nn.Linear(512 * 8 * 8, latent_dim)
@@ -178,9 +184,11 @@ class Decoder(_OwnedByVAE, nn.Module):
     the reference's ``len(skips) >= k`` guards; ``skips=[]`` is the sampling call of :290) is one native call
     (``lo_vae_decode_skips``); with gradients enabled it is an autograd node whose backward is ``lo_vae_decoder_backward``."""
 
-    def __init__(self, latent_dim: int = 256):
+    def __init__(self, latent_dim: int = 256, attention: bool = False):
         super().__init__()
         self.fc = nn.Linear(latent_dim, 512 * 8 * 8)
+        if attention:       # on fc(z).view(B, 512, 8, 8), before up1; a parameter container here, run inside the native decoder
+            self.attn = SelfAttention2d(512)
         for i, (cin, cout) in enumerate(_DEC, start=1):
             setattr(self, f"up{i}", nn.Sequential(nn.ConvTranspose2d(cin, cout, kernel_size=4, stride=2, padding=1),
                                                   nn.GroupNorm(8, cout), nn.Mish()))
@@ -386,14 +394,23 @@ class LunarisCoreVAE(nn.Module):
     #: OCP e4m3 operands where the input channel count is a multiple of 128, fp16 backward; see include/lunaris_hip.h)
     MFMA_PRECISIONS = {"fp16": 0, "fp8": 1}
 
-    def __init__(self, latent_dim: int = 256, mfma_precision: str = "fp16"):
+    #: lo_vae_create_ex flag of ``attention=True`` (LO_VAE_ATTN, include/lunaris_hip.h)
+    ATTENTION_FLAG = 2
+
+    def __init__(self, latent_dim: int = 256, mfma_precision: str = "fp16", attention: bool = False):
         super().__init__()
         if mfma_precision not in self.MFMA_PRECISIONS:
             raise ValueError(f"mfma_precision must be one of {sorted(self.MFMA_PRECISIONS)}, got {mfma_precision!r}")
+        if attention and mfma_precision == "fp8":
+            raise ValueError("attention=True cannot be combined with mfma_precision='fp8': up1 would read an e4m3 copy of the attention's output")
         self.mfma_precision = mfma_precision
         self.latent_dim = latent_dim
-        self.encoder = Encoder(latent_dim=latent_dim)
-        self.decoder = Decoder(latent_dim=latent_dim)
+        #: opt-in: the reference's SelfAttention2d(512) (lunar_generate.py:56-78, defined there "if you decide to add it later") at both
+        #: ends of the bottleneck -- ``encoder.attn`` on the stage-4 output before the flatten, ``decoder.attn`` on fc(z) before up1;
+        #: 14 more state_dict keys (86), gamma initialised to 0.  Runs inside the native step (lo_attn8.hip), not as a module of its own
+        self.attention = bool(attention)
+        self.encoder = Encoder(latent_dim=latent_dim, attention=self.attention)
+        self.decoder = Decoder(latent_dim=latent_dim, attention=self.attention)
         for sub in (self.encoder, self.decoder):                 # not a registered attribute: no module cycle, nothing in state_dict
             object.__setattr__(sub, "_owner", weakref.ref(self))
         #: loss scale of the FUSED step (trainer.VAEStepper, which also runs GradScaler's policy on it).  The autograd path does not
@@ -430,7 +447,7 @@ class LunarisCoreVAE(nn.Module):
         self._weights_version += 1
 
     def _params_version(self) -> int:
-        """Sum of the 72 parameters' autograd version counters: moves on every in-place update of any of them (the views of the
+        """Sum of the parameters' (72; 86 with attention) autograd version counters: moves on every in-place update of any of them (the views of the
         flat buffer keep their own counters, and `torch.optim.AdamW.step()` bumps them; tests/test_module_boundary_gpu.py)."""
         return sum(p._version for p in self.parameters())
 
@@ -467,7 +484,7 @@ class LunarisCoreVAE(nn.Module):
         if dev.type != "cuda":
             raise _lib.LunarisHipError("LunarisCoreVAE parameters must be on the GPU (model.to('cuda')); there is no CPU path")
         probe = C.c_void_p()
-        _lib.check(_lib.lib.lo_vae_create(1, self.latent_dim, C.byref(probe)), "lo_vae_create")
+        _lib.check(_lib.lib.lo_vae_create_ex(1, self.latent_dim, self._engine_flags(), C.byref(probe)), "lo_vae_create_ex")
         try:
             assert _lib.lib.lo_vae_num_params(probe) == len(params), "parameter table mismatch"
             layout = []
@@ -487,8 +504,12 @@ class LunarisCoreVAE(nn.Module):
         self._weights_version += 1
         self._engines.clear()
 
+    def _engine_flags(self) -> int:
+        """lo_vae_create_ex flags of this model: the operand precision and the attention sites (the parameter table depends on them)."""
+        return self.MFMA_PRECISIONS[self.mfma_precision] | (self.ATTENTION_FLAG if self.attention else 0)
+
     def flat_parameters(self) -> torch.Tensor:
-        """The single fp32 buffer all 72 parameters are views of (padding elements are zero)."""
+        """The single fp32 buffer all parameters (72; 86 with attention) are views of (padding elements are zero)."""
         self._ensure_flat()
         return self._flat
 
@@ -497,7 +518,7 @@ class LunarisCoreVAE(nn.Module):
         key = (batch, str(self._flat.device))
         eng = self._engines.get(key)
         if eng is None:
-            eng = _Engine(batch, self.latent_dim, self._flat.device, self.MFMA_PRECISIONS[self.mfma_precision])
+            eng = _Engine(batch, self.latent_dim, self._flat.device, self._engine_flags())
             self._engines[key] = eng
         version = self._current_version()
         if eng.packed_version != version:
