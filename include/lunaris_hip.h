@@ -173,6 +173,15 @@ int lo_clip_adamw_step_presummed(float* p, const float* g, float* m, float* v, s
                                  float lr, float beta1, float beta2, float eps, float weight_decay, int step, float* scratch,
                                  void* stream);
 
+/* Gradient accumulation: acc[i] = (first ? 0 : acc[i]) + scale * g[i] over n fp32 elements, the pass that adds one micro-batch's
+ * gradients to those of its window.  The reference zeroes the gradients at the top of every _process_batch
+ * (train_hybrid.py:841-842), divides the losses by gradient_accumulation_steps (:895-896) and steps on every k-th call only (:907), so
+ * it keeps one micro-batch of k; with this entry behind every backward the step sees all k (VAEStepper(accumulate_gradients=True),
+ * opt-in).  first != 0: acc is NOT read -- whatever it held, NaN included, is overwritten.  acc and g must not overlap (-1); any
+ * 4-byte-aligned pointers and any n >= 1.  16-byte loads and stores from acc's first 16-byte boundary on (g as well where it has the
+ * same phase, as the same range of two flat buffers has), single elements in front and behind; no atomics: bitwise reproducible. */
+int lo_grad_accumulate(float* acc, const float* g, size_t n, float scale, int first, void* stream);
+
 /* Tool level: two passes of the optimizer step as single calls, exported for measurement only (tools/op_bench.py); the training
  * path never calls them and a binding may leave them out.
  * The AdamW pass alone (train_hybrid.py:921) on one flat range of n elements -- p, g, m, v: n floats -- as lo_clip_adamw_step and
@@ -279,6 +288,12 @@ size_t lo_vae_gathered_scratch_bytes(const LoVae* h, int world);   /* 0: world *
 int lo_vae_gathered_early_norm(LoVae* h, const void* gathered, int world, float* gram_scratch, const float* flat_grads, float* scratch,
                                void* stream);
 int lo_vae_linear_factored(const LoVae* h);
+/* Mode 3 for gradient accumulation on one GPU (VAEStepper(accumulate_gradients=True); the reference steps on one micro-batch of k,
+ * train_hybrid.py:841-842, 907): the k micro-batches of a window are k "ranks" arriving one after the other, each leaving its factor
+ * block behind lo_vae_backward_phase(1), and their gradients -- each already carrying lo_vae_loss's 1 / accum (:895-896) -- are ADDED.
+ * on != 0: every pass over gathered blocks (lo_vae_gathered_early_norm, the AdamW tiles, both materialize calls) multiplies by
+ * 1 / loss scale instead of 1 / (loss scale * world).  Off by default; lo_vae_set_linear_factored does not reset it. */
+int lo_vae_set_gathered_sum(LoVae* h, int on);
 int lo_vae_materialize_linear_grads(LoVae* h, void* ws, float* flat_grads, void* stream);
 /* The two passes of mode 3 on plain pointers.  W is [N][K] fp32 (N % 64 == 0, K % 64 == 0); its averaged gradient is
  * gscale * sum_r dY_r^T X_r with the factors TRANSPOSED and batch-padded, fp16: xt [K][Bp], yt [N][Bp] per rank, columns

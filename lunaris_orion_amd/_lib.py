@@ -145,6 +145,8 @@ SIGNATURES = {
     "lo_grad_unscale_dev": (i32, [f32p, sz, f32p, vp, vp]),
     "lo_vae_fp8_layers": (i32, [vp, C.POINTER(C.c_int)]),
     "lo_vae_stage4_grad_range": (i32, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "lo_grad_accumulate": (i32, [f32p, f32p, sz, flt, i32, vp]),
+    "lo_vae_set_gathered_sum": (i32, [vp, i32]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

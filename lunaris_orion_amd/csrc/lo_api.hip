@@ -163,6 +163,11 @@ extern "C" int lo_clip_adamw_step_presummed(float* p, const float* g, float* m, 
   return lo_adamw(p, g, m, v, n, scratch + 1024, lr, beta1, beta2, eps, weight_decay, step, S(stream));
 }
 
+// one micro-batch's gradients into the accumulator of its window (see lo_train.hip)
+extern "C" int lo_grad_accumulate(float* acc, const float* g, size_t n, float scale, int first, void* stream) {
+  return lo_grad_accumulate_run(acc, g, n, scale, first != 0, S(stream));
+}
+
 extern "C" int lo_decode_sprites_u8(const void* u8_hwc, float* out_chw, int B, void* stream) {
   LO_REQUIRE(u8_hwc && out_chw && B > 0, "lo_decode_sprites_u8: bad argument");
   return lo_decode_sprites((const uint8_t*)u8_hwc, out_chw, B, S(stream));

@@ -44,6 +44,7 @@ int lo_latent_bwd(const f16* dz, const float* mu, const float* logvar, const flo
 int lo_colsum_f16(const f16* x, float* out, int M, int N, float scale, hipStream_t st);
 int lo_cast_f32_f16(const float* src, f16* dst, size_t n, hipStream_t st);
 int lo_scale_f32(float* x, size_t n, float scale, hipStream_t st);
+int lo_grad_accumulate_run(float* acc, const float* g, size_t n, float scale, bool first, hipStream_t st);   // acc = (first ? 0 : acc) + scale * g
 int lo_dp_pack_f16_run(const float* g, f16* wire, size_t n, float scale, hipStream_t st);     // data-parallel exchange helpers
 int lo_dp_unpack_f16_run(const f16* wire, float* g, size_t n, float inv_scale, hipStream_t st);
 int lo_dp_unpack_f16_sumsq_run(const f16* wire, float* g, size_t n, float inv_scale, float* scratch, hipStream_t st);

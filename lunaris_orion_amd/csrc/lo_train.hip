@@ -659,3 +659,76 @@ int lo_scale_dev_run(float* x, size_t n, const float* scale_dev, const unsigned 
   LO_LAUNCH_CHECK("scale_dev");
   return LO_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Gradient accumulation over the micro-batches of a window (VAEStepper(accumulate_gradients=True)): what the reference's
+// `zero_grad` at the top of every _process_batch (train_hybrid.py:841-842), its `/ gradient_accumulation_steps` (:895-896) and its
+// step on every k-th call (:907) would add up to if the zero_grad sat where the step is.  One streaming pass behind the backward:
+//   acc[i] = (first ? 0 : acc[i]) + scale * g[i]
+// first: acc is not read (whatever it held, NaN included, is gone).  acc and g must not overlap; both only need 4-byte alignment.
+// The body runs from the first 16-byte boundary of acc in float4s -- g too where it shares acc's phase, as every range of two flat
+// buffers does; four dwords otherwise -- with LO_ACC_UNROLL independent loads per lane in flight before the first use; the up to three
+// elements in front of the body and behind it are single dwords of workgroup 0.  Every element is written by exactly one lane: no
+// atomics, the same bits on every run.
+// ---------------------------------------------------------------------------------------------
+#define LO_ACC_UNROLL 4
+template <bool FIRST, bool GVEC>
+__global__ __launch_bounds__(256) void lo_grad_accumulate_kernel(float* __restrict__ acc, const float* __restrict__ g, size_t head, size_t n4,
+                                                                 size_t n, float scale) {
+  f32x4* __restrict__ a4 = reinterpret_cast<f32x4*>(acc + head);
+  const float* __restrict__ gb = g + head;
+  const size_t stride = (size_t)gridDim.x * 256 * LO_ACC_UNROLL;
+  for (size_t base = (size_t)blockIdx.x * 256 * LO_ACC_UNROLL + threadIdx.x; base < n4; base += stride) {
+    f32x4 gv[LO_ACC_UNROLL], av[LO_ACC_UNROLL];
+#pragma unroll
+    for (int j = 0; j < LO_ACC_UNROLL; ++j) {
+      const size_t k = base + (size_t)j * 256;
+      if (k >= n4) continue;
+      if (GVEC) gv[j] = reinterpret_cast<const f32x4*>(gb)[k];
+      else gv[j] = (f32x4){gb[4 * k], gb[4 * k + 1], gb[4 * k + 2], gb[4 * k + 3]};
+      if (!FIRST) av[j] = a4[k];
+    }
+#pragma unroll
+    for (int j = 0; j < LO_ACC_UNROLL; ++j) {
+      const size_t k = base + (size_t)j * 256;
+      if (k >= n4) continue;
+      a4[k] = FIRST ? gv[j] * scale : av[j] + gv[j] * scale;
+    }
+  }
+  if (blockIdx.x != 0 || threadIdx.x >= 8) return;
+  // lanes 0..3: the elements in front of the body; lanes 4..7: those behind it
+  const size_t t = threadIdx.x & 3, body_end = head + 4 * n4;
+  const size_t i = threadIdx.x < 4 ? t : body_end + t;
+  if (threadIdx.x < 4 ? t < head : i < n) acc[i] = FIRST ? g[i] * scale : acc[i] + g[i] * scale;
+}
+// compute units of the current device, asked once per process (the grid of a pure streaming pass: 8 workgroups per CU, at most 2048)
+static int lo_stream_grid_cap() {
+  static const int cap = [] {
+    int dev = 0, ncu = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 1) ncu = 256;
+    return ncu * 8 > 2048 ? 2048 : ncu * 8;
+  }();
+  return cap;
+}
+int lo_grad_accumulate_run(float* acc, const float* g, size_t n, float scale, bool first, hipStream_t st) {
+  const uintptr_t pa = reinterpret_cast<uintptr_t>(acc), pg = reinterpret_cast<uintptr_t>(g);
+  LO_REQUIRE(acc && g && n >= 1 && pa % 4 == 0 && pg % 4 == 0, "lo_grad_accumulate: acc and g must be non-null, 4-byte aligned, n >= 1");
+  LO_REQUIRE(pa + 4 * n <= pg || pg + 4 * n <= pa, "lo_grad_accumulate: acc and g overlap");
+  size_t head = ((16 - (pa & 15)) & 15) / 4;
+  if (head > n) head = n;
+  const size_t n4 = (n - head) / 4;
+  const bool gvec = ((pg + 4 * head) & 15) == 0;
+  const size_t want = (n4 + 256 * LO_ACC_UNROLL - 1) / (256 * LO_ACC_UNROLL);
+  const int cap = lo_stream_grid_cap();
+  const dim3 grid(want < 1 ? 1 : (want > (size_t)cap ? cap : (unsigned)want));
+  LoProfScope _p("lo_grad_accumulate", 0, (first ? 8.0 : 12.0) * n, st);
+  if (first) {
+    if (gvec) hipLaunchKernelGGL((lo_grad_accumulate_kernel<true, true>), grid, dim3(256), 0, st, acc, g, head, n4, n, scale);
+    else hipLaunchKernelGGL((lo_grad_accumulate_kernel<true, false>), grid, dim3(256), 0, st, acc, g, head, n4, n, scale);
+  } else {
+    if (gvec) hipLaunchKernelGGL((lo_grad_accumulate_kernel<false, true>), grid, dim3(256), 0, st, acc, g, head, n4, n, scale);
+    else hipLaunchKernelGGL((lo_grad_accumulate_kernel<false, false>), grid, dim3(256), 0, st, acc, g, head, n4, n, scale);
+  }
+  LO_LAUNCH_CHECK("grad_accumulate");
+  return LO_OK;
+}

@@ -136,6 +136,7 @@ struct LoVae {
   // dml^T [2L][Bp], xflat^T [32768][Bp], Gfc^T [32768][Bp], z^T [L][Bp] (one contiguous block), Gram scratch
   LoLinearMode lin_mode = LoLinearMode::off;
   LoFactorStep fac;
+  bool gathered_sum = false;   // lo_vae_set_gathered_sum: the gathered blocks are ADDED (micro-batches of one window), not averaged (ranks)
   int Bp = 0;
   size_t o_fac_dmlT = 0, o_fac_xT = 0, o_fac_gfcT = 0, o_fac_zT = 0, o_gram = 0;
   int n_cu = 0;              // compute units of the device (partition) this plan was made on; 0 = no device: nothing that waits across workgroups is planned
@@ -349,6 +350,8 @@ static inline bool vae_phased_leaves_factors(const LoVae* h) { return h->lin_mod
 static inline int vae_flat_lacks_linear(const LoVae* h) { return vae_opt_from_factors(h) ? (int)h->lin_mode : 0; }
 // Gathered factor blocks (data parallel): every rank's block keeps the workspace's layout dml^T | xflat^T | Gfc^T | z^T.  Elements from
 // one rank's block to the next, and where the factor at workspace offset o_fac sits inside rank 0's block of `gathered`:
+// what multiplies sum_r dY_r^T X_r of `world` gathered blocks: 1 / loss scale, over `world` for the ranks' average
+static inline float vae_gathered_scale(const LoVae* h, int world) { return h->gathered_sum ? h->fac.scale : h->fac.scale / (float)world; }
 static inline size_t vae_fac_block_elems(const LoVae* h) { return (h->o_gram - h->o_fac_dmlT) / 2; }
 static inline const f16* vae_fac_in_block(const LoVae* h, const f16* gathered, size_t o_fac) { return gathered + (o_fac - h->o_fac_dmlT) / 2; }
 

@@ -91,7 +91,7 @@ static LoLinearRanges vae_linear_ranges(const LoVae* h, float* P, float* M, floa
 // AdamW of the two matrices from their factors: this rank's (mode 1) or the `fac.world` gathered blocks, 1 / world folded into the scale
 static int vae_adamw_linear(const LoVae* h, const LoLinearRanges& r, const LoAdamHyper& hp, hipStream_t st) {
   if (!vae_factors_gathered(h)) return lo_adamw_lowrank(r.lrm, 2, h->B, h->fac.scale, hp, st);
-  return lo_adamw_lowrank_gathered(r.lrm, 2, vae_fac_block_elems(h), h->fac.world, h->B, h->fac.scale / (float)h->fac.world, hp, st);
+  return lo_adamw_lowrank_gathered(r.lrm, 2, vae_fac_block_elems(h), h->fac.world, h->B, vae_gathered_scale(h, h->fac.world), hp, st);
 }
 
 // Levels 2..5 of a pipelined optimizer step: AdamW of everything from the encoder's last stage on, in the order the forward needs

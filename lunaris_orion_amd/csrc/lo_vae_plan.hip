@@ -393,6 +393,14 @@ extern "C" size_t lo_vae_gathered_scratch_bytes(const LoVae* h, int world) {
   if (!h || !lo_lowrank_gathered_applies(world, h->B)) return 0;
   return lo_lowrank_gathered_gram_elems(world, h->B) * sizeof(float);
 }
+// Gradient accumulation on one GPU: the k micro-batches of a window are k "ranks" that arrive one after the other, and their
+// gradients -- each already carrying lo_vae_loss's 1 / accum -- are added, not averaged: on != 0 drops the 1 / world from every pass
+// that reads gathered blocks (norm, AdamW tiles, the matrices written out).  Survives lo_vae_set_linear_factored.
+extern "C" int lo_vae_set_gathered_sum(LoVae* h, int on) {
+  LO_REQUIRE(h, "lo_vae_set_gathered_sum: null handle");
+  h->gathered_sum = on != 0;
+  return LO_OK;
+}
 // Called behind the all-gather of the factor blocks AND the exchange of the rest of the phase-1 range, on the stream that ran them:
 // fills scratch[512..1024) the way the single-process backward's early norm does (VaeBackward::early_norm) -- [512, 767) everything
 // behind decoder.fc.weight and [767] the two head biases from the AVERAGED flat buffer, [768, 896) and [896, 1024) the two matrices
@@ -418,7 +426,7 @@ extern "C" int lo_vae_gathered_early_norm(LoVae* h, const void* gathered, int wo
   const LoLowrankNorm nl[2] = {
       {vae_fac_in_block(h, base, h->o_fac_dmlT), 2 * L, vae_fac_in_block(h, base, h->o_fac_xT), 32768, gram_scratch, scratch + 768, 128},
       {vae_fac_in_block(h, base, h->o_fac_zT), L, vae_fac_in_block(h, base, h->o_fac_gfcT), 32768, gram_scratch + kt * kt, scratch + 896, 128}};
-  LO_TRY(lo_lowrank_sumsq_gathered(nl, 2, vae_fac_block_elems(h), world, h->B, h->fac.scale / (float)world, st));
+  LO_TRY(lo_lowrank_sumsq_gathered(nl, 2, vae_fac_block_elems(h), world, h->B, vae_gathered_scale(h, world), st));
   h->fac.gathered = base;
   h->fac.world = world;
   h->fac.ready = true;
@@ -440,7 +448,7 @@ extern "C" int lo_vae_materialize_gathered_linear_grads(LoVae* h, const void* ga
   const int L = h->L;
   const size_t blk = vae_fac_block_elems(h);
   const f16* base = reinterpret_cast<const f16*>(gathered);
-  const float sc = h->fac.scale / (float)world;
+  const float sc = vae_gathered_scale(h, world);
   LO_TRY(lo_lowrank_materialize_gathered(G + h->p_off[h->idx_fc_mu_w], vae_fac_in_block(h, base, h->o_fac_xT), vae_fac_in_block(h, base, h->o_fac_dmlT),
                                          blk, world, 2 * L, 32768, h->B, sc, st));
   return lo_lowrank_materialize_gathered(G + h->p_off[h->idx_dfc_w], vae_fac_in_block(h, base, h->o_fac_zT), vae_fac_in_block(h, base, h->o_fac_gfcT),

@@ -10,7 +10,9 @@ What is mirrored, line by line:
   :886-889  vae_loss             -> (recon_weight - mean_advantage)*MSE + kl_weight*KL   (pg_loss = -mean(adv)*MSE)
   :895      / accumulation steps
   :907      optimizer steps only when (batch_idx+1) % accum == 0 — with the reference's zero_grad placement the
-            gradients of the other micro-batches are discarded, so their backward is skipped here
+            gradients of the other micro-batches are discarded, so their backward is skipped here.  Opt-in,
+            ``accumulate_gradients=True``: every micro-batch of a window takes its backward and the step sees their sum
+            (lo_grad_accumulate) -- what the flag's name promises; off, nothing changes
   :913      clip_grad_norm_(max_grad_norm)   :921 AdamW(lr, wd=0.01, betas=(0.9,0.999))   :925 scheduler.step()
 The teacher's contribution is the detached scalar ``mean_advantage``; it is an input here.
 """
@@ -84,6 +86,38 @@ class LossScalePolicy:
         return scale
 
 
+class AccumulationWindow:
+    """Host bookkeeping of ``accumulate_gradients=True``: which of the k micro-batches of a window a call is.
+
+    A window is the k consecutive calls that start at ``batch_idx % k == 0``; its last call, ``(batch_idx + 1) % k == 0``, is the one
+    that steps (train_hybrid.py:907).  A call with ``batch_idx % k == 0`` always starts a new window and whatever an incomplete one
+    had gathered is dropped (the end of an epoch whose length is no multiple of k).  A call that finds no window open starts one
+    wherever it is (a run that begins in the middle of an epoch): that window is shorter than k and still ends at the reference's
+    step.  ``advance`` returns (first, last, slot): slot = how many micro-batches of this window came before."""
+
+    def __init__(self, k: int):
+        self.k = max(1, int(k))
+        self.count = 0          # micro-batches the open window holds; 0 = none open
+
+    @property
+    def open(self) -> bool:
+        return self.count > 0
+
+    def advance(self, batch_idx: int):
+        first = batch_idx % self.k == 0 or self.count == 0
+        slot = 0 if first else self.count
+        if slot >= self.k:
+            self.count = 0
+            raise ValueError(f"accumulate_gradients: more than {self.k} calls without the end of a window (batch_idx {batch_idx}); "
+                             "batch_idx must count the micro-batches of an epoch from 0")
+        last = (batch_idx + 1) % self.k == 0
+        self.count = 0 if last else slot + 1
+        return first, last, slot
+
+    def drop(self) -> None:
+        self.count = 0
+
+
 class VAEStepper:
     _DP_LAG = 2     # data parallel: an observation is evaluated this many optimizer steps after it was enqueued
 
@@ -91,8 +125,12 @@ class VAEStepper:
                  weight_decay: float = 0.01, max_grad_norm: float = 1.0, recon_weight: float = 1.0, kl_weight: float = 0.1,
                  gradient_accumulation_steps: int = 1, betas=(0.9, 0.999), eps: float = 1e-8,
                  grad_sync: Optional[Callable[[torch.Tensor], None]] = None, pipeline_optimizer: bool = False,
-                 dp_factored_adamw: Optional[bool] = None):
+                 dp_factored_adamw: Optional[bool] = None, accumulate_gradients: bool = False):
         _lib.require_gpu()
+        if accumulate_gradients and grad_sync is not None and (int(getattr(grad_sync, "world", 1)) > 1 or getattr(grad_sync, "force", False)):
+            # accumulation under data parallel (one exchange of the accumulated buffers per window, k * world factor blocks) is not
+            # built; an exchange object of one rank averages nothing and is not called in the mode
+            raise NotImplementedError("accumulate_gradients=True is single process only (grad_sync with world > 1 is not built)")
         if getattr(vae, "attention", False) and grad_sync is not None and int(getattr(grad_sync, "world", 1)) > 1:
             # the exchange ranges, the factor all-gather and the gathered-factor optimizer have never been run with the 86-tensor
             # layout: not offered untested
@@ -145,6 +183,17 @@ class VAEStepper:
         self._skip_inflight = []      # (event, pinned slot, optimizer-step index), oldest first
         self._last_engine = None
         self._presummed_begin: Optional[int] = None   # set by a backward that left the early part of the gradient norm in the scratch
+        # accumulate_gradients (opt-in; off: nothing below is touched): every micro-batch of a window takes its backward and the
+        # window's last call steps on the sum -- `self.grads` is the accumulator, the first micro-batch's backward writes straight
+        # into it, the others write `_stage` and lo_grad_accumulate adds them.  The two Linear matrices, while the factored mode
+        # applies, are kept as one factor block per micro-batch (`_fac_slots`) and never written out: the gathered-factor passes of
+        # the data-parallel mode 3 read them, told to add instead of average (lo_vae_set_gathered_sum).
+        self.accumulate = bool(accumulate_gradients)
+        self._window = AccumulationWindow(self.accum) if self.accumulate else None
+        self._win_batch = 0             # batch size of the open window
+        self._stage: Optional[torch.Tensor] = None
+        self._fac_slots = {}            # batch -> accum factor blocks, slot i = micro-batch i of the window
+        self._deferred_scale = []       # loss-scale observations made inside a window (metrics()): evaluated at its end
 
     @property
     def lr(self) -> float:
@@ -155,14 +204,20 @@ class VAEStepper:
         """One micro-batch.  Returns (recon, mu, logvar); losses stay on the device in ``self.losses``."""
         vae = self.vae
         images = images.detach().contiguous().float()
+        first, last, slot = self._window_advance(images.shape[0], batch_idx)
         recon, mu, logvar, eng = vae._native_forward(images, eps, target=images)
         st = _lib.stream_ptr()
         _lib.check(_lib.lib.lo_vae_loss(eng.handle, eng.ws.data_ptr(), self.recon_weight, self.kl_weight, float(mean_advantage),
-                                        _lib.ptr(adv_dev), float(self.accum), float(vae.loss_scale), self.losses.data_ptr(), st),
+                                        _lib.ptr(adv_dev), float(self.accum), self._chain_loss_scale(), self.losses.data_ptr(), st),
                    "lo_vae_loss")
-        if (batch_idx + 1) % self.accum == 0:
+        if self.accumulate:
+            self._backward_accumulating(eng, images, recon, st, None, first, slot)
+        if last:
             flat = vae._flat
-            self._backward_and_exchange(eng, images, recon, st)
+            if self.accumulate:
+                self._finish_window(eng, slot + 1, st)
+            else:
+                self._backward_and_exchange(eng, images, recon, st)
             lr = self.lr
             self.opt_steps += 1
             self._clip_adamw(flat, lr, st, eng)
@@ -170,11 +225,102 @@ class VAEStepper:
         self.last = (recon, mu, logvar)
         return recon, mu, logvar
 
+    # ---- gradient accumulation (accumulate_gradients=True) ------------------------------------------------------------------------
+    def _window_advance(self, batch: int, batch_idx: int):
+        """(first, last, slot) of this call.  Off: every call is its own "window" and `last` is the reference's step rule.  On: the
+        position in the window (`AccumulationWindow`); a new window first lets the loss-scale policy see what was observed inside the
+        previous one, so that the scale it runs at is fixed before its first lo_vae_loss."""
+        if not self.accumulate:
+            return True, (batch_idx + 1) % self.accum == 0, 0
+        first, last, slot = self._window.advance(batch_idx)
+        if first:
+            self._apply_deferred_scale()
+            self._win_batch = batch
+        elif batch != self._win_batch:
+            self._window.drop()
+            raise ValueError(f"accumulate_gradients: every micro-batch of a window must have the same batch size (window of {self._win_batch}, "
+                             f"got {batch} at batch_idx {batch_idx})")
+        return first, last, slot
+
+    def _window_factored(self, eng) -> bool:
+        """The two Linear matrices of a window stay factor blocks: the factored mode is on, the batch is within its rank (128), the
+        combined rank accum * padded batch is within what the gathered passes hold (512), and the model is the 72-tensor one (the
+        gathered passes have never run with the attention layout).  Otherwise they are accumulated like every other gradient."""
+        return (self.linear_factored and eng.batch <= 128 and not getattr(self.vae, "attention", False)
+                and _lib.lib.lo_vae_gathered_scratch_bytes(eng.handle, self.accum) > 0)
+
+    def _accumulate(self, acc: torch.Tensor, g: torch.Tensor, begin: int, end: int, st) -> None:
+        """acc[begin:end] += g[begin:end] (lo_grad_accumulate; each micro-batch's gradients already carry 1 / accum)."""
+        if end > begin:
+            _lib.check(_lib.lib.lo_grad_accumulate(acc.data_ptr() + 4 * begin, g.data_ptr() + 4 * begin, end - begin, 1.0, 0, st),
+                       "lo_grad_accumulate")
+
+    def _backward_accumulating(self, eng, images: torch.Tensor, recon: torch.Tensor, st, drecon: Optional[torch.Tensor], first: bool,
+                               slot: int) -> None:
+        """One micro-batch's backward into the window's accumulator `self.grads`: the first writes it (every element: nothing of an
+        earlier window survives), the others write the staging buffer and are added.  Factored: the phased backward (data-parallel
+        mode 3) leaves this micro-batch's factor block, which is copied to its slot; the two matrices are in neither buffer.  No
+        backward of a window takes any part of the gradient norm (no scratch set): the norm is that of the sum, taken at the end."""
+        vae = self.vae
+        self._last_engine = eng
+        if not first and self._stage is None:
+            self._stage = torch.zeros_like(self.grads)
+        G = self.grads if first else self._stage
+        bargs = (images.data_ptr(), vae._flat.data_ptr(), eng.ws.data_ptr(), recon.data_ptr(), images.data_ptr(),
+                 1 if drecon is None else 2, _lib.ptr(drecon), None, None, self._chain_loss_scale(), G.data_ptr(), st)
+        _lib.check(_lib.lib.lo_vae_set_gradnorm_scratch(eng.handle, None), "lo_vae_set_gradnorm_scratch")
+        n = self.grads.numel()
+        if self._window_factored(eng):
+            _set_linear_mode(eng, 3)
+            _lib.check(_lib.lib.lo_vae_set_gathered_sum(eng.handle, 1), "lo_vae_set_gathered_sum")
+            _lib.check(_lib.lib.lo_vae_set_async_handover(eng.handle, 0), "lo_vae_set_async_handover")
+            _lib.check(_lib.lib.lo_vae_backward_phase(eng.handle, 1, *bargs), "lo_vae_backward_phase(1)")
+            _lib.check(_lib.lib.lo_vae_backward_phase(eng.handle, 2, *bargs), "lo_vae_backward_phase(2)")
+            fo, fb = _grad_range(eng, "lo_vae_factor_block")
+            self._factor_slots(eng, fb)[slot * fb:(slot + 1) * fb].copy_(eng.ws[fo:fo + fb])
+            h_end, d_beg, d_end = self._linear_matrix_bounds(eng)
+            ranges = ((0, _grad_range(eng, "lo_vae_linear_grad_range")[0]), (h_end, d_beg), (d_end, n))
+        else:
+            _set_linear_mode(eng, 0)
+            _lib.check(_lib.lib.lo_vae_backward(eng.handle, *bargs), "lo_vae_backward")
+            ranges = ((0, n),)
+        if not first:
+            for b, e in ranges:
+                self._accumulate(self.grads, G, b, e, st)
+
+    def _factor_slots(self, eng, block_bytes: int) -> torch.Tensor:
+        if eng.batch not in self._fac_slots:
+            self._fac_slots[eng.batch] = _alloc_scratch(self.accum * block_bytes, eng.ws.device)
+        return self._fac_slots[eng.batch]
+
+    def _finish_window(self, eng, filled: int, st) -> None:
+        """Behind the window's last backward: factored, the norm's share of everything from fc_mu.weight on -- the accumulated flat
+        buffer, and the Gram matrices of the `filled` factor blocks for the two matrices, cross terms between micro-batches included
+        -- goes to scratch[512..1024) and the blocks are left to the optimizer step; materialised, that step takes the whole norm."""
+        if not self._window_factored(eng):
+            return
+        fb = _grad_range(eng, "lo_vae_factor_block")[1]
+        self._norm_of_gathered(eng, self._factor_slots(eng, fb)[:filled * fb], filled)
+        self._presummed_begin = _grad_range(eng, "lo_vae_phase1_grad_range")[0]
+
+    def _chain_loss_scale(self) -> float:
+        """The loss scale lo_vae_loss's seeds, the reward term and the backward are given.  Off: the model's.  On: times accum -- the
+        seeds carry 1 / accum, and with the scale raised by as much the fp16 activation gradients of every micro-batch are the ones a
+        plain step at accumulation 1 carries (no 1 / k taken out of fp16's range, the same roundings for a k that is no power of two);
+        the backward's fp32 `1 / scale` applies the 1 / accum instead.  One value for a whole window (`_update_loss_scale`)."""
+        return float(self.vae.loss_scale) * (self.accum if self.accumulate else 1)
+
+    def _apply_deferred_scale(self) -> None:
+        pending, self._deferred_scale = self._deferred_scale, []
+        for skipped_total, at in pending:
+            self.vae.loss_scale = self._scale_policy.observe(self.vae.loss_scale, skipped_total, at, self.opt_steps)
+
     def _observe_skipped_updates(self) -> None:
         """Runs the loss-scale policy every optimizer step (the reference's GradScaler.update(), train_hybrid.py:917-923) with no
         host synchronisation in the single-process case: the skipped-update counter of the step just enqueued travels to pinned
         memory behind it; whichever earlier copy has landed by now is evaluated.  The host runs a step or two ahead of the GPU, so
         an overflow is answered after that many skipped updates — not after `--log_every` of them, as when only metrics() looked."""
+        self._apply_deferred_scale()      # accumulate_gradients: what metrics() saw inside the window that has just ended
         dp = self.grad_sync is not None and getattr(self.grad_sync, "world", 1) > 1
         if dp:
             # fixed lag: wait for the observation of `_DP_LAG` steps ago (long finished unless the host runs further ahead than that)
@@ -367,6 +513,11 @@ class VAEStepper:
     def _update_loss_scale(self, skipped_total: float, observed_after_step: Optional[int] = None) -> None:
         """Feed one observation of the device's skipped-update counter to the loss-scale policy (`LossScalePolicy`)."""
         at = self.opt_steps if observed_after_step is None else int(observed_after_step)
+        if self.accumulate and self._window.open:
+            # every micro-batch of a window runs at ONE loss scale (its factor blocks share one 1 / scale; the accumulator adds
+            # un-scaled gradients of one scale's fp16 range): the policy runs at optimizer steps only
+            self._deferred_scale.append((int(skipped_total), at))
+            return
         self.vae.loss_scale = self._scale_policy.observe(self.vae.loss_scale, int(skipped_total), at, self.opt_steps)
 
     def metrics(self) -> Dict[str, float]:
@@ -404,7 +555,11 @@ class VAEStepper:
 
     def parameter_grads(self):
         """Views of the flat gradient buffer, one per parameter (state_dict order).  In the factored mode the two Linear weight
-        gradients of the last step are written out first (`lo_vae_materialize_linear_grads`: the tiles the AdamW pass formed)."""
+        gradients of the last step are written out first (`lo_vae_materialize_linear_grads`: the tiles the AdamW pass formed).
+        With ``accumulate_gradients`` these are the gradients accumulated over the last COMPLETE window (the matrices from its factor
+        blocks); inside a window the buffers are half-filled and asking for them is an error."""
+        if self.accumulate and self._window.open:
+            raise RuntimeError("accumulate_gradients: the gradients are complete after the last call of a window, not inside one")
         for eng in self.vae._engines.values():
             if eng is self._last_engine and _lib.lib.lo_vae_linear_factored(eng.handle):
                 _lib.check(_lib.lib.lo_vae_materialize_linear_grads(eng.handle, eng.ws.data_ptr(), self.grads.data_ptr(), _lib.stream_ptr()),
@@ -450,6 +605,7 @@ class HybridStepper(VAEStepper):
         self.adv_dev = torch.zeros(1, dtype=torch.float32, device=dev)
         self.reward_grad_out = torch.zeros(2, dtype=torch.float32, device=dev)   # reward term of vae_loss, mean(q_eval)
         self.seed_coef = torch.zeros(1, dtype=torch.float32, device=dev)         # un-scaled MSE coefficient of d vae_loss / d recon
+        self._t_stage = None                     # accumulate_gradients: the teacher gradients of micro-batches 2..k before they are added
         self._t_ready = False                    # t_range, t_grads, t_m, t_v, t_scratch exist (_teacher_setup)
         self._pending_teacher_opt = None         # a checkpoint's teacher optimizer state until then (hostside.restore_checkpoint)
         self.last_teacher_out = None             # outputs of the last train-mode teacher(recon)
@@ -482,12 +638,15 @@ class HybridStepper(VAEStepper):
         images = images.detach().contiguous().float()
         B = images.shape[0]
         st = _lib.stream_ptr()
+        # accumulate_gradients: every micro-batch of a window takes its gradients (VAE and teacher), the window's last call steps
+        first, last, slot = self._window_advance(B, batch_idx)
+        takes_grads = last or self.accumulate
         recon, mu, logvar, eng = vae._native_forward(images, eps, target=images)
         if self.run_dead_teacher_call:
             t.update_statistics_only(images)            # train_hybrid.py:853-855 (side effects only)
         # train_hybrid.py:865 (no autograd node: the head gradients are taken below).  Full-backward mode: the plain forward that keeps
-        # every block's output for lo_teacher_full_backward (only on the micro-batch whose gradients are used)
-        tout = t._native_forward(recon, mode="keep" if self.teacher_full_backward and (batch_idx + 1) % self.accum == 0 else "auto")[0]
+        # every block's output for lo_teacher_full_backward (only on the micro-batches whose gradients are used)
+        tout = t._native_forward(recon, mode="keep" if self.teacher_full_backward and takes_grads else "auto")[0]
         self.last_teacher_out = tout
         self._teacher_setup(B)
         q_rows, s_rows, n_rows = tout["quality_scores"], tout["semantic_score"], B
@@ -504,23 +663,31 @@ class HybridStepper(VAEStepper):
                                              float(self.quality_weight), float(self.accum), self.reward_state.data_ptr(),
                                              self.reward_out.data_ptr(), self.adv_dev.data_ptr(), st), "lo_hybrid_reward")
         _lib.check(_lib.lib.lo_vae_loss(eng.handle, eng.ws.data_ptr(), self.recon_weight, self.kl_weight, 0.0, self.adv_dev.data_ptr(),
-                                        float(self.accum), float(vae.loss_scale), self.losses.data_ptr(), st), "lo_vae_loss")
-        if (batch_idx + 1) % self.accum == 0:
-            flat = vae._flat
-            drecon = None
+                                        float(self.accum), self._chain_loss_scale(), self.losses.data_ptr(), st), "lo_vae_loss")
+        drecon = None
+        if takes_grads:
             if self.reward_grad_weight > 0:
                 # the eval forward below overwrites what the teacher's own backward reads (the kept train-mode tensors in bws, the
                 # pooled features and logits in ws, the call's dropout stream): its gradients are taken first, its update stays last
-                self._teacher_grads(t, recon, tout)
+                self._teacher_grads(t, recon, tout, first)
                 drecon = self._reward_grad_seed(t, eng, images, recon, st)
-            self._backward_and_exchange(eng, images, recon, st, drecon)     # data parallel: exchange overlapped with the backward
+            if self.accumulate:
+                self._backward_accumulating(eng, images, recon, st, drecon, first, slot)
+            if not last and drecon is None:
+                self._teacher_grads(t, recon, tout, first)
+        if last:
+            flat = vae._flat
+            if self.accumulate:
+                self._finish_window(eng, slot + 1, st)
+            else:
+                self._backward_and_exchange(eng, images, recon, st, drecon)     # data parallel: exchange overlapped with the backward
             lr = self.lr
             t_lr = cosine_warm_restarts_lr(self.teacher_base_lr, self.min_lr, self.t0, 2, self.opt_steps)
             self.opt_steps += 1
             self._clip_adamw(flat, lr, st, eng)
             self._observe_skipped_updates()
             if drecon is None:
-                self._teacher_grads(t, recon, tout)
+                self._teacher_grads(t, recon, tout, first)
             if self.teacher_full_backward:
                 self._teacher_full_update(t, recon, t_lr, st)
                 self.last = (recon, mu, logvar)
@@ -538,15 +705,27 @@ class HybridStepper(VAEStepper):
         self.last = (recon, mu, logvar)
         return recon, mu, logvar
 
-    def _teacher_grads(self, t, recon, tout) -> None:
+    def _teacher_grads(self, t, recon, tout, first: bool = True) -> None:
         """teacher_loss.backward() into ``self.t_grads`` (train_hybrid.py:891-904): the gate and the quality heads
         (`heads_backward`), or with ``teacher_full_backward`` every parameter on the loss path (`full_backward` on the evaluated images,
-        under non-reentrant checkpoints).  Reads what the train-mode teacher(recon) of this step left."""
+        under non-reentrant checkpoints).  Reads what the train-mode teacher(recon) of this step left.  first = False
+        (``accumulate_gradients``, micro-batches 2..k of a window): into the staging buffer, then added to ``t_grads`` over `t_range`
+        (both backwards write every element of it)."""
         coef = float(self.quality_weight) / float(self.accum)
+        if not first and self._t_stage is None:
+            self._t_stage = torch.zeros_like(self.t_grads)
+        out = self.t_grads if first else self._t_stage
         if self.teacher_full_backward:
-            t.full_backward(recon, tout["expert_weights"], coef, out=self.t_grads)
+            # accumulate_gradients: the fp16 activation gradients stay where a plain step's are (coef carries 1 / accum, gscale gives
+            # it back; the fp32 parameter gradients come out un-scaled either way) -- at gscale alone the smallest of them, in the
+            # feature extractor, lose bits to fp16's subnormal range: 1e-4 on its first conv's gradient at accum = 2
+            from .teacher import loss_gscale
+            gscale = loss_gscale(recon.shape[0]) * self.accum if self.accumulate else None
+            t.full_backward(recon, tout["expert_weights"], coef, gscale=gscale, out=out)
         else:
-            t.heads_backward(tout["expert_weights"], coef, out=self.t_grads)
+            t.heads_backward(tout["expert_weights"], coef, out=out)
+        if not first:
+            self._accumulate(self.t_grads, out, *self.t_range, _lib.stream_ptr())
 
     def _reward_grad_seed(self, t, eng, images, recon, st) -> torch.Tensor:
         """The reward pass of a ``reward_grad_weight`` step, after lo_vae_loss: the teacher in EVAL mode on recon (running statistics,
@@ -565,7 +744,7 @@ class HybridStepper(VAEStepper):
         rg = self._rg
         teng = t._native_forward(recon, mode="keep_eval", out=rg["out"])[1]
         _lib.check(_lib.lib.lo_vae_reward_term(eng.handle, eng.ws.data_ptr(), rg["q"].data_ptr(), self.reward_grad_weight, float(self.accum),
-                                               float(self.vae.loss_scale), self.losses.data_ptr(), self.reward_grad_out.data_ptr(),
+                                               self._chain_loss_scale(), self.losses.data_ptr(), self.reward_grad_out.data_ptr(),
                                                self.seed_coef.data_ptr(), st), "lo_vae_reward_term")
         t._native_backward(teng, "eval_full", recon, teng.saved_views(), rg["w"], rg["up"], None, (0.0, 0), None, rg["seed"],
                            seed=(images, self.seed_coef, self.reward_grad_weight / (8.0 * B * float(self.accum))))

@@ -93,6 +93,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="the VAE also climbs the frozen teacher's quality score: vae_loss -= W * mean(quality_scores of the teacher in eval mode "
                         "on the reconstruction, not detached) / accumulation steps; the teacher's parameters are constants in the term and its "
                         "own training is unchanged.  0 = off (the reference's objective).  Needs the teacher: not with --vae_only")
+    p.add_argument("--accumulate_gradients", action="store_true",
+                   help="real gradient accumulation: every micro-batch of a window of --gradient_accumulation_steps takes its backward and the "
+                        "window's last one steps on the sum (the gradient of the mean micro-loss), VAE and teacher alike; off = the reference's "
+                        "rule, which steps on the last micro-batch alone (train_hybrid.py:841-842, 907).  Single process only.  Checkpoints are "
+                        "taken as without the flag: a window that is still open is not part of a checkpoint, a resumed run starts a new one")
     return p
 
 
@@ -166,7 +171,11 @@ def main(argv=None):
     common = dict(lr=args.vae_lr, min_lr=args.min_lr, scheduler_t0=args.scheduler_t0, weight_decay=args.weight_decay,
                   max_grad_norm=args.max_grad_norm, recon_weight=args.recon_weight, kl_weight=args.kl_weight,
                   gradient_accumulation_steps=args.gradient_accumulation_steps, grad_sync=grad_sync,
-                  pipeline_optimizer=True)     # Linear / decoder update beside the next encoder forward; checkpoints synchronise first
+                  pipeline_optimizer=True,     # Linear / decoder update beside the next encoder forward; checkpoints synchronise first
+                  accumulate_gradients=args.accumulate_gradients)
+    if args.accumulate_gradients:
+        log.info(f"gradient accumulation on: every update sees {args.gradient_accumulation_steps} micro-batches of {args.batch_size} "
+                 f"(effective batch {args.gradient_accumulation_steps * args.batch_size})")
     teacher = None
     if teacher_on:
         from lunaris_orion_amd.teacher import LunarMoETeacher
