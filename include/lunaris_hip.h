@@ -136,6 +136,35 @@ int lo_final_conv_backward(const void* a4, const float* w, const float* recon, c
  * uint8 HWC [B,128,128,3] -> float32 CHW [B,3,128,128] = x/127.5 - 1. */
 int lo_decode_sprites_u8(const void* u8_hwc, float* out_chw, int B, void* stream);
 
+/* The latent / loss passes of the step as single ops: each is the launcher lo_vae_forward / lo_vae_loss / lo_vae_backward call, on
+ * plain pointers (tests/test_train_ops_gpu.py).
+ * lo_reparam_noise: out[i] (n floats), i < n = the N(0,1) sample lo_vae_forward(eps = NULL, seed) applies to flat latent element
+ * first + i (b * latent_dim + l): the counter generator of the reparameterisation (torch.randn_like, lunar_generate.py:259-261), a
+ * 64-bit hash of (seed, index) into two 24-bit uniforms and one Box-Muller cosine branch; |out| <= sqrt(-2 ln 2^-25) = 5.89.
+ * oracle/noise_ref.py restates it.
+ * lo_latent_forward_op (fc_mu | fc_logvar split-K reduction + reparameterisation + KL partial sums; lunar_generate.py:124-125,
+ * 150-152,259-261; train_hybrid.py:862): slab nsplit*B*2L floats ([nsplit][B][mu | logvar]), bias 2L; eps_in B*L floats or NULL
+ * (then the generator above with `seed`); out: mu, logvar, eps_out B*L floats each, z B*L halves = fp16(mu + eps * exp(logvar / 2)),
+ * kl_partial ceil(B*L / 256) floats, each the sum of 1 + logvar - mu^2 - exp(logvar) over 256 consecutive elements; mu_user /
+ * logvar_user: both NULL, or B*L floats each receiving copies of mu / logvar.
+ * lo_latent_backward_op: dz B*L halves; mu, logvar, eps B*L floats; coefs NULL or 2 floats ([1] = the KL coefficient c:
+ * dmu = c * mu + dz, dlogvar = c/2 * (exp(logvar) - 1) + dz * eps/2 * exp(logvar / 2)); gmu / glv NULL or B*L floats, added times
+ * gscale; dml B*2L halves = per sample [dmu | dlogvar].
+ * lo_loss_finalize_op: mse_partial n_mse floats, kl_partial n_kl floats (summed in double, fixed order); adv_dev NULL or 1 float
+ * overriding mean_advantage; losses 4 floats = recon (sum mse / n_rec), kl (-0.5 sum kl / n_lat), (rw * recon + kw * kl + pg) / accum,
+ * pg = -adv * recon; coefs 2 floats = loss_scale * (rw - adv) / accum * 2 / n_rec, loss_scale * kw / accum / n_lat.
+ * lo_colsum_f16_op: x M*N halves, out N floats: out[j] = scale * sum_m x[m][j] (the Linear layers' bias gradients; fp32 sums in a
+ * fixed order); N a multiple of 8, else -1. */
+int lo_reparam_noise(uint64_t seed, size_t first, size_t n, float* out, void* stream);
+int lo_latent_forward_op(const float* slab, const float* bias, const float* eps_in, uint64_t seed, float* mu, float* logvar, void* z,
+                         float* eps_out, float* kl_partial, int B, int L, int nsplit, float* mu_user, float* logvar_user, void* stream);
+int lo_latent_backward_op(const void* dz, const float* mu, const float* logvar, const float* eps, const float* coefs, const float* gmu,
+                          const float* glv, float gscale, void* dml, int B, int L, void* stream);
+int lo_loss_finalize_op(const float* mse_partial, int n_mse, const float* kl_partial, int n_kl, float recon_weight, float kl_weight,
+                        float mean_advantage, const float* adv_dev, float accum, float loss_scale, float* losses, float* coefs,
+                        float n_rec, float n_lat, void* stream);
+int lo_colsum_f16_op(const void* x, float* out, int M, int N, float scale, void* stream);
+
 /* SelfAttention2d.forward (lunar_generate.py:68-78; the module is defined but never instantiated by the reference):
  * out = gamma * (V softmax(Q^T K)^T) + x with Q,K = 1x1 convs to C/8 channels, V = 1x1 conv to C channels.  x/out fp32
  * [B,C,N=H*W]; q,k ([B,C/8,N]) and v ([B,C,N]) are caller-provided scratch/outputs.  C and N multiples of 64, C <= 512. */
@@ -220,7 +249,9 @@ int lo_vae_set_gradnorm_scratch(LoVae* h, float* scratch);
 /* The same partial sum for a caller that exchanges gradients between processes (data parallel: the norm is that of the AVERAGED
  * gradients, so the library cannot take it inside the backward): sum of squares of flat_grads[begin, end) into scratch[512..1024),
  * to be enqueued behind the exchange of that range, on whatever stream ran it; lo_clip_adamw_step_presummed / the `presummed` form
- * of lo_vae_optimizer_step then read only [0, begin).  clip_grad_norm_'s norm (train_hybrid.py:913), split in two. */
+ * of lo_vae_optimizer_step then read only [0, begin).  clip_grad_norm_'s norm (train_hybrid.py:913), split in two.  The pass issues
+ * 16-byte loads from flat_grads + begin on: begin must be a multiple of 4 elements (every range the library names starts at a multiple
+ * of 64); any other begin returns -1 with a message and launches nothing.  end is free (the last (end - begin) % 4 elements are read singly). */
 int lo_gradnorm_early_range(const float* flat_grads, size_t begin, size_t end, float* scratch, void* stream);
 /* Asynchronous hand-over of the phased backward's gradient ranges (data parallel).  By default lo_vae_backward_phase(1) and (3)
  * return with `stream` ordered behind everything that writes their range (the library's side stream is joined).  With on = 1 they
@@ -376,7 +407,10 @@ int lo_vae_sync_fail_word(const LoVae* h, size_t* byte_offset, int* fused_layers
  * unscale_, clip_grad_norm_, step).  The upstream gradients an autograd node receives are already multiplied by the caller's loss
  * scale; the backward carries fp16 activation gradients and needs them in a fixed range.  lo_grad_scale_pick: max |g| over up to five
  * fp32 tensors (NULL = absent) -> scratch[0] = r = 2^k with max|g| * r in [2, 4), scratch[1] = 1 / r, scratch[2] = max |g|
- * (scratch: >= 260 floats, device memory; no host synchronisation).  lo_scale_copy_dev: dst = src * scale_dev[0].
+ * (scratch: >= 260 floats, device memory; no host synchronisation).  All-zero gradients, or an infinite one, give r = 1.  NaN
+ * elements do not enter the maximum (it is taken with fmaxf, which returns its other operand): r, 1 / r and scratch[2] are those of
+ * the remaining elements -- r = 1 when nothing else is non-zero -- and the NaN itself reaches the parameter gradients through
+ * lo_scale_copy_dev, where GradScaler.unscale_ finds it.  lo_scale_copy_dev: dst = src * scale_dev[0].
  * lo_grad_unscale_dev: x *= scale_dev[0] in place; fail_word (may be NULL): the plan's rendezvous-failure word -- when it is set
  * the result is NaN instead, which is how a lost launch reaches a foreign training loop (GradScaler.unscale_ /
  * clip_grad_norm_ see it; there is no optimizer kernel of this library behind the autograd path that could skip the update). */

@@ -53,7 +53,12 @@ SIGNATURES = {
     "lo_final_conv_forward": (i32, [vp, f32p, f32p, f32p, f32p, f32p, i32, vp]),
     "lo_final_conv_backward": (i32, [vp, f32p, f32p, f32p, f32p, f32p, flt, vp, f32p, f32p, f32p, i32, flt, vp]),
     "lo_decode_sprites_u8": (i32, [vp, f32p, i32, vp]),
-    "lo_selfattn2d_forward": (i32, [f32p] * 12 + [i32, i32, i32, vp]),
+    "lo_reparam_noise": (i32, [u64, sz, sz, f32p, vp]),
+    "lo_latent_forward_op": (i32, [f32p, f32p, f32p, u64, f32p, f32p, vp, f32p, f32p, i32, i32, i32, f32p, f32p, vp]),
+    "lo_latent_backward_op": (i32, [vp, f32p, f32p, f32p, f32p, f32p, f32p, flt, vp, i32, i32, vp]),
+    "lo_loss_finalize_op": (i32, [f32p, i32, f32p, i32, flt, flt, flt, f32p, flt, flt, f32p, f32p, flt, flt, vp]),
+    "lo_colsum_f16_op": (i32, [vp, f32p, i32, i32, flt, vp]),
+    "lo_selfattn2d_forward":(i32, [f32p] * 12 + [i32, i32, i32, vp]),
     "lo_selfattn2d_backward_scratch_elems": (C.c_size_t, [i32, i32, i32]),
     "lo_selfattn2d_backward": (i32, [f32p] * 18 + [i32, i32, i32, vp]),
     "lo_attn8_forward": (i32, [vp, vp, f32p, vp, i32, vp]),

@@ -173,6 +173,35 @@ extern "C" int lo_decode_sprites_u8(const void* u8_hwc, float* out_chw, int B, v
   return lo_decode_sprites((const uint8_t*)u8_hwc, out_chw, B, S(stream));
 }
 
+// op level: the latent / loss / column-sum launchers of the step (lo_train.hip) and its noise generator, as the executor calls them
+extern "C" int lo_reparam_noise(uint64_t seed, size_t first, size_t n, float* out, void* stream) {
+  LO_REQUIRE(out && n > 0, "lo_reparam_noise: bad argument");
+  return lo_randn_fill(seed, first, n, out, S(stream));
+}
+extern "C" int lo_latent_forward_op(const float* slab, const float* bias, const float* eps_in, uint64_t seed, float* mu, float* logvar,
+                                    void* z, float* eps_out, float* kl_partial, int B, int L, int nsplit, float* mu_user,
+                                    float* logvar_user, void* stream) {
+  LO_REQUIRE(slab && bias && mu && logvar && z && eps_out && kl_partial && B > 0 && L > 0 && nsplit > 0 && !mu_user == !logvar_user,
+             "lo_latent_forward_op: bad argument");
+  return lo_head_reduce(slab, bias, eps_in, seed, mu, logvar, (f16*)z, eps_out, kl_partial, B, L, nsplit, S(stream), mu_user, logvar_user);
+}
+extern "C" int lo_latent_backward_op(const void* dz, const float* mu, const float* logvar, const float* eps, const float* coefs,
+                                     const float* gmu, const float* glv, float gscale, void* dml, int B, int L, void* stream) {
+  LO_REQUIRE(dz && mu && logvar && eps && dml && B > 0 && L > 0, "lo_latent_backward_op: bad argument");
+  return lo_latent_bwd((const f16*)dz, mu, logvar, eps, coefs, gmu, glv, gscale, (f16*)dml, B, L, S(stream));
+}
+extern "C" int lo_loss_finalize_op(const float* mse_partial, int n_mse, const float* kl_partial, int n_kl, float recon_weight,
+                                   float kl_weight, float mean_advantage, const float* adv_dev, float accum, float loss_scale,
+                                   float* losses, float* coefs, float n_rec, float n_lat, void* stream) {
+  LO_REQUIRE(mse_partial && kl_partial && losses && coefs && n_mse > 0 && n_kl > 0, "lo_loss_finalize_op: bad argument");
+  return lo_loss_finalize(mse_partial, n_mse, kl_partial, n_kl, recon_weight, kl_weight, mean_advantage, adv_dev, accum, loss_scale,
+                          losses, coefs, n_rec, n_lat, S(stream));
+}
+extern "C" int lo_colsum_f16_op(const void* x, float* out, int M, int N, float scale, void* stream) {
+  LO_REQUIRE(x && out && M > 0 && N > 0, "lo_colsum_f16_op: bad argument");
+  return lo_colsum_f16((const f16*)x, out, M, N, scale, S(stream));
+}
+
 extern "C" int lo_selfattn2d_forward(const float* x, const float* wq, const float* bq, const float* wk, const float* bk,
                                      const float* wv, const float* bv, const float* gamma, float* q, float* k, float* v,
                                      float* out, int B, int C, int N, void* stream) {

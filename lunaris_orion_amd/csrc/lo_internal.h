@@ -42,6 +42,7 @@ int lo_loss_finalize(const float* mse_partial, int n_mse, const float* kl_partia
 int lo_latent_bwd(const f16* dz, const float* mu, const float* logvar, const float* eps, const float* coefs,
                   const float* gmu, const float* glv, float gscale, f16* dml, int B, int L, hipStream_t st);
 int lo_colsum_f16(const f16* x, float* out, int M, int N, float scale, hipStream_t st);
+int lo_randn_fill(uint64_t seed, size_t first, size_t n, float* out, hipStream_t st);   // out[i] = the noise lo_head_reduce draws for element first + i
 int lo_cast_f32_f16(const float* src, f16* dst, size_t n, hipStream_t st);
 int lo_scale_f32(float* x, size_t n, float scale, hipStream_t st);
 int lo_grad_accumulate_run(float* acc, const float* g, size_t n, float scale, bool first, hipStream_t st);   // acc = (first ? 0 : acc) + scale * g

@@ -23,6 +23,19 @@ __device__ __forceinline__ float lo_randn(uint64_t seed, uint64_t idx) {
   float u2 = ((float)(uint32_t)((h >> 8) & 0xFFFFFF)) * (1.0f / 16777216.0f);    // [0,1)
   return sqrtf(-2.0f * __logf(u1)) * __cosf(6.28318530718f * u2);
 }
+// out[i] = lo_randn(seed, first + i): the noise lo_head_reduce_kernel applies to flat latent element first + i when eps_in is NULL
+// (op level: the parity and statistics tests of the generator, lo_reparam_noise)
+__global__ __launch_bounds__(256) void lo_randn_fill_kernel(uint64_t seed, uint64_t first, size_t n, float* __restrict__ out) {
+  const size_t stride = (size_t)gridDim.x * 256;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) out[i] = lo_randn(seed, first + (uint64_t)i);
+}
+int lo_randn_fill(uint64_t seed, size_t first, size_t n, float* out, hipStream_t st) {
+  const size_t want = (n + 255) / 256;
+  hipLaunchKernelGGL(lo_randn_fill_kernel, dim3((unsigned)(want < 1 ? 1 : (want > 1024 ? 1024 : want))), dim3(256), 0, st, seed,
+                     (uint64_t)first, n, out);
+  LO_LAUNCH_CHECK("randn_fill");
+  return LO_OK;
+}
 
 // ---------------------------------------------------------------------------------------------
 // head reduce: slab [nsplit][B][2L] -> mu, logvar (fp32 [B][L]), z = mu + eps*exp(0.5 logvar) (fp16 [B][L]),
@@ -560,8 +573,9 @@ int lo_dp_sum_shares_run(const void* recv, void* share, int world, size_t chunk,
 // gradients that a foreign loop has already multiplied by ITS loss scale (GradScaler starts at 65 536); the backward carries fp16
 // activation gradients, so it needs them in a fixed range whatever that scale is.  lo_grad_scale_pick takes max |g| over the
 // upstream tensors and leaves r = 2^k with max|g| * r in [2, 4) (and 1/r) in device memory -- a power of two, so scaling by r
-// before the backward and by 1/r after it is exact in fp32 and no host synchronisation is needed; all-zero or non-finite
-// gradients give r = 1 (non-finite values then propagate into the parameter gradients, where GradScaler.unscale_ finds them).
+// before the backward and by 1/r after it is exact in fp32 and no host synchronisation is needed; all-zero gradients or an
+// infinite one give r = 1; NaN elements drop out of the fmaxf reduction, so r is that of the other elements (either way the
+// non-finite values propagate into the parameter gradients, where GradScaler.unscale_ finds them).
 // ---------------------------------------------------------------------------------------------
 struct LoAmaxJobs { const float* p[5]; size_t n[5]; };
 __global__ __launch_bounds__(256) void lo_amax_partial_kernel(LoAmaxJobs J, float* __restrict__ partial) {

@@ -607,6 +607,8 @@ extern "C" int lo_vae_wait_handover(LoVae* h, void* stream) {
 }
 extern "C" int lo_gradnorm_early_range(const float* flat_grads, size_t begin, size_t end, float* scratch, void* stream) {
   LO_REQUIRE(flat_grads && scratch && end > begin, "lo_gradnorm_early_range: bad argument");
+  // the kernel issues 16-byte loads from flat_grads + begin on: the pointer is 16-byte aligned by the ABI, so begin must keep that
+  LO_REQUIRE(begin % 4 == 0, "lo_gradnorm_early_range: begin=%zu must be a multiple of 4 elements (16-byte loads start there)", begin);
   return lo_sumsq_range(flat_grads, begin, end, scratch, S(stream));
 }
 
