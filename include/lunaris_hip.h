@@ -631,6 +631,30 @@ int lo_dp_unpack_f16(const void* wire, float* g, size_t n, float inv_scale, void
 int lo_dp_unpack_f16_sumsq(const void* wire, float* g, size_t n, float inv_scale, float* scratch, void* stream);
 int lo_dp_sum_shares(const void* recv, void* share, int world, size_t chunk, int is_f16, void* stream);
 
+/* ---- held-out validation (lunaris_orion_amd/evaluate.py) ---------------------------------------------------------------------
+ * The reference sets a tenth of the dataset aside (train_hybrid.py:552-573 builds a val_loader) and names the early-stopping
+ * argument validation_loss (:216), then feeds it the training loss (:1049) and never reads the loader.  These three entries are what
+ * a pass over those sprites needs on the device, so that a whole pass ends in ONE device-to-host copy.  All three sum in a fixed
+ * order without atomics: the same inputs give the same bits.  Samples b >= n_valid are padding (the short last batch of a pass,
+ * filled up to the engine's batch size): their output rows are written as 0 and their inputs are NOT READ -- NaN there is invisible.
+ *
+ * lo_eval_image_metrics: recon, target fp32 NCHW [B][3][128][128] in [-1, 1] (what lo_vae_forward writes and reads) ->
+ *   per_sample [B][2] = (sum over the sample's 49 152 elements of (recon - target)^2 -- the per-sample numerator of F.mse_loss,
+ *   train_hybrid.py:859 --, mean SSIM).  SSIM as Wang et al. 2004: 11 x 11 Gaussian window, sigma 1.5 (weights in double on the host,
+ *   normalised to sum 1), "valid" window positions only (a 118 x 118 map per channel), C1 = (0.01 * 2)^2, C2 = (0.03 * 2)^2 (data
+ *   range 2), variances as E[x^2] - mu^2, mean over the map and the three channels.  fp32 throughout, separable filter out of LDS,
+ *   one workgroup per sample.  An identical pair gives exactly (0, 1).
+ * lo_eval_latent_kl: mu, logvar [B][L] (L a multiple of 64) -> per_sample_kl [B] = -0.5 * mean_l(1 + logvar - mu^2 - exp(logvar)),
+ *   the per-sample form of train_hybrid.py:661-662; its mean over b is the batch's kl_loss.
+ * lo_eval_accumulate: adds one batch to acc, 8 doubles on the device: [0] samples counted, [1..5] sums of the per-sample MSE
+ *   (per_sample_img[b][0] / 49 152), KL, PSNR = 10 log10(4 / max(MSE, 1e-12)), SSIM and mean quality score (quality: NULL, or the
+ *   teacher's quality_scores [B][4], lunar_evaluator.py:431-432; NULL leaves [5] alone), [6] / [7] the smallest / largest PSNR.  A
+ *   call that finds acc[0] == 0 starts a pass (the caller zeroes acc once).  One workgroup. */
+int lo_eval_image_metrics(const float* recon, const float* target, int B, int n_valid, float* per_sample, void* stream);
+int lo_eval_latent_kl(const float* mu, const float* logvar, int B, int L, int n_valid, float* per_sample_kl, void* stream);
+int lo_eval_accumulate(const float* per_sample_img, const float* per_sample_kl, const float* quality, int n_valid, double* acc,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -152,6 +152,9 @@ SIGNATURES = {
     "lo_vae_stage4_grad_range": (i32, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "lo_grad_accumulate": (i32, [f32p, f32p, sz, flt, i32, vp]),
     "lo_vae_set_gathered_sum": (i32, [vp, i32]),
+    "lo_eval_image_metrics": (i32, [f32p, f32p, i32, i32, f32p, vp]),
+    "lo_eval_latent_kl": (i32, [f32p, f32p, i32, i32, i32, f32p, vp]),
+    "lo_eval_accumulate": (i32, [f32p, f32p, f32p, i32, vp, vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

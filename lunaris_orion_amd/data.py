@@ -16,7 +16,7 @@ import glob
 import os
 import queue
 import threading
-from typing import Iterable, Iterator, Optional
+from typing import Iterable, Iterator, Optional, Tuple
 
 import numpy as np
 import torch
@@ -83,6 +83,22 @@ def epoch_batches(indices: np.ndarray, batch: int, rank: int = 0, world: int = 1
     order = order[: steps_per_epoch(len(order), batch, world) * world * batch][rank::world]
     for b in range(len(order) // batch):
         yield np.sort(order[b * batch:(b + 1) * batch])      # sorted: sequential reads inside a shard
+
+
+def val_batches(val_idx: np.ndarray, batch: int, rank: int = 0, world: int = 1) -> Iterator[Tuple[np.ndarray, int]]:
+    """(indices, n_valid) batches of one validation pass for this rank (evaluate.Validator).  Unlike a training epoch nothing is
+    dropped: rank r takes ``val_idx[r::world]``, so every held-out index is seen exactly once across the ranks.  Every batch has
+    ``batch`` indices, the step's batch size (one engine, one workspace): a short one is filled up by repeating its first index and
+    ``n_valid`` says how many leading entries count.  Every rank yields the same number of batches, rank 0's (the longest stride);
+    a rank whose stride has run out yields batches with ``n_valid = 0`` that repeat the first held-out index.  Nothing for an
+    empty ``val_idx``."""
+    val_idx = np.asarray(val_idx, dtype=np.int64)
+    mine = val_idx[rank::world]
+    longest = -(-len(val_idx) // world)                       # len(val_idx[0::world])
+    for b in range(-(-longest // batch)):
+        part = mine[b * batch:(b + 1) * batch]
+        fill = part[0] if len(part) else val_idx[0]
+        yield np.concatenate([part, np.full(batch - len(part), fill, dtype=np.int64)]), len(part)
 
 
 class SpriteFeeder:

@@ -169,10 +169,10 @@ def prune_periodic_checkpoints(ckpt_dir: Path, keep: int) -> list:
     return removed
 
 
-def checkpoint_dict(stepper, vae, teacher, global_step: int, best_loss: float, args: dict) -> dict:
+def checkpoint_dict(stepper, vae, teacher, global_step: int, best_loss: float, args: dict, best_val_loss: Optional[float] = None) -> dict:
     """The reference's checkpoint dictionary (train_hybrid.py:594-605) from the native state.  Extra key
     `lunaris_amd_extra` (ignored by the reference) keeps what the reference loses on resume: the reward baseline and the
-    fp16 loss scale."""
+    fp16 loss scale.  best_val_loss (runs with `--validate_every`; None: no such key): the held-out loss `best.pt` was chosen by."""
     vp = OrderedDict(vae.named_parameters())
     ck = {"global_step": global_step,
           "vae_state_dict": {k: v.detach().cpu().clone() for k, v in vae.state_dict().items()},
@@ -229,8 +229,15 @@ def checkpoint_dict(stepper, vae, teacher, global_step: int, best_loss: float, a
     extra["noise_calls"] = int(getattr(vae, "noise_calls", 0))
     if teacher is not None:
         extra["drop_calls"] = int(getattr(teacher, "drop_calls", 0))
+    if best_val_loss is not None:
+        extra["best_val_loss"] = float(best_val_loss)
     ck["lunaris_amd_extra"] = extra
     return ck
+
+
+def restored_best_val_loss(ck: dict) -> float:
+    """`best_val_loss` of a checkpoint written by a run with `--validate_every` (inf: none recorded)."""
+    return float((ck.get("lunaris_amd_extra") or {}).get("best_val_loss", float("inf")))
 
 
 def restore_checkpoint(ck: dict, stepper, vae, teacher) -> Tuple[int, float]:

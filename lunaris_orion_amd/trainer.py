@@ -45,6 +45,17 @@ def cosine_warm_restarts_lr(base_lr: float, eta_min: float, t0: int, t_mult: int
     return eta_min + (base_lr - eta_min) * (1.0 + math.cos(math.pi * t_cur / t_i)) / 2.0
 
 
+def decode_sprites_u8(u8_hwc: torch.Tensor) -> torch.Tensor:
+    """uint8 [B,128,128,3] on the device -> normalised float32 [B,3,128,128] (train_hybrid.py:181-182), native kernel."""
+    if u8_hwc.dtype != torch.uint8 or tuple(u8_hwc.shape[1:]) != (128, 128, 3) or not u8_hwc.is_cuda:
+        raise ValueError("expected a CUDA uint8 tensor of shape [B,128,128,3]")
+    u8_hwc = u8_hwc.contiguous()
+    out = torch.empty(u8_hwc.shape[0], 3, 128, 128, dtype=torch.float32, device=u8_hwc.device)
+    _lib.check(_lib.lib.lo_decode_sprites_u8(u8_hwc.data_ptr(), out.data_ptr(), u8_hwc.shape[0], _lib.stream_ptr()),
+               "lo_decode_sprites_u8")
+    return out
+
+
 def _set_linear_mode(eng, mode: int) -> None:
     """lo_vae_set_linear_factored, if the engine is not in that mode already (`eng.fac_mode` mirrors the library's state)."""
     if eng.fac_mode != mode:
@@ -501,14 +512,8 @@ class VAEStepper:
                                                    flat.numel(), *args), "lo_clip_adamw_step")
 
     def decode_sprites(self, u8_hwc: torch.Tensor) -> torch.Tensor:
-        """uint8 [B,128,128,3] on the device -> normalised float32 [B,3,128,128] (train_hybrid.py:181-182), native kernel."""
-        if u8_hwc.dtype != torch.uint8 or tuple(u8_hwc.shape[1:]) != (128, 128, 3) or not u8_hwc.is_cuda:
-            raise ValueError("expected a CUDA uint8 tensor of shape [B,128,128,3]")
-        u8_hwc = u8_hwc.contiguous()
-        out = torch.empty(u8_hwc.shape[0], 3, 128, 128, dtype=torch.float32, device=u8_hwc.device)
-        _lib.check(_lib.lib.lo_decode_sprites_u8(u8_hwc.data_ptr(), out.data_ptr(), u8_hwc.shape[0], _lib.stream_ptr()),
-                   "lo_decode_sprites_u8")
-        return out
+        """uint8 [B,128,128,3] on the device -> normalised float32 [B,3,128,128] (`decode_sprites_u8`)."""
+        return decode_sprites_u8(u8_hwc)
 
     def _update_loss_scale(self, skipped_total: float, observed_after_step: Optional[int] = None) -> None:
         """Feed one observation of the device's skipped-update counter to the loss-scale policy (`LossScalePolicy`)."""

@@ -16,6 +16,10 @@ VAE then) and the teacher-only metrics are reported as 0; `--rewar
 also lets the VAE climb the frozen, eval-mode teacher's quality score on the undetached reconstruction.  The reference's
 defects are not inherited: no tensorboard hard dependency, no DataLoader timeout assertion, per-epoch average
 loss is a real number, checkpoints are written.  Launch one process per GPU with torch.distributed.run for DP.
+
+`--validate_every N` (a builder flag, default 0 = off: the reference's rule, bit for bit) validates the held-out tenth of the split,
+which the reference sets aside and never reads (:552-573), at the end of every N-th epoch and lets `val_loss` decide early stopping
+and best.pt; `--validate_only --resume_from CKPT` validates a checkpoint once and prints one JSON line.
 """
 from __future__ import annotations
 
@@ -98,6 +102,15 @@ def build_parser() -> argparse.ArgumentParser:
                         "window's last one steps on the sum (the gradient of the mean micro-loss), VAE and teacher alike; off = the reference's "
                         "rule, which steps on the last micro-batch alone (train_hybrid.py:841-842, 907).  Single process only.  Checkpoints are "
                         "taken as without the flag: a window that is still open is not part of a checkpoint, a resumed run starts a new one")
+    p.add_argument("--validate_every", type=int, default=0,
+                   help="every N epochs, at the epoch's end, validate on the held-out tenth of the split (the sprites the reference sets aside "
+                        "and never reads, train_hybrid.py:552-573): per-sample MSE, KL, PSNR, SSIM (and the teacher's eval-mode quality score) "
+                        "with z = mu; val_* scalars go to the log and TensorBoard, early stopping and best.pt are decided by val_loss = "
+                        "recon_weight * recon + kl_weight * kl, and best_val_loss rides in the checkpoint.  0 = off: the reference's rule "
+                        "(the mean logged training loss decides)")
+    p.add_argument("--validate_only", action="store_true",
+                   help="with --resume_from: validate the checkpoint once on the held-out tenth, print one JSON line of the metrics and exit; "
+                        "no training step is taken and nothing is saved")
     return p
 
 
@@ -110,10 +123,14 @@ def parse_args(argv=None) -> argparse.Namespace:
     if args.vae_only and args.reward_grad_weight > 0:
         parser.error("--reward_grad_weight needs the teacher (its eval-mode quality score is the reward), and --vae_only does not run one: "
                      "drop --vae_only, or pass --reward_scale 0 --quality_weight 0 to keep the teacher's own objective out")
+    if args.validate_every < 0:
+        parser.error("--validate_every must be >= 0")
+    if args.validate_only and not args.resume_from:
+        parser.error("--validate_only needs --resume_from (the checkpoint to validate)")
     return args
 
 
-from lunaris_orion_amd.data import SpriteFeeder, SpriteShards, epoch_batches, steps_per_epoch as _steps_per_epoch   # noqa: E402
+from lunaris_orion_amd.data import SpriteFeeder, SpriteShards, epoch_batches, steps_per_epoch as _steps_per_epoch, val_batches   # noqa: E402
 
 
 def main(argv=None):
@@ -161,7 +178,7 @@ def main(argv=None):
     writer = None
     try:
         from torch.utils.tensorboard import SummaryWriter
-        writer = SummaryWriter(log_dir=str(out_dir / "tensorboard")) if rank == 0 else None
+        writer = SummaryWriter(log_dir=str(out_dir / "tensorboard")) if rank == 0 and not args.validate_only else None
     except Exception:
         log.info("tensorboard not installed: scalar logging goes to training.log only")
 
@@ -194,6 +211,8 @@ def main(argv=None):
         stepper = VAEStepper(vae, **common)
     log.info(f"VAE Parameters - Total: {sum(p.numel() for p in vae.parameters()):,}")
     global_step, best_loss = 0, float("inf")
+    validating = args.validate_every > 0 or args.validate_only
+    best_val_loss = float("inf")
 
     from lunaris_orion_amd import hostside
 
@@ -203,12 +222,15 @@ def main(argv=None):
         stepper.synchronize_parameters()          # the pipelined optimizer step may still be updating the decoder's parameters
         torch.cuda.synchronize()
         stepper.check_device_health()             # raises instead of writing a checkpoint after a lost launch (rendezvous-failure word)
-        torch.save(hostside.checkpoint_dict(stepper, vae, teacher, global_step, best_loss, vars(args)), out_dir / "checkpoints" / f"{tag}.pt")
+        torch.save(hostside.checkpoint_dict(stepper, vae, teacher, global_step, best_loss, vars(args), best_val_loss if validating else None),
+                   out_dir / "checkpoints" / f"{tag}.pt")
         log.info(f"Checkpoint saved at step {global_step}")
 
     if args.resume_from:
         ck = torch.load(args.resume_from, map_location="cpu", weights_only=True)
         global_step, best_loss = hostside.restore_checkpoint(ck, stepper, vae, teacher)
+        if validating:
+            best_val_loss = hostside.restored_best_val_loss(ck)
         log.info(f"Successfully loaded checkpoint from step {global_step}")
 
     data = SpriteShards(args.data_dir)
@@ -218,6 +240,28 @@ def main(argv=None):
     per_rank = args.batch_size
     steps_per_epoch = _steps_per_epoch(n_train, per_rank, world)    # drop_last (:569) at the global batch: identical on every rank
     log.info(f"Dataset initialized with {len(data)} samples; {steps_per_epoch} batches/epoch/rank")
+
+    validator = None
+    if validating:
+        from lunaris_orion_amd.evaluate import Validator
+        validator = Validator(stepper, teacher)
+        val_idx = perm[n_train:]                              # the tenth random_split sets aside (:555-556)
+
+    def validate():
+        """One pass over the held-out sprites (every rank its stride; the same metrics on every rank); None when there are none."""
+        plan = list(val_batches(val_idx, per_rank, rank, world))
+        if not plan:
+            log.info("validation skipped: the split leaves no held-out sprites")
+            return None
+        val_feeder = SpriteFeeder(data, (idx for idx, _ in plan), per_rank, device=f"cuda:{local}")
+        return validator.run(val_feeder, [n_valid for _, n_valid in plan])
+
+    if args.validate_only:
+        import json
+        res = validate()
+        if rank == 0:
+            print(json.dumps({"global_step": global_step, "best_val_loss": best_val_loss, **(res if res is not None else {"n": 0})}), flush=True)
+        return
 
     early = hostside.EarlyStopping(patience=args.early_stopping_patience)
     interrupted = {"flag": False}
@@ -276,13 +320,31 @@ def main(argv=None):
             grad_sync.average_small(t_avg)
             avg = float(t_avg.item())
         log.info(f"Epoch {epoch + 1} Summary: Time {(time.time() - t0) / 60:.2f} min, Average Loss {avg:.4f}, Best Loss {best_loss:.4f}")
-        early(avg)                                                                         # train_hybrid.py:1049-1052
-        if early.early_stop:
-            log.info("Early stopping triggered")
-            done = True
-        if avg < best_loss:
-            best_loss = avg
-            save_checkpoint("best")
+        if args.validate_every > 0:
+            # the held-out loss decides (what EarlyStopping's `validation_loss` argument names, :216); the training mean is only kept
+            best_loss = min(best_loss, avg)
+            val = validate() if (epoch + 1) % args.validate_every == 0 else None
+            if val is not None:
+                if writer is not None:
+                    for k, v in val.items():
+                        writer.add_scalar(k, v, global_step)
+                log.info(f"Epoch {epoch + 1} Validation: " + " ".join(f"{k} {v:.6g}" for k, v in val.items())
+                         + f" best_val_loss {best_val_loss:.6g}")
+                early(val["val_loss"])
+                if early.early_stop:
+                    log.info("Early stopping triggered")
+                    done = True
+                if val["val_loss"] < best_val_loss:
+                    best_val_loss = val["val_loss"]
+                    save_checkpoint("best")
+        else:
+            early(avg)                                                                     # train_hybrid.py:1049-1052
+            if early.early_stop:
+                log.info("Early stopping triggered")
+                done = True
+            if avg < best_loss:
+                best_loss = avg
+                save_checkpoint("best")
         save_checkpoint("latest")
         if done:
             break
