@@ -519,6 +519,27 @@ int lo_teacher_heads_backward(LoTeacher* h, const float* flat_state, void* ws, c
  * pooled expert features [E][B][F], pre-weighting quality logits [B][E][4]), so a caller may copy them and run this backward
  * after later forward calls — together with that call's dropout_p (0 in eval mode) and drop_seed. */
 int lo_teacher_heads_saved(const LoTeacher* h, size_t* byte_offsets3, size_t* elems3);
+/* Where a teacher forward leaves an intermediate tensor, for tests that check every layer in situ against a plain reference of that
+ * layer's own stored operands (tests/test_teacher_insitu_gpu.py).  Launches nothing, changes nothing.  dims4: NHWC of an fp16 tensor
+ * (the compact attention rows [B][1024][F] as B, 8, 128, F: they are image rows 0..7), or 1, 1, C, 2 of an fp32 per-channel table;
+ * elem_bytes 2 = fp16, 4 = fp32.  An unknown kind, or e / l outside what the kind takes, is an error (lo_last_error says which).
+ * space 1 = bws of lo_teacher_forward_keep / _keep_eval (feature extractor kinds take e = l = 0 unless said otherwise):
+ *    0 raw32 = lrelu(conv 3->32)        1 dw[l], l = 0..2: depthwise 3x3, 5x5, 3x3    2 cat: the three pointwise convs, raw, 64 channels each
+ *    3 catd = Dropout(BN(cat))          4 rawF = lrelu(fusion conv)                   5 feat = BN(rawF)
+ *    6 xs[e][l]: output of ExpertBlock (e, l)
+ *    per block (e, l) -- an error under the shared-set plan (LO_T_BWD_SHARED=1), which holds one block at a time:
+ *    7 rawA = lrelu(conv1)    8 bnA = Dropout2d(BN(rawA))    9 qkv (3F channels)    10 attc: compact attention rows (rows >= 543 zero)
+ *   11 projc = proj(attc)    12 a2 = proj_drop, full resolution    13 rawB = lrelu(conv2)    14 scraw: shortcut conv (feature_dim != 128, l = 0)
+ *   15 mrA, 16 mrB: (mean, rstd) of BatchNorm1 / 2    17 mrS, 18 ssS: (mean, rstd) and (scale, shift) of the shortcut BatchNorm (as 14)
+ *   19 the feature extractor's (mean, rstd) tables, l = 3 conv1 (32 channels), 4..6 branches (64), 7 fusion (128)
+ *   20 conv1's (scale, shift), which the depthwise convs read
+ * space 0 = ws of lo_teacher_forward, e = l = 0; the block tensors are those of the LAST block the call ran:
+ *    0 o_raw32    1 o_cat    2 o_feat    3 o_x0, 4 o_x1: block outputs, ping-pong    5 o_rawA    6 o_projc (compact)    7 o_proj = proj_drop
+ *    8 o_rawB     9 o_ss: (scale, shift) of the last BatchNorm finalize    10 o_ssb: the per-sample Dropout2d table [B][F][2]
+ *   11 o_ss_cat: (scale, shift) of the 192 concatenated channels    12 o_wfus_fold fp16 [128][192], 13 o_bfus_fold fp32 [128]: the fusion
+ *      conv with the branch BatchNorms folded in (dropout-free calls)
+ * The pooled features and pre-weighting logits are where lo_teacher_heads_saved says. */
+int lo_teacher_debug_tensor(const LoTeacher* h, int space, int which, int e, int l, size_t* byte_offset, int* dims4, int* elem_bytes);
 int lo_teacher_heads_backward_ex(LoTeacher* h, const float* flat_state, const float* pooled_f, const float* pooled_e,
                                  const float* raw_q, const float* expert_weights, const float* d_quality, const float* d_weights,
                                  float dropout_p, uint64_t drop_seed, float* rows, float* flat_grads, void* stream);

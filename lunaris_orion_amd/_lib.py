@@ -80,6 +80,7 @@ SIGNATURES = {
     "lo_teacher_grad_range": (i32, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "lo_teacher_heads_backward": (i32, [vp, f32p, vp, f32p, flt, f32p, f32p, vp]),
     "lo_teacher_heads_saved": (i32, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "lo_teacher_debug_tensor": (i32, [vp, i32, i32, i32, i32, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "lo_teacher_full_backward_bytes": (C.c_size_t, [vp]),
     "lo_teacher_full_backward_ex": (i32, [vp, f32p, f32p, vp, vp, f32p, f32p, f32p, f32p, f32p, f32p, flt, u64, flt, f32p, f32p, vp]),
     "lo_teacher_full_backward_dx": (i32, [vp, f32p, f32p, vp, vp, f32p, f32p, f32p, f32p, f32p, f32p, flt, u64, flt, f32p, f32p, f32p, vp]),

@@ -259,6 +259,83 @@ extern "C" size_t lo_teacher_full_backward_bytes(const LoTeacher* h) {
   return p.bytes;
 }
 
+// Where a teacher tensor lives (include/lunaris_hip.h has the table of kinds): space 1 = the scratch of lo_teacher_forward_keep /
+// _keep_eval, straight from tb_plan; space 0 = the workspace of lo_teacher_forward.  Launches nothing, changes nothing.
+extern "C" int lo_teacher_debug_tensor(const LoTeacher* h, int space, int which, int e, int l, size_t* byte_offset, int* dims4, int* elem_bytes) {
+  LO_REQUIRE(h && byte_offset && dims4 && elem_bytes, "lo_teacher_debug_tensor: null argument");
+  LO_REQUIRE(space == 0 || space == 1, "lo_teacher_debug_tensor: unknown space %d (0 = forward workspace, 1 = kept-forward scratch)", space);
+  const int B = h->B, F = h->F;
+  auto put = [&](size_t off, int d0, int d1, int d2, int d3, int eb) {
+    *byte_offset = off; dims4[0] = d0; dims4[1] = d1; dims4[2] = d2; dims4[3] = d3; *elem_bytes = eb;
+    return LO_OK;
+  };
+  if (space == 0) {
+    LO_REQUIRE(e == 0 && l == 0, "lo_teacher_debug_tensor: the forward workspace holds one tensor per kind (e = l = 0), asked for (%d, %d)", e, l);
+    switch (which) {
+      case 0: return put(h->o_raw32, B, 128, 128, 32, 2);
+      case 1: return put(h->o_cat, B, 128, 128, 192, 2);
+      case 2: return put(h->o_feat, B, 128, 128, 128, 2);
+      case 3: return put(h->o_x0, B, 128, 128, F, 2);
+      case 4: return put(h->o_x1, B, 128, 128, F, 2);
+      case 5: return put(h->o_rawA, B, 128, 128, F, 2);
+      case 6: return put(h->o_projc, B, 8, 128, F, 2);
+      case 7: return put(h->o_proj, B, 128, 128, F, 2);
+      case 8: return put(h->o_rawB, B, 128, 128, F, 2);
+      case 9: return put(h->o_ss, 1, 1, F, 2, 4);
+      case 10: return put(h->o_ssb, B, 1, F, 2, 4);
+      case 11: return put(h->o_ss_cat, 1, 1, 192, 2, 4);
+      case 12: return put(h->o_wfus_fold, 1, 1, 128, 192, 2);
+      case 13: return put(h->o_bfus_fold, 1, 1, 1, 128, 4);
+      default: break;
+    }
+    LO_REQUIRE(false, "lo_teacher_debug_tensor: unknown tensor kind %d of the forward workspace (0 .. 13)", which);
+  }
+  TbPlan p;
+  tb_plan(h, &p);
+  const bool per_block = which >= 6 && which <= 18;
+  if (per_block) {
+    LO_REQUIRE(e >= 0 && e < h->E && l >= 0 && l < 3, "lo_teacher_debug_tensor: block (%d, %d) out of range (%d experts, 3 layers)", e, l, h->E);
+    LO_REQUIRE(which == 6 || p.saved, "lo_teacher_debug_tensor: tensor kind %d is per block, and this plan keeps one shared set (LO_T_BWD_SHARED)", which);
+  } else if (which == 1) {
+    LO_REQUIRE(e == 0 && l >= 0 && l < 3, "lo_teacher_debug_tensor: depthwise branch %d out of range (e = 0, l = 0 .. 2)", l);
+  } else if (which == 19) {
+    LO_REQUIRE(e == 0 && l >= 3 && l <= 7, "lo_teacher_debug_tensor: (mean, rstd) table %d out of range (e = 0, l = 3 .. 7)", l);
+  } else {
+    LO_REQUIRE(e == 0 && l == 0, "lo_teacher_debug_tensor: tensor kind %d takes e = l = 0, asked for (%d, %d)", which, e, l);
+  }
+  const TbBlk& b = p.blk[per_block ? e : 0][per_block ? l : 0];
+  switch (which) {
+    case 0: return put(p.o_raw32, B, 128, 128, 32, 2);
+    case 1: return put(p.o_dwb[l], B, 128, 128, 32, 2);
+    case 2: return put(p.o_cat, B, 128, 128, 192, 2);
+    case 3: return put(p.o_catd, B, 128, 128, 192, 2);
+    case 4: return put(p.o_rawF, B, 128, 128, 128, 2);
+    case 5: return put(p.o_feat, B, 128, 128, 128, 2);
+    case 6: return put(p.o_xs[e][l], B, 128, 128, F, 2);
+    case 7: return put(b.rawA, B, 128, 128, F, 2);
+    case 8: return put(b.bnA, B, 128, 128, F, 2);
+    case 9: return put(b.qkv, B, 128, 128, 3 * F, 2);
+    case 10: return put(b.attc, B, 8, 128, F, 2);
+    case 11: return put(b.projc, B, 8, 128, F, 2);
+    case 12: return put(b.a2, B, 128, 128, F, 2);
+    case 13: return put(b.rawB, B, 128, 128, F, 2);
+    case 14:
+      LO_REQUIRE(F != 128 && l == 0, "lo_teacher_debug_tensor: block (%d, %d) at feature_dim %d has no shortcut conv", e, l, F);
+      return put(b.scraw, B, 128, 128, F, 2);
+    case 15: return put(b.mrA, 1, 1, F, 2, 4);
+    case 16: return put(b.mrB, 1, 1, F, 2, 4);
+    case 17:
+    case 18:
+      LO_REQUIRE(F != 128 && l == 0, "lo_teacher_debug_tensor: block (%d, %d) at feature_dim %d has no shortcut BatchNorm", e, l, F);
+      return put(which == 17 ? b.mrS : b.ssS, 1, 1, F, 2, 4);
+    case 19: return put(p.o_mr[l], 1, 1, l == 3 ? 32 : (l == 7 ? 128 : 64), 2, 4);
+    case 20: return put(p.o_ssx[3], 1, 1, 32, 2, 4);
+    default: break;
+  }
+  LO_REQUIRE(false, "lo_teacher_debug_tensor: unknown tensor kind %d of the kept-forward scratch (0 .. 20)", which);
+  return LO_OK;
+}
+
 static int tb_ctx_init(TbCtx& c, LoTeacher* h, float* P, void* ws, void* bws, float* grads, float drop_p, uint64_t drop_seed, float gscale, void* stream) {
   c.h = h; c.P = P; c.ws = ws; c.bws = bws; c.G = grads; c.st = reinterpret_cast<hipStream_t>(stream);
   tb_plan(h, &c.pl);
