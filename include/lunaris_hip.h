@@ -282,6 +282,15 @@ int lo_vae_pack(LoVae* h, const float* flat_params, void* ws, void* stream);
 int lo_vae_optimizer_step(LoVae* h, float* p, const float* g, float* m, float* v, void* ws, float max_norm, float lr, float beta1,
                           float beta2, float eps, float weight_decay, int step, float* scratch, int flags, void* stream);
 int lo_vae_join(LoVae* h, void* stream);   /* `stream` waits for the side-stream work of lo_vae_pack / lo_vae_optimizer_step */
+/* Weight EMA (no reference counterpart; VAEStepper(ema_decay=...), opt-in).  ema[i] += (p[i] - ema[i]) * one_minus_decay over n fp32
+ * elements: subtract, multiply, add, each rounded to fp32 (no fma), so numpy float32 replays it bit for bit and launches over
+ * sub-ranges equal one launch.  ema and p 16-byte aligned and not overlapping, any n >= 1.  gate: NULL, or 3 floats as
+ * scratch[1024..1026] of lo_clip_adamw_step -- gate[2] == 0 (a skipped update) writes nothing. */
+int lo_ema_update(float* ema, const float* p, size_t n, float one_minus_decay, const float* gate, void* stream);
+/* The same over all lo_vae_flat_elems() elements, ordered by the engine: behind every parameter write of the last
+ * lo_vae_optimizer_step on this handle (on its side stream after a pipelined step, beside the next forward) and ahead of the next
+ * one; lo_vae_join covers it.  scratch: that step's scratch (the gate is scratch + 1024), or NULL for no gate. */
+int lo_vae_ema_update(LoVae* h, const float* flat_params, float* ema, float one_minus_decay, const float* scratch, void* stream);
 /* Factored Linear-layer gradients.  fc_mu | fc_logvar ([2L, 32768]) and decoder.fc ([32768, L]) hold 82 % of the parameters
  * (lunar_generate.py:124-125, 165) and at batch B their weight gradients dW = dY^T X have rank B.  With the mode on (batch <= 128),
  * a FUSED single-call lo_vae_backward does not write those two gradients into flat_grads: it keeps the factors (transposed,

@@ -101,6 +101,8 @@ SIGNATURES = {
     "lo_vae_wait_handover": (i32, [vp, vp]),
     "lo_vae_optimizer_step": (i32, [vp, f32p, f32p, f32p, f32p, vp, flt, flt, flt, flt, flt, flt, i32, f32p, i32, vp]),
     "lo_vae_join": (i32, [vp, vp]),
+    "lo_ema_update": (i32, [f32p, f32p, sz, flt, f32p, vp]),
+    "lo_vae_ema_update": (i32, [vp, f32p, f32p, flt, f32p, vp]),
     "lo_vae_set_linear_factored": (i32, [vp, i32]),
     "lo_vae_linear_factored": (i32, [vp]),
     "lo_vae_factor_block": (i32, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),

@@ -8,7 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "liblunaris_hip.so")
-SOURCES = ["lo_util.cpp", "lo_conv_geom.hip", "lo_igemm.hip", "lo_conv_f8.hip", "lo_conv_select.hip", "lo_conv3.hip", "lo_wgrad.hip", "lo_wgrad3.hip", "lo_wgrad2.hip", "lo_norm.hip", "lo_edge.hip", "lo_imgdgrad.hip", "lo_train.hip", "lo_eval.hip", "lo_lowrank.hip", "lo_attn.hip", "lo_attn8.hip", "lo_teacher_plan.hip", "lo_teacher_kernels.hip", "lo_teacher_f128.hip", "lo_teacher_heads.hip", "lo_teacher_forward.hip", "lo_teacher_bwd_block.hip", "lo_teacher_bwd.hip", "lo_api.hip", "lo_vae_plan.hip", "lo_vae_opt.hip", "lo_vae_step.hip"]
+SOURCES = ["lo_util.cpp", "lo_conv_geom.hip", "lo_igemm.hip", "lo_conv_f8.hip", "lo_conv_select.hip", "lo_conv3.hip", "lo_wgrad.hip", "lo_wgrad3.hip", "lo_wgrad2.hip", "lo_norm.hip", "lo_edge.hip", "lo_imgdgrad.hip", "lo_train.hip", "lo_ema.hip", "lo_eval.hip", "lo_lowrank.hip", "lo_attn.hip", "lo_attn8.hip", "lo_teacher_plan.hip", "lo_teacher_kernels.hip", "lo_teacher_f128.hip", "lo_teacher_heads.hip", "lo_teacher_forward.hip", "lo_teacher_bwd_block.hip", "lo_teacher_bwd.hip", "lo_api.hip", "lo_vae_plan.hip", "lo_vae_opt.hip", "lo_vae_step.hip"]
 HEADERS = ["lo_common.h", "lo_internal.h", "lo_conv.h", "lo_conv_dev.h", "lo_norm.h", "lo_vae.h", "lo_teacher.h", os.path.join("..", "..", "include", "lunaris_hip.h")]
 
 

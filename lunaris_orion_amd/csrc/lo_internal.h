@@ -46,6 +46,7 @@ int lo_randn_fill(uint64_t seed, size_t first, size_t n, float* out, hipStream_t
 int lo_cast_f32_f16(const float* src, f16* dst, size_t n, hipStream_t st);
 int lo_scale_f32(float* x, size_t n, float scale, hipStream_t st);
 int lo_grad_accumulate_run(float* acc, const float* g, size_t n, float scale, bool first, hipStream_t st);   // acc = (first ? 0 : acc) + scale * g
+int lo_ema_run(float* ema, const float* p, size_t n, float one_minus_decay, const float* gate, hipStream_t st);   // lo_ema.hip: ema += (p - ema)(1 - decay); gate[2] == 0 skips
 int lo_dp_pack_f16_run(const float* g, f16* wire, size_t n, float scale, hipStream_t st);     // data-parallel exchange helpers
 int lo_dp_unpack_f16_run(const f16* wire, float* g, size_t n, float inv_scale, hipStream_t st);
 int lo_dp_unpack_f16_sumsq_run(const f16* wire, float* g, size_t n, float inv_scale, float* scratch, hipStream_t st);

@@ -121,6 +121,7 @@ struct LoVae {
   // pipelined optimizer step: levels 2..5 (AdamW of 97 % of the parameters + their operand refresh) are ENQUEUED by the next
   // forward once its first stage has run -- see lo_vae_optimizer_step
   struct { bool pending = false; float* P; const float* G; float* M; float* V; void* ws; LoAdamHyper hp; } defer;
+  bool opt_tail_on_side = false;   // the last lo_vae_optimizer_step was pipelined: [b4, n) was updated on `side` (lo_vae_ema_update follows it there)
   int n_packjobs_s4 = 0, pack_blocks_s4 = 0, n_packjobs8_s4 = 0, pack_blocks8_s4 = 0;   // job-table prefix up to and including encoder stage 4
   int bwd_layer = 0;         // conv layers processed so far in the current backward (selects the dv buffer / events)
   size_t o_skslab = 0;       // slabs of the split-K convolutions (one launch at a time on the caller's stream)

@@ -223,7 +223,8 @@ extern "C" int lo_vae_optimizer_step(LoVae* h, float* P, const float* G, float* 
   if (presummed) LO_TRY(lo_gradnorm_split(G, b, max_norm, scratch, scratch + 1024, st, fail));
   else LO_TRY(lo_gradnorm(G, n, max_norm, scratch, scratch + 1024, st, fail));
   const LoAdamHyper hp = {scratch + 1024, lr, beta1, beta2, eps, weight_decay, step};
-  if (serial || !vae_side_on(h)) {
+  h->opt_tail_on_side = !serial && vae_side_on(h);
+  if (!h->opt_tail_on_side) {
     auto adam = [&](size_t lo, size_t hi) { return lo_adamw(P + lo, G + lo, M + lo, V + lo, hi - lo, hp, st); };
     if (vae_opt_from_factors(h)) {
       const LoLinearRanges r = vae_linear_ranges(h, P, M, V, ws, false);      // no copies: lo_vae_pack below makes them
@@ -252,6 +253,24 @@ extern "C" int lo_vae_optimizer_step(LoVae* h, float* P, const float* G, float* 
   LO_TRY(vae_flush_deferred(h, nullptr));
   return LO_OK;
 }
+// EMA of the flat parameters behind an optimizer step: ema[0, n) <- ema + (P - ema)(1 - decay), gated like the step's AdamW launches.
+// Ordering.  Pipelined step (side stream on): AdamW wrote [0, b4) on `stream` and writes [b4, n) on h->side, possibly still deferred.  The
+// pass is enqueued on h->side behind the flushed tail: that stream is in order, so it follows the AdamW of [b4, n), and it waited on
+// ev_pre -- bound to the AdamW launch of [0, b4), which itself follows the clip kernel that writes the gate -- before its first launch
+// of the step.  Level 5 is then recorded again behind the pass: lo_vae_join and the next backward (vae_wait_level(.., 5)) wait for
+// it, and the next write of any parameter -- the next step's AdamW, on `stream` behind that backward, then on the side stream behind
+// this pass -- is ordered behind its read.  Levels 2..4 keep their events, so the next forward waits for no more than before and the
+// 12 B / parameter run beside it.  Serial step or no side stream: everything the step enqueued is on `stream`, and so is the pass
+// (what lo_vae_pack left on the side stream only reads the parameters, like the pass).
+extern "C" int lo_vae_ema_update(LoVae* h, const float* P, float* ema, float one_minus_decay, const float* scratch, void* stream) {
+  LO_REQUIRE(h && P && ema, "lo_vae_ema_update: null argument");
+  const float* gate = scratch ? scratch + 1024 : nullptr;
+  if (!(h->opt_tail_on_side && vae_side_on(h))) return lo_ema_run(ema, P, h->flat_elems, one_minus_decay, gate, S(stream));
+  LO_TRY(vae_flush_deferred(h, nullptr));
+  LO_TRY(lo_ema_run(ema, P, h->flat_elems, one_minus_decay, gate, h->side));
+  return vae_side_record(h, 5, h->side);
+}
+
 // `stream` waits for whatever lo_vae_pack / lo_vae_optimizer_step left running (or still to be enqueued) on the side stream.
 extern "C" int lo_vae_join(LoVae* h, void* stream) {
   LO_REQUIRE(h, "lo_vae_join: null handle");

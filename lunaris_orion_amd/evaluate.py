@@ -29,7 +29,7 @@ ACC_COUNT, ACC_MSE, ACC_KL, ACC_PSNR, ACC_SSIM, ACC_QUALITY, ACC_PSNR_MIN, ACC_P
 
 
 class Validator:
-    """``Validator(stepper_or_vae, teacher=None).run(batches, n_valid_per_batch) -> dict``.
+    """``Validator(stepper_or_vae, teacher=None, weights="live").run(batches, n_valid_per_batch) -> dict``.
 
     Given a stepper (``VAEStepper`` / ``HybridStepper``) the pass uses its model, loss weights, gradient exchange (data parallel) and,
     unless ``teacher`` is passed, its teacher; given a bare ``LunarisCoreVAE`` the reference's default weights (1.0, 0.1).
@@ -41,8 +41,10 @@ class Validator:
     depends on the batch size (tiles, K splits), so the last bits of a sample's losses do too; at one batch size a metric does not
     depend on how the caller cut the held-out set into batches, nor on what the padding rows hold."""
 
-    def __init__(self, stepper_or_vae, teacher=None):
+    def __init__(self, stepper_or_vae, teacher=None, weights: str = "live"):
         _lib.require_gpu()
+        if weights not in ("live", "ema"):
+            raise ValueError(f"weights must be 'live' or 'ema', got {weights!r}")
         if isinstance(stepper_or_vae, LunarisCoreVAE):
             self.stepper, self.vae = None, stepper_or_vae
         else:
@@ -51,6 +53,11 @@ class Validator:
         self.recon_weight = float(getattr(self.stepper, "recon_weight", 1.0))
         self.kl_weight = float(getattr(self.stepper, "kl_weight", 0.1))
         self.grad_sync = getattr(self.stepper, "grad_sync", None)
+        # "ema": every pass runs inside stepper.ema_weights() -- the averaged weights, the live ones back bit for bit afterwards -- and
+        # says so in its result ("val_weights": "ema"); "live" is the pass as it has always been
+        self.weights = weights
+        if weights == "ema" and getattr(self.stepper, "ema", None) is None:
+            raise ValueError("weights='ema' needs a stepper that keeps a weight EMA (VAEStepper(..., ema_decay > 0))")
         self.batch: Optional[int] = None               # pinned by the first batch
         self._bufs: Dict[int, dict] = {}
         self._acc: Optional[torch.Tensor] = None
@@ -117,7 +124,16 @@ class Validator:
         """One pass.  batches: device tensors, uint8 [B,128,128,3] (as the feeder delivers them) or float [B,3,128,128] in [-1, 1];
         n_valid_per_batch: how many leading rows of each count.  Keys: val_recon_loss, val_kl_loss, val_loss (= recon_weight * recon +
         kl_weight * kl: no policy-gradient term), val_psnr, val_psnr_min, val_psnr_max, val_ssim, val_quality (with a teacher) and
-        n.  Per-sample means over the held-out sprites of ALL ranks; n = 0 gives NaN for every metric."""
+        n.  Per-sample means over the held-out sprites of ALL ranks; n = 0 gives NaN for every metric.  ``weights="ema"``: the same
+        pass on the stepper's averaged weights, plus ``"val_weights": "ema"``."""
+        if self.weights == "ema":
+            with self.stepper.ema_weights():
+                out = self._run(batches, n_valid_per_batch)
+            out["val_weights"] = "ema"
+            return out
+        return self._run(batches, n_valid_per_batch)
+
+    def _run(self, batches: Iterable[torch.Tensor], n_valid_per_batch: Iterable[int]) -> Dict[str, float]:
         dev = self.vae.flat_parameters().device
         if self._acc is None or self._acc.device != dev:
             self._acc = torch.zeros(8, dtype=torch.float64, device=dev)

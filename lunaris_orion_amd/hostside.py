@@ -5,6 +5,7 @@ as `torch.optim.AdamW.state_dict()`s, so a checkpoint written here resumes in th
 Nothing here touches the GPU kernels; tensors arrive as CPU copies or are copied once."""
 from __future__ import annotations
 
+import logging
 import time
 from collections import OrderedDict
 from pathlib import Path
@@ -30,6 +31,25 @@ class EarlyStopping:
                 self.early_stop = True
         else:
             self.best_loss, self.counter = loss, 0
+
+
+def ema_decay_at(decay: float, updates_so_far: int, warmup: bool = False) -> float:
+    """Per-step decay of the weight EMA (VAEStepper(ema_decay=...)) at the optimizer step that follows `updates_so_far` earlier ones.
+
+    Without warm-up: `decay`.  With it: min(decay, (1 + t) / (10 + t)), so that a young average follows the weights (0.1 at t = 0,
+    0.53 at t = 9) instead of keeping the initial ones for 1 / (1 - decay) steps.  t counts the optimizer steps ATTEMPTED since the
+    average began (construction, or a resume without an EMA in the checkpoint): a step whose update the device skipped (non-finite
+    gradient norm) leaves the average's bits alone but still counts here -- the host never waits to learn which steps those were."""
+    if not warmup:
+        return float(decay)
+    t = int(updates_so_far)
+    return min(float(decay), (1.0 + t) / (10.0 + t))
+
+
+def ema_one_minus_decay(step_decay: float, every: int = 1) -> float:
+    """What an EMA pass that stands for `every` optimizer steps is given: 1 - step_decay ** every, formed in double; the kernel's
+    argument is this value rounded to fp32 (ctypes does that)."""
+    return 1.0 - float(step_decay) ** int(every)
 
 
 def to_uint8_hwc(images: torch.Tensor) -> np.ndarray:
@@ -231,8 +251,42 @@ def checkpoint_dict(stepper, vae, teacher, global_step: int, best_loss: float, a
         extra["drop_calls"] = int(getattr(teacher, "drop_calls", 0))
     if best_val_loss is not None:
         extra["best_val_loss"] = float(best_val_loss)
+    if getattr(stepper, "ema", None) is not None:
+        # the averaged weights under the model's own keys: the reference's loader ignores the entry, and a reference user who wants
+        # them calls LunarCoreVAE.load_state_dict(ck["vae_ema_state_dict"]).  Without an EMA: no new key anywhere
+        ck["vae_ema_state_dict"] = dict(stepper.ema_state_dict())
+        extra.update(ema_decay=float(stepper.ema_decay), ema_every=int(stepper.ema_every), ema_warmup=bool(stepper.ema_warmup),
+                     ema_steps=int(stepper.ema_steps), ema_updates=int(stepper.ema_updates))
     ck["lunaris_amd_extra"] = extra
     return ck
+
+
+def restore_ema(ck: dict, stepper, vae) -> bool:
+    """Fills `stepper.ema` (a stepper built with ema_decay > 0) after the model's weights have been loaded.  From the checkpoint's
+    `vae_ema_state_dict` and the step counts beside it (True); a checkpoint without one -- the reference's, or a run without
+    --ema_decay -- restarts the average from the loaded parameters with the counts at 0, and one log line says so (False)."""
+    if getattr(stepper, "ema", None) is None:
+        return False
+    getattr(stepper, "synchronize_parameters", lambda: None)()      # an EMA pass of a pipelined step may still be writing the buffer
+    flat = vae.flat_parameters()
+    sd = ck.get("vae_ema_state_dict")
+    if not sd:
+        stepper.ema.copy_(flat)
+        stepper.ema_steps = stepper.ema_updates = 0
+        logging.getLogger("TrainHybrid.ema").info("checkpoint holds no vae_ema_state_dict: the weight EMA restarts from the loaded parameters (0 updates)")
+        return False
+    vp = OrderedDict(vae.named_parameters())
+    missing = [k for k in vp if k not in sd]
+    if missing:
+        raise KeyError(f"vae_ema_state_dict lacks {len(missing)} of the model's {len(vp)} parameters (first: {missing[0]})")
+    stepper.ema.copy_(flat)                                   # the padding between tensors as the flat buffer has it
+    for k, o in flat_offsets(vp, flat).items():
+        n = vp[k].numel()
+        stepper.ema[o:o + n].copy_(sd[k].reshape(-1).to(stepper.ema.dtype))
+    extra = ck.get("lunaris_amd_extra") or {}
+    stepper.ema_steps = int(extra.get("ema_steps", 0))
+    stepper.ema_updates = int(extra.get("ema_updates", 0))
+    return True
 
 
 def restored_best_val_loss(ck: dict) -> float:
@@ -264,4 +318,5 @@ def restore_checkpoint(ck: dict, stepper, vae, teacher) -> Tuple[int, float]:
         vae._seed, vae.noise_calls = None, int(extra["noise_calls"])          # re-derived (and advanced) at the next forward
     if teacher is not None and "drop_calls" in extra:
         teacher._drop_seed, teacher.drop_calls = None, int(extra["drop_calls"])
+    restore_ema(ck, stepper, vae)
     return int(ck.get("global_step", 0)), float(ck.get("best_loss", float("inf")))

@@ -18,6 +18,7 @@ The teacher's contribution is the detached scalar ``mean_advantage`` (SURVEY §3
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import os
@@ -136,7 +137,12 @@ class VAEStepper:
                  weight_decay: float = 0.01, max_grad_norm: float = 1.0, recon_weight: float = 1.0, kl_weight: float = 0.1,
                  gradient_accumulation_steps: int = 1, betas=(0.9, 0.999), eps: float = 1e-8,
                  grad_sync: Optional[Callable[[torch.Tensor], None]] = None, pipeline_optimizer: bool = False,
-                 dp_factored_adamw: Optional[bool] = None, accumulate_gradients: bool = False):
+                 dp_factored_adamw: Optional[bool] = None, accumulate_gradients: bool = False,
+                 ema_decay: float = 0.0, ema_every: int = 1, ema_warmup: bool = False):
+        if not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"ema_decay must be in [0, 1) (0 = no EMA), got {ema_decay}")
+        if int(ema_every) < 1:
+            raise ValueError(f"ema_every must be >= 1, got {ema_every}")
         _lib.require_gpu()
         if accumulate_gradients and grad_sync is not None and (int(getattr(grad_sync, "world", 1)) > 1 or getattr(grad_sync, "force", False)):
             # accumulation under data parallel (one exchange of the accumulated buffers per window, k * world factor blocks) is not
@@ -205,6 +211,16 @@ class VAEStepper:
         self._stage: Optional[torch.Tensor] = None
         self._fac_slots = {}            # batch -> accum factor blocks, slot i = micro-batch i of the window
         self._deferred_scale = []       # loss-scale observations made inside a window (metrics()): evaluated at its end
+        # Weight EMA (opt-in; 0 = off: no buffer, no call, the step launches what it launches without the argument).  `ema` is an fp32
+        # copy of the flat buffer that follows it by lo_vae_ema_update after every `ema_every`-th optimizer step (DESIGN.md section
+        # 6d); evaluation, samples and checkpoints read it through ema_weights() / ema_state_dict().  Like the parameters it may
+        # still be in flight after a pipelined step: synchronize_parameters() before reading it with your own torch ops.  Data
+        # parallel needs no exchange: every rank applies the same update to the same parameters, so the averages are identical.
+        self.ema_decay, self.ema_every, self.ema_warmup = float(ema_decay), int(ema_every), bool(ema_warmup)
+        self.ema: Optional[torch.Tensor] = flat.clone() if self.ema_decay > 0 else None
+        self.ema_steps = 0              # optimizer steps attempted since the average began (hostside.ema_decay_at's t)
+        self.ema_updates = 0            # EMA passes enqueued (ema_steps // ema_every)
+        self._ema_open = False          # inside ema_weights(): the flat buffer holds the average, the live weights are in a backup
 
     @property
     def lr(self) -> float:
@@ -214,6 +230,7 @@ class VAEStepper:
              mean_advantage: float = 0.0, adv_dev: Optional[torch.Tensor] = None):
         """One micro-batch.  Returns (recon, mu, logvar); losses stay on the device in ``self.losses``."""
         vae = self.vae
+        self._require_live_weights()
         images = images.detach().contiguous().float()
         first, last, slot = self._window_advance(images.shape[0], batch_idx)
         recon, mu, logvar, eng = vae._native_forward(images, eps, target=images)
@@ -503,6 +520,7 @@ class VAEStepper:
             eng.packed_version = self.vae._current_version()     # this engine's operand copies were refreshed by the call itself
             if self.pipeline_optimizer:
                 self._pipelined_engine = eng
+            self._ema_after_step(flat, st, eng)
             return
         if pre is not None:
             _lib.check(_lib.lib.lo_clip_adamw_step_presummed(flat.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(),
@@ -510,6 +528,88 @@ class VAEStepper:
         else:
             _lib.check(_lib.lib.lo_clip_adamw_step(flat.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
                                                    flat.numel(), *args), "lo_clip_adamw_step")
+        self._ema_after_step(flat, st, None)
+
+    # ---- weight EMA (ema_decay > 0) --------------------------------------------------------------------------------------------------
+    @property
+    def ema_decay_now(self) -> float:
+        """The per-step decay the next optimizer step's EMA runs at (`hostside.ema_decay_at`: `ema_decay`, lower during warm-up)."""
+        from .hostside import ema_decay_at
+        return ema_decay_at(self.ema_decay, self.ema_steps, self.ema_warmup)
+
+    def _ema_after_step(self, flat: torch.Tensor, st, eng) -> None:
+        """Right behind an optimizer step: every `ema_every`-th one moves the average, with the per-step decay of THIS step
+        (`ema_decay_now`) raised to the power `ema_every` -- the weight the average would have kept over the steps it sat out.  The
+        pass is gated by the step's norm block, so an update the device skipped leaves the average's bits alone; through the engine
+        it is ordered behind the pipelined AdamW on the library's side stream (lo_vae_ema_update)."""
+        if self.ema is None:
+            return
+        from .hostside import ema_one_minus_decay
+        decay = self.ema_decay_now
+        self.ema_steps += 1
+        if self.ema_steps % self.ema_every != 0:
+            return
+        omd = ema_one_minus_decay(decay, self.ema_every)
+        if eng is not None:
+            _lib.check(_lib.lib.lo_vae_ema_update(eng.handle, flat.data_ptr(), self.ema.data_ptr(), omd, self.scratch.data_ptr(), st),
+                       "lo_vae_ema_update")
+        else:
+            _lib.check(_lib.lib.lo_ema_update(self.ema.data_ptr(), flat.data_ptr(), flat.numel(), omd, self.scratch.data_ptr() + 4096, st),
+                       "lo_ema_update")
+        self.ema_updates += 1
+
+    def _require_ema(self) -> None:
+        if self.ema is None:
+            raise RuntimeError("this stepper keeps no weight EMA (construct it with ema_decay > 0)")
+
+    def _require_live_weights(self) -> None:
+        if self._ema_open:
+            raise RuntimeError("step() inside ema_weights(): the model holds the averaged weights; leave the block before training on")
+
+    def _join_engines(self) -> None:
+        """The current stream waits for the side-stream work of EVERY engine of the model (operand refreshes read the flat buffer)."""
+        for eng in self.vae._engines.values():
+            _lib.check(_lib.lib.lo_vae_join(eng.handle, _lib.stream_ptr()), "lo_vae_join")
+
+    def ema_state_dict(self):
+        """The averaged weights under the model's ``state_dict`` keys (CPU clones, cut from the EMA buffer at the parameters' flat
+        offsets): ``LunarisCoreVAE.load_state_dict`` and the reference's ``LunarCoreVAE.load_state_dict`` take it."""
+        from collections import OrderedDict
+        from .hostside import flat_offsets
+        self._require_ema()
+        self.synchronize_parameters()
+        vp = OrderedDict(self.vae.named_parameters())
+        offs = flat_offsets(vp, self.vae.flat_parameters())
+        keys = list(self.vae.state_dict().keys())
+        assert keys == list(vp.keys()), "the VAE's state_dict holds its parameters and nothing else"
+        return OrderedDict((k, self.ema[offs[k]:offs[k] + vp[k].numel()].detach().cpu().reshape(vp[k].shape).clone()) for k in keys)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """``with stepper.ema_weights():`` -- inside the block the model computes with the averaged weights (``vae(x)``, ``decode``,
+        ``sample``, ``Validator``, every engine of every batch size); on exit the live weights are back bit for bit.  A content
+        swap through one backup buffer: flat -> backup, EMA -> flat on entry, backup -> flat on exit, each followed by
+        ``mark_weights_changed()`` so that every engine re-packs its operands from what the flat buffer then holds (a pack is a
+        function of the fp32 values alone, so the operands of the live weights come back bit for bit as well).  The backup (the
+        size of the flat buffer) lives only while the block is open.  ``step()`` inside the block raises; blocks do not nest."""
+        self._require_ema()
+        if self._ema_open:
+            raise RuntimeError("ema_weights() blocks do not nest")
+        vae = self.vae
+        flat = vae.flat_parameters()
+        self.synchronize_parameters()          # the pipelined AdamW and the EMA pass behind it
+        self._join_engines()                   # ... and whatever else still reads the flat buffer on a side stream
+        backup = flat.clone()
+        flat.copy_(self.ema)
+        vae.mark_weights_changed()
+        self._ema_open = True
+        try:
+            yield vae
+        finally:
+            self._join_engines()               # operand refreshes of the averaged weights may still be reading the flat buffer
+            flat.copy_(backup)
+            vae.mark_weights_changed()
+            self._ema_open = False
 
     def decode_sprites(self, u8_hwc: torch.Tensor) -> torch.Tensor:
         """uint8 [B,128,128,3] on the device -> normalised float32 [B,3,128,128] (`decode_sprites_u8`)."""
@@ -640,6 +740,7 @@ class HybridStepper(VAEStepper):
 
     def step(self, images: torch.Tensor, batch_idx: int = 0, eps: Optional[torch.Tensor] = None, **_):
         vae, t = self.vae, self.teacher
+        self._require_live_weights()
         images = images.detach().contiguous().float()
         B = images.shape[0]
         st = _lib.stream_ptr()

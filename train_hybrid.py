@@ -20,10 +20,14 @@ loss is a real number, checkpoints are written.  Launch one process per GPU with
 `--validate_every N` (a builder flag, default 0 = off: the reference's rule, bit for bit) validates the held-out tenth of the split,
 which the reference sets aside and never reads (:552-573), at the end of every N-th epoch and lets `val_loss` decide early stopping
 and best.pt; `--validate_only --resume_from CKPT` validates a checkpoint once and prints one JSON line.
+
+`--ema_decay D` (a builder flag, default 0 = off) keeps an exponential moving average of the VAE's weights, updated on the device behind
+every optimizer step; validation, `--generate_samples` and the checkpoint's `vae_ema_state_dict` then use the averaged weights.
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import logging
 import os
 import signal
@@ -111,6 +115,15 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--validate_only", action="store_true",
                    help="with --resume_from: validate the checkpoint once on the held-out tenth, print one JSON line of the metrics and exit; "
                         "no training step is taken and nothing is saved")
+    p.add_argument("--ema_decay", type=float, default=0.0,
+                   help="keep an exponential moving average of the VAE's weights beside the optimizer state (one HIP pass per optimizer step, "
+                        "ordered behind the pipelined AdamW): ema <- ema + (w - ema) * (1 - D) per step.  With it on, --validate_every / "
+                        "--validate_only validate the AVERAGED weights (so early stopping and best.pt follow them), --generate_samples decodes "
+                        "with them, and checkpoints carry them as vae_ema_state_dict.  0 = off: nothing changes")
+    p.add_argument("--ema_every", type=int, default=1,
+                   help="with --ema_decay: update the average on every K-th optimizer step only, with the decay raised to the K-th power")
+    p.add_argument("--ema_warmup", action="store_true",
+                   help="with --ema_decay: the per-step decay is min(D, (1 + t) / (10 + t)) after t optimizer steps, so a young average follows the weights")
     return p
 
 
@@ -125,6 +138,10 @@ def parse_args(argv=None) -> argparse.Namespace:
                      "drop --vae_only, or pass --reward_scale 0 --quality_weight 0 to keep the teacher's own objective out")
     if args.validate_every < 0:
         parser.error("--validate_every must be >= 0")
+    if not 0.0 <= args.ema_decay < 1.0:
+        parser.error("--ema_decay must be in [0, 1) (0 = off)")
+    if args.ema_every < 1:
+        parser.error("--ema_every must be >= 1")
     if args.validate_only and not args.resume_from:
         parser.error("--validate_only needs --resume_from (the checkpoint to validate)")
     return args
@@ -189,7 +206,12 @@ def main(argv=None):
                   max_grad_norm=args.max_grad_norm, recon_weight=args.recon_weight, kl_weight=args.kl_weight,
                   gradient_accumulation_steps=args.gradient_accumulation_steps, grad_sync=grad_sync,
                   pipeline_optimizer=True,     # Linear / decoder update beside the next encoder forward; checkpoints synchronise first
-                  accumulate_gradients=args.accumulate_gradients)
+                  accumulate_gradients=args.accumulate_gradients,
+                  ema_decay=args.ema_decay, ema_every=args.ema_every, ema_warmup=args.ema_warmup)
+    ema_on = args.ema_decay > 0
+    if ema_on:
+        log.info(f"weight EMA on: decay {args.ema_decay} per optimizer step" + (f", updated every {args.ema_every} steps" if args.ema_every > 1 else "")
+                 + (", warm-up min(decay, (1 + t) / (10 + t))" if args.ema_warmup else "") + "; validation, samples and vae_ema_state_dict use the averaged weights")
     if args.accumulate_gradients:
         log.info(f"gradient accumulation on: every update sees {args.gradient_accumulation_steps} micro-batches of {args.batch_size} "
                  f"(effective batch {args.gradient_accumulation_steps * args.batch_size})")
@@ -222,12 +244,17 @@ def main(argv=None):
         stepper.synchronize_parameters()          # the pipelined optimizer step may still be updating the decoder's parameters
         torch.cuda.synchronize()
         stepper.check_device_health()             # raises instead of writing a checkpoint after a lost launch (rendezvous-failure word)
-        torch.save(hostside.checkpoint_dict(stepper, vae, teacher, global_step, best_loss, vars(args), best_val_loss if validating else None),
+        # a run without --ema_decay writes the checkpoint it has always written: the three flags are not among its `args` either
+        saved_args = {k: v for k, v in vars(args).items() if ema_on or not k.startswith("ema_")}
+        torch.save(hostside.checkpoint_dict(stepper, vae, teacher, global_step, best_loss, saved_args, best_val_loss if validating else None),
                    out_dir / "checkpoints" / f"{tag}.pt")
         log.info(f"Checkpoint saved at step {global_step}")
 
     if args.resume_from:
         ck = torch.load(args.resume_from, map_location="cpu", weights_only=True)
+        if args.validate_only and ema_on and not ck.get("vae_ema_state_dict"):
+            raise SystemExit(f"--validate_only --ema_decay: {args.resume_from} holds no vae_ema_state_dict (it was written without --ema_decay, or by "
+                             "the reference), so there are no averaged weights to validate; drop --ema_decay to validate its live weights")
         global_step, best_loss = hostside.restore_checkpoint(ck, stepper, vae, teacher)
         if validating:
             best_val_loss = hostside.restored_best_val_loss(ck)
@@ -244,7 +271,7 @@ def main(argv=None):
     validator = None
     if validating:
         from lunaris_orion_amd.evaluate import Validator
-        validator = Validator(stepper, teacher)
+        validator = Validator(stepper, teacher, weights="ema" if ema_on else "live")
         val_idx = perm[n_train:]                              # the tenth random_split sets aside (:555-556)
 
     def validate():
@@ -284,8 +311,11 @@ def main(argv=None):
                 if writer is not None:
                     for k, v in metrics.items():
                         writer.add_scalar(k, v, global_step)
+                if ema_on and writer is not None:
+                    writer.add_scalar("ema_decay", stepper.ema_decay_now, global_step)
                 log.info(f"step {global_step} loss {metrics['total_loss']:.4f} recon {metrics['recon_loss']:.4f} "
-                         f"kl {metrics['kl_loss']:.4f} lr {m['lr']:.2e} grad_norm {m['grad_norm']:.3f}")
+                         f"kl {metrics['kl_loss']:.4f} lr {m['lr']:.2e} grad_norm {m['grad_norm']:.3f}"
+                         + (f" ema_decay {stepper.ema_decay_now:.6f}" if ema_on else ""))
             if args.save_every > 0 and global_step % args.save_every == 0:                 # train_hybrid.py:1113,1115 (dead flags there)
                 save_checkpoint(f"step_{global_step}")
                 if rank == 0:
@@ -327,8 +357,9 @@ def main(argv=None):
             if val is not None:
                 if writer is not None:
                     for k, v in val.items():
-                        writer.add_scalar(k, v, global_step)
-                log.info(f"Epoch {epoch + 1} Validation: " + " ".join(f"{k} {v:.6g}" for k, v in val.items())
+                        if not isinstance(v, str):                                         # "val_weights": "ema" is not a scalar
+                            writer.add_scalar(k, v, global_step)
+                log.info(f"Epoch {epoch + 1} Validation: " + " ".join(f"{k} {v}" if isinstance(v, str) else f"{k} {v:.6g}" for k, v in val.items())
                          + f" best_val_loss {best_val_loss:.6g}")
                 early(val["val_loss"])
                 if early.early_stop:
@@ -349,7 +380,9 @@ def main(argv=None):
         if done:
             break
     if rank == 0 and args.generate_samples > 0:
-        paths = hostside.save_samples(out_dir, vae.sample(args.generate_samples), global_step)
+        with (stepper.ema_weights() if ema_on else contextlib.nullcontext()):             # the averaged weights, if the run keeps them
+            images = vae.sample(args.generate_samples)
+        paths = hostside.save_samples(out_dir, images, global_step)
         log.info(f"Generated and saved {len(list(paths))} samples")
     if writer is not None:
         writer.close()
