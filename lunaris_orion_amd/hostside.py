@@ -207,7 +207,7 @@ def checkpoint_dict(stepper, vae, teacher, global_step: int, best_loss: float, a
         tp = OrderedDict(teacher.named_parameters())
         from .trainer import cosine_warm_restarts_lr
         t_lr = cosine_warm_restarts_lr(stepper.teacher_base_lr, stepper.min_lr, stepper.t0, 2, stepper.opt_steps)
-        if getattr(stepper, "_t_ready", False):
+        if getattr(stepper, "teacher_optimizer_ready", False):
             b, e = stepper.t_range
             offs = flat_offsets(tp, teacher._flat)
             live = [k for k, o in offs.items() if b <= o < e]
@@ -308,7 +308,7 @@ def restore_checkpoint(ck: dict, stepper, vae, teacher) -> Tuple[int, float]:
     elif ck.get("vae_scheduler", {}).get("last_epoch") is not None:
         stepper.opt_steps = int(ck["vae_scheduler"]["last_epoch"])
     if teacher is not None and (ck.get("teacher_optimizer") or {}).get("state"):
-        stepper._pending_teacher_opt = ck["teacher_optimizer"]          # applied once the teacher buffers exist (first step)
+        stepper.load_teacher_optimizer_state(ck["teacher_optimizer"])   # applied once the teacher buffers exist (first step)
     extra = ck.get("lunaris_amd_extra") or {}
     if "loss_scale" in extra:
         vae.loss_scale = float(extra["loss_scale"])

@@ -279,6 +279,160 @@ class FlatGradSync:
         self.finish()
 
 
+def grad_range(eng, query: str):
+    """One of the library's two-`size_t` queries on a VAE engine (the lo_vae_*_grad_range family, lo_vae_factor_block) as a pair of ints."""
+    import ctypes as C
+    from . import _lib
+    first, second = C.c_size_t(), C.c_size_t()
+    _lib.check(getattr(_lib.lib, query)(eng.handle, C.byref(first), C.byref(second)), query)
+    return first.value, second.value
+
+
+def set_linear_mode(eng, mode: int) -> None:
+    """lo_vae_set_linear_factored, if the engine is not in that mode already (`eng.fac_mode` mirrors the library's state)."""
+    from . import _lib
+    if eng.fac_mode != mode:
+        _lib.check(_lib.lib.lo_vae_set_linear_factored(eng.handle, mode), "lo_vae_set_linear_factored")
+        eng.fac_mode = mode
+
+
+def backward_phase(eng, phase: int, bargs) -> None:
+    """One part of the phased VAE backward (1: everything from fc_mu.weight on, 2: the encoder, or 3 + 4: its last stage, the rest)."""
+    from . import _lib
+    _lib.check(_lib.lib.lo_vae_backward_phase(eng.handle, phase, *bargs), f"lo_vae_backward_phase({phase})")
+
+
+class GradHandover:
+    """The hand-over protocol between the phased VAE backward and a `FlatGradSync`-like exchange (`backward`), and what it shares
+    with gradient accumulation: where the two Linear matrices lie in the flat buffer, the norm of gathered factor blocks, the factor
+    slots.  It is given the stepper's buffers -- the flat gradient buffer, the 1028-float optimizer scratch -- and its allocation
+    function for pure scratch; what it allocates is cached: the Gram scratch per (world, batch), the factor slots per batch.  It
+    holds no reference to the stepper: the exchange object and the stepper's public flags, which bench.py and tests change between
+    steps, are arguments of every call."""
+
+    def __init__(self, vae, grads: torch.Tensor, scratch: torch.Tensor, alloc, early_norm: bool = True):
+        self.vae, self.grads, self.scratch, self.alloc = vae, grads, scratch, alloc
+        self.early_norm = early_norm    # LO_EARLY_NORM != 0: the first range's share of the norm is taken behind its exchange
+        self._gram_scratch = {}         # (world, batch) -> Gram scratch of lo_vae_gathered_early_norm
+        self._linear_bounds = None      # linear_matrix_bounds
+        self._fac_slots = {}            # batch -> factor blocks of an accumulation window, slot i = micro-batch i
+
+    def factor_slots(self, eng, count: int, block_bytes: int) -> torch.Tensor:
+        if eng.batch not in self._fac_slots:
+            self._fac_slots[eng.batch] = self.alloc(count * block_bytes, eng.ws.device)
+        return self._fac_slots[eng.batch]
+
+    def norm_of_gathered(self, eng, gathered: torch.Tensor, world: int) -> None:
+        """The norm's share of everything from fc_mu.weight on into scratch[512..1024): the flat buffer, and the two matrices from
+        the Gram matrices of the `world` gathered factor blocks (lo_vae_gathered_early_norm; the engine is in mode 3)."""
+        from . import _lib
+        key = (world, eng.batch)
+        if key not in self._gram_scratch:
+            self._gram_scratch[key] = self.alloc(_lib.lib.lo_vae_gathered_scratch_bytes(eng.handle, world), gathered.device)
+        _lib.check(_lib.lib.lo_vae_gathered_early_norm(eng.handle, gathered.data_ptr(), world, self._gram_scratch[key].data_ptr(),
+                                                       self.grads.data_ptr(), self.scratch.data_ptr(), _lib.stream_ptr()),
+                   "lo_vae_gathered_early_norm")
+
+    def linear_matrix_bounds(self, eng):
+        """(end of fc_mu | fc_logvar.weight, begin of decoder.fc.weight, its end) in the flat buffer, from the module's layout table
+        by parameter name; checked once against the ranges the library reports."""
+        if self._linear_bounds is None:
+            at = {name: (o, n) for (name, _p), (o, n, _s) in zip(self.vae.named_parameters(), self.vae._layout)}
+            (mu, n_mu), (lv, n_lv), (fc, n_fc) = at["encoder.fc_mu.weight"], at["encoder.fc_logvar.weight"], at["decoder.fc.weight"]
+            lin_b, lin_e = grad_range(eng, "lo_vae_linear_grad_range")
+            assert lv == mu + n_mu and mu == lin_b == grad_range(eng, "lo_vae_phase1_grad_range")[0], "flat layout: head weights"
+            # decoder.fc.bias is the last tensor of the Linear range (32768 elements, aligned)
+            assert at["decoder.fc.bias"][0] == fc + n_fc == lin_e - 32768, "flat layout: decoder.fc"
+            self._linear_bounds = (lv + n_lv, fc, fc + n_fc)
+        return self._linear_bounds
+
+    def linear_mode(self, eng, sync, factored: bool, factored_adamw: bool, active: bool, early: bool) -> int:
+        """Mode of lo_vae_set_linear_factored for a data-parallel step: 0 the Linear weight gradients are exchanged like the rest,
+        2 (`factored`: the stepper's `dp_factored`) their factors are all-gathered and the averaged matrices materialised, 3 (opt-in,
+        `factored_adamw`: its `dp_factored_adamw`) norm and AdamW read the gathered factors.  Mode 3 needs the exchange's `then` hook on a GPU communication stream and world * padded batch <= 512
+        (lo_vae_gathered_scratch_bytes says so); otherwise mode 2, silently."""
+        from . import _lib
+        if not (factored and active and eng.batch <= 128):
+            return 0
+        world = int(getattr(sync, "world", 1))
+        if (factored_adamw and early and getattr(sync, "backend", "nccl") != "gloo"
+                and _lib.lib.lo_vae_gathered_scratch_bytes(eng.handle, world) > 0):
+            return 3
+        return 2
+
+    def backward(self, eng, bargs, sync, active: bool, factored: bool, factored_adamw: bool, three_phase: bool) -> Optional[int]:
+        """The phased backward with every range handed to the exchange the moment it is final.  Everything from fc_mu.weight to the
+        end of the flat buffer (Linear layers, decoder and final convs: 90 % of the bytes) is final after phase 1 and is exchanged
+        while the encoder backward runs; the encoder's last stage (94 % of the encoder bytes) is final after phase 3 and is exchanged
+        during stages 3..1; only the small remainder (7.7 MB) is exchanged with nothing left to hide it.  Returns the begin of the
+        first range if its share of the norm was taken behind its exchange (the optimizer step then reads only the rest), else None."""
+        from . import _lib
+        g = self.grads
+        b, e = grad_range(eng, "lo_vae_phase1_grad_range")
+        b4, e4 = grad_range(eng, "lo_vae_stage4_grad_range")
+        assert e4 == b and e == g.numel()
+        # FlatGradSync runs the exchange on its own stream: the phases then hand their range over as an event for THAT stream
+        # (lo_vae_set_async_handover) instead of holding this one up until the side stream's weight gradients have finished
+        hooks = getattr(sync, "supports_then", False)
+        early = self.early_norm and hooks
+        mode = self.linear_mode(eng, sync, factored, factored_adamw, active, early)
+        set_linear_mode(eng, mode)
+        _lib.check(_lib.lib.lo_vae_set_async_handover(eng.handle, 1 if hooks else 0), "lo_vae_set_async_handover")
+
+        def wait_range():
+            _lib.check(_lib.lib.lo_vae_wait_handover(eng.handle, _lib.stream_ptr()), "lo_vae_wait_handover")
+        kw = {"pre": wait_range} if hooks else {}
+        backward_phase(eng, 1, bargs)
+        presummed = self._exchange_first_range(eng, sync, mode, b, e, early, kw)
+        if three_phase:
+            backward_phase(eng, 3, bargs)
+            sync.begin(g[b4:e4], **kw)
+            backward_phase(eng, 4, bargs)
+            sync.begin(g[:b4])
+        else:                    # two-call form: the whole encoder range after phase 2
+            backward_phase(eng, 2, bargs)
+            sync.begin(g[:b])
+        sync.finish()
+        return b if presummed else None
+
+    def _exchange_first_range(self, eng, sync, mode: int, b: int, e: int, early: bool, kw) -> bool:
+        """Hands the phase-1 range [b, e) to the exchange.  True: the range's share of the sum of squares for clip_grad_norm_ (of
+        the AVERAGED gradients) was taken right behind the exchange on the communication stream, beside the encoder backward, so the
+        tail of the step reads only the encoder range.  Three forms, by the mode of lo_vae_set_linear_factored:
+          0  the whole range is averaged like any other;
+          2  the two Linear weight gradients travel as factors: all-gather, write the averaged matrices out locally, average the rest
+             of the range (head biases; decoder.fc.bias, decoder and final convs), then the norm of the range;
+          3  the factors are kept: the callback only notes what the all-gather delivered, and the hook behind the exchange of the
+             rest takes the norm -- the rest from the averaged flat buffer, the two matrices from the Gram matrices of the gathered
+             factors -- and leaves the gathered buffer to the optimizer step."""
+        from . import _lib
+        g = self.grads
+        if mode == 0:
+            if early:
+                return sync.begin(g[b:e], sumsq_scratch=self.scratch.data_ptr(), **kw)
+            sync.begin(g[b:e], **kw)
+            return False
+        fo, fb = grad_range(eng, "lo_vae_factor_block")
+        factors = eng.ws[fo:fo + fb]
+        h_end, d_beg, d_end = self.linear_matrix_bounds(eng)
+        pieces = [g[h_end:d_beg], g[d_end:e]]
+        if mode == 3:
+            seen = []
+            if not sync.begin_factored(pieces, factors, lambda gathered, world: seen.append((gathered, world)),
+                                       then=lambda: self.norm_of_gathered(eng, *seen[-1]), **kw):
+                raise RuntimeError("dp_factored_adamw: the gradient exchange did not run its hooks (begin_factored returned False)")
+            return True
+
+        def materialize(gathered, world):
+            _lib.check(_lib.lib.lo_vae_materialize_gathered_linear_grads(eng.handle, gathered.data_ptr(), world, g.data_ptr(), _lib.stream_ptr()),
+                       "lo_vae_materialize_gathered_linear_grads")
+
+        def norm_of_range():
+            _lib.check(_lib.lib.lo_gradnorm_early_range(g.data_ptr(), b, e, self.scratch.data_ptr(), _lib.stream_ptr()), "lo_gradnorm_early_range")
+
+        return sync.begin_factored(pieces, factors, materialize, then=norm_of_range if early else None, **kw) and early
+
+
 def shard_batch(global_batch: torch.Tensor, rank: int, world: int) -> torch.Tensor:
     """Contiguous shard of a global batch for this rank (drop_last semantics like train_hybrid.py:569)."""
     per = global_batch.shape[0] // world

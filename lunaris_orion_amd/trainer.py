@@ -19,7 +19,6 @@ The teacher's contribution is the detached scalar ``mean_advantage`` (SURVEY §3
 from __future__ import annotations
 
 import contextlib
-import ctypes as C
 import math
 import os
 from typing import Callable, Dict, Optional
@@ -27,6 +26,7 @@ from typing import Callable, Dict, Optional
 import torch
 
 from . import _lib
+from .parallel import GradHandover, backward_phase, grad_range, set_linear_mode
 from .vae import LunarisCoreVAE
 
 
@@ -57,20 +57,6 @@ def decode_sprites_u8(u8_hwc: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def _set_linear_mode(eng, mode: int) -> None:
-    """lo_vae_set_linear_factored, if the engine is not in that mode already (`eng.fac_mode` mirrors the library's state)."""
-    if eng.fac_mode != mode:
-        _lib.check(_lib.lib.lo_vae_set_linear_factored(eng.handle, mode), "lo_vae_set_linear_factored")
-        eng.fac_mode = mode
-
-
-def _grad_range(eng, query: str):
-    """One of the library's two-`size_t` queries on an engine (the lo_vae_*_grad_range family, lo_vae_factor_block) as a pair of ints."""
-    first, second = C.c_size_t(), C.c_size_t()
-    _lib.check(getattr(_lib.lib, query)(eng.handle, C.byref(first), C.byref(second)), query)
-    return first.value, second.value
-
-
 class LossScalePolicy:
     """GradScaler's policy (torch.cuda.amp.GradScaler, used by train_hybrid.py:917-923) for observations that LAG the device.
 
@@ -96,6 +82,63 @@ class LossScalePolicy:
             self.changed_at = now
             return min(self.init, scale * 2.0)
         return scale
+
+
+class LossScaleObserver:
+    """GradScaler's update (train_hybrid.py:917-923) without a host sync: the device's skipped-update counter is copied to pinned
+    memory after optimizer steps (asynchronously) and evaluated when the copy has landed, i.e. one or two steps later.  Each
+    observation carries the optimizer-step index it was taken after, so that updates skipped at a scale that has since been changed
+    are not counted again (`LossScalePolicy`).  Data parallel (`fixed_lag`): the ranks must change the scale at the SAME step (the
+    scale multiplies fp16 activation gradients, a rank at a higher scale can overflow alone), so there the observation taken `DP_LAG`
+    steps earlier is waited for instead of polled -- a fixed lag, identical on every rank (the counters are: every rank sees the same
+    averaged gradients).  `in_window`: an accumulation window is open.  Every micro-batch of a window runs at ONE loss scale (its
+    factor blocks share one 1 / scale; the accumulator adds un-scaled gradients of one scale's fp16 range), so what is observed
+    inside one is kept and the policy sees it when the window has ended or the next begins."""
+    DP_LAG = 2      # data parallel: an observation is evaluated this many optimizer steps after it was enqueued
+
+    def __init__(self, vae, policy: LossScalePolicy, counter: torch.Tensor):
+        self.vae, self.policy, self.counter = vae, policy, counter
+        self._slots = [torch.zeros(1, dtype=torch.float32).pin_memory() for _ in range(self.DP_LAG + 1)]
+        self._inflight = []       # (event, pinned slot, optimizer-step index), oldest first
+        self._deferred = []       # observations made inside a window: (skipped total, optimizer-step index)
+
+    def window_begins(self, now: int) -> None:
+        """The policy sees what was observed inside the previous window, so that the scale a window runs at is fixed before its
+        first lo_vae_loss.  `now` = the optimizer step the host has enqueued up to."""
+        pending, self._deferred = self._deferred, []
+        for skipped_total, at in pending:
+            self.vae.loss_scale = self.policy.observe(self.vae.loss_scale, skipped_total, at, now)
+
+    def observed(self, skipped_total: float, at: int, now: int, in_window: bool = False) -> None:
+        """One host-side observation of the device's skipped-update counter, taken after optimizer step `at`."""
+        if in_window:
+            self._deferred.append((int(skipped_total), at))
+            return
+        self.vae.loss_scale = self.policy.observe(self.vae.loss_scale, int(skipped_total), at, now)
+
+    def step_enqueued(self, now: int, fixed_lag: bool) -> None:
+        """Behind every optimizer step: the counter of the step just enqueued travels to pinned memory behind it; whichever earlier
+        copy has landed by now is evaluated.  The host runs a step or two ahead of the GPU, so an overflow is answered after that
+        many skipped updates — not after `--log_every` of them, as when only metrics() looked."""
+        self.window_begins(now)           # accumulate_gradients: what metrics() saw inside the window that has just ended
+        # (no window is open here: under accumulation the optimizer step is the last call of one, so `observed` applies at once)
+        if fixed_lag:
+            # wait for the observation of `DP_LAG` steps ago (long finished unless the host runs further ahead than that)
+            while len(self._inflight) >= self.DP_LAG:
+                ev, slot, at = self._inflight.pop(0)
+                ev.synchronize()
+                self.observed(float(slot[0]), at, now)
+        else:
+            while self._inflight and self._inflight[0][0].query():
+                ev, slot, at = self._inflight.pop(0)
+                self.observed(float(slot[0]), at, now)
+        if len(self._inflight) < len(self._slots):
+            busy = {id(s_) for _, s_, _ in self._inflight}
+            slot = next(s_ for s_ in self._slots if id(s_) not in busy)
+            slot.copy_(self.counter, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            self._inflight.append((ev, slot, now))
 
 
 class AccumulationWindow:
@@ -131,7 +174,7 @@ class AccumulationWindow:
 
 
 class VAEStepper:
-    _DP_LAG = 2     # data parallel: an observation is evaluated this many optimizer steps after it was enqueued
+    _swallows_keywords = False      # step(): an unknown keyword is an error (HybridStepper ignores them)
 
     def __init__(self, vae: LunarisCoreVAE, lr: float = 1e-4, min_lr: float = 1e-6, scheduler_t0: int = 10,
                  weight_decay: float = 0.01, max_grad_norm: float = 1.0, recon_weight: float = 1.0, kl_weight: float = 0.1,
@@ -144,15 +187,16 @@ class VAEStepper:
         if int(ema_every) < 1:
             raise ValueError(f"ema_every must be >= 1, got {ema_every}")
         _lib.require_gpu()
-        if accumulate_gradients and grad_sync is not None and (int(getattr(grad_sync, "world", 1)) > 1 or getattr(grad_sync, "force", False)):
+        self.vae = vae
+        self.grad_sync = grad_sync      # data parallel: averages the flat gradient buffer across ranks (RCCL)
+        if accumulate_gradients and self._dp_active():
             # accumulation under data parallel (one exchange of the accumulated buffers per window, k * world factor blocks) is not
             # built; an exchange object of one rank averages nothing and is not called in the mode
             raise NotImplementedError("accumulate_gradients=True is single process only (grad_sync with world > 1 is not built)")
-        if getattr(vae, "attention", False) and grad_sync is not None and int(getattr(grad_sync, "world", 1)) > 1:
+        if getattr(vae, "attention", False) and self._dp_world() > 1:
             # the exchange ranges, the factor all-gather and the gathered-factor optimizer have never been run with the 86-tensor
             # layout: not offered untested
             raise NotImplementedError("data parallel (grad_sync with world > 1) is not built for LunarisCoreVAE(attention=True)")
-        self.vae = vae
         # pipeline_optimizer: the update of the Linear / decoder parameters (87 % of AdamW's 1.7 GB) and their operand refresh run
         # on the library's side stream beside the NEXT step's encoder forward (lo_vae_optimizer_step).  Parameters may then still
         # be in flight when step() returns: call synchronize_parameters() before touching them outside this stepper
@@ -164,7 +208,6 @@ class VAEStepper:
         self.recon_weight, self.kl_weight = recon_weight, kl_weight
         self.accum = max(1, int(gradient_accumulation_steps))
         self.betas, self.eps = betas, eps
-        self.grad_sync = grad_sync      # data parallel: averages the flat gradient buffer across ranks (RCCL)
         # The weight gradients of the three Linear layers (82 % of the parameters) are rank-B matrices: the fused step keeps them as
         # their factors -- norm from Gram matrices, gradient tiles formed inside the AdamW pass (csrc/lo_lowrank.hip) -- instead of
         # writing and re-reading 201 MB.  Single process, batch <= 128; LO_LINEAR_FACTORED=0: the materialised path (A/B).
@@ -177,9 +220,9 @@ class VAEStepper:
         # ... and, opt-in (LO_LINEAR_FACTORED=2, or dp_factored_adamw=True), never writes the averaged matrices either: norm and AdamW
         # read the gathered blocks (mode 3 of lo_vae_set_linear_factored; world * padded batch <= 512, else mode 2 as above)
         self.dp_factored_adamw = (knob == "2") if dp_factored_adamw is None else bool(dp_factored_adamw)
-        self._gram_scratch = {}         # (world, batch) -> Gram scratch of lo_vae_gathered_early_norm
-        self._linear_bounds = None      # _linear_matrix_bounds
         self.dp_three_phase = True      # hand the encoder's last stage over before stages 3..1 run (False: one encoder range)
+        # LO_EARLY_NORM=0 (A/B knob): no part of the norm is taken beside the encoder backward (the factored mode always takes its own)
+        self._early_norm = os.environ.get("LO_EARLY_NORM", "1") != "0"
         flat = vae.flat_parameters()
         self.grads = torch.zeros_like(flat)
         self.exp_avg = torch.zeros_like(flat)
@@ -188,29 +231,20 @@ class VAEStepper:
         self.losses = torch.zeros(4, dtype=torch.float32, device=flat.device)       # recon, kl, vae_loss, pg_loss
         self.opt_steps = 0
         self.last = None
-        self._scale_policy = LossScalePolicy()
-        # GradScaler policy without a host sync: the device's skipped-update counter is copied to pinned memory after optimizer
-        # steps (asynchronously) and evaluated when the copy has landed, i.e. one or two steps later.  Each observation carries the
-        # optimizer-step index it was taken after, so that updates skipped at a scale that has since been changed are not counted
-        # again (see _update_loss_scale).  Data parallel: the ranks must change the scale at the SAME step (the scale multiplies
-        # fp16 activation gradients, a rank at a higher scale can overflow alone), so there the observation taken `_DP_LAG` steps
-        # earlier is waited for instead of polled -- a fixed lag, identical on every rank (the counters are: every rank sees the
-        # same averaged gradients).
-        self._skip_slots = [torch.zeros(1, dtype=torch.float32).pin_memory() for _ in range(self._DP_LAG + 1)]
-        self._skip_inflight = []      # (event, pinned slot, optimizer-step index), oldest first
         self._last_engine = None
-        self._presummed_begin: Optional[int] = None   # set by a backward that left the early part of the gradient norm in the scratch
+        # the hand-over protocol of the data-parallel backward, and what the accumulation path shares with it (parallel.py)
+        self._exchange = GradHandover(vae, self.grads, self.scratch, _alloc_scratch, early_norm=self._early_norm)
         # accumulate_gradients (opt-in; off: nothing below is touched): every micro-batch of a window takes its backward and the
         # window's last call steps on the sum -- `self.grads` is the accumulator, the first micro-batch's backward writes straight
         # into it, the others write `_stage` and lo_grad_accumulate adds them.  The two Linear matrices, while the factored mode
-        # applies, are kept as one factor block per micro-batch (`_fac_slots`) and never written out: the gathered-factor passes of
-        # the data-parallel mode 3 read them, told to add instead of average (lo_vae_set_gathered_sum).
+        # applies, are kept as one factor block per micro-batch (`GradHandover.factor_slots`) and never written out: the
+        # gathered-factor passes of the data-parallel mode 3 read them, told to add instead of average (lo_vae_set_gathered_sum).
         self.accumulate = bool(accumulate_gradients)
         self._window = AccumulationWindow(self.accum) if self.accumulate else None
         self._win_batch = 0             # batch size of the open window
         self._stage: Optional[torch.Tensor] = None
-        self._fac_slots = {}            # batch -> accum factor blocks, slot i = micro-batch i of the window
-        self._deferred_scale = []       # loss-scale observations made inside a window (metrics()): evaluated at its end
+        self._scale_policy = LossScalePolicy()
+        self._loss_scale = LossScaleObserver(vae, self._scale_policy, self.scratch[1027:1028])
         # Weight EMA (opt-in; 0 = off: no buffer, no call, the step launches what it launches without the argument).  `ema` is an fp32
         # copy of the flat buffer that follows it by lo_vae_ema_update after every `ema_every`-th optimizer step (DESIGN.md section
         # 6d); evaluation, samples and checkpoints read it through ema_weights() / ema_state_dict().  Like the parameters it may
@@ -226,32 +260,63 @@ class VAEStepper:
     def lr(self) -> float:
         return cosine_warm_restarts_lr(self.base_lr, self.min_lr, self.t0, 2, self.opt_steps)
 
+    def _dp_world(self) -> int:
+        """Ranks of the exchange (`grad_sync.world`, which tests change between steps; 1 without an exchange object)."""
+        return int(getattr(self.grad_sync, "world", 1))
+
+    def _dp_linear_mode(self, eng, active: bool, early: bool) -> int:
+        """`GradHandover.linear_mode` for this stepper's exchange object and flags as they are now."""
+        return self._exchange.linear_mode(eng, self.grad_sync, self.dp_factored, self.dp_factored_adamw, active, early)
+
+    def _dp_active(self) -> bool:
+        """A data-parallel exchange is active: more than one rank, or an exchange object told to issue its collectives anyway."""
+        return self._dp_world() > 1 or bool(getattr(self.grad_sync, "force", False))
+
     def step(self, images: torch.Tensor, batch_idx: int = 0, eps: Optional[torch.Tensor] = None,
-             mean_advantage: float = 0.0, adv_dev: Optional[torch.Tensor] = None):
-        """One micro-batch.  Returns (recon, mu, logvar); losses stay on the device in ``self.losses``."""
+             mean_advantage: float = 0.0, adv_dev: Optional[torch.Tensor] = None, **ignored):
+        """One micro-batch.  Returns (recon, mu, logvar); losses stay on the device in ``self.losses``.  The one step body of both
+        steppers: HybridStepper threads the teacher through `_objective_inputs`, `_drecon_seed` and `_behind_vae_work`.  Here an
+        unknown keyword is a TypeError, as before; HybridStepper takes the advantage from its teacher and ignores `mean_advantage`,
+        `adv_dev` and every other keyword it is given (its `step(images, batch_idx, eps, **_)` of before)."""
+        if ignored and not self._swallows_keywords:
+            raise TypeError(f"step() got an unexpected keyword argument {next(iter(ignored))!r}")
         vae = self.vae
         self._require_live_weights()
         images = images.detach().contiguous().float()
+        # accumulate_gradients: every micro-batch of a window takes its gradients, the window's last call steps
         first, last, slot = self._window_advance(images.shape[0], batch_idx)
+        takes_grads = last or self.accumulate
         recon, mu, logvar, eng = vae._native_forward(images, eps, target=images)
         st = _lib.stream_ptr()
+        mean_advantage, adv_dev = self._objective_inputs(images, recon, takes_grads, mean_advantage, adv_dev, st)
         _lib.check(_lib.lib.lo_vae_loss(eng.handle, eng.ws.data_ptr(), self.recon_weight, self.kl_weight, float(mean_advantage),
                                         _lib.ptr(adv_dev), float(self.accum), self._chain_loss_scale(), self.losses.data_ptr(), st),
                    "lo_vae_loss")
-        if self.accumulate:
-            self._backward_accumulating(eng, images, recon, st, None, first, slot)
+        presummed = None
+        if takes_grads:
+            drecon = self._drecon_seed(eng, images, recon, first, st)
+            presummed = self._backward(eng, images, recon, drecon, first, slot, last, st)
         if last:
-            flat = vae._flat
-            if self.accumulate:
-                self._finish_window(eng, slot + 1, st)
-            else:
-                self._backward_and_exchange(eng, images, recon, st)
             lr = self.lr
             self.opt_steps += 1
-            self._clip_adamw(flat, lr, st, eng)
-            self._observe_skipped_updates()
+            self._clip_adamw(vae._flat, lr, st, eng, presummed)
+            self._loss_scale.step_enqueued(self.opt_steps, fixed_lag=self._dp_world() > 1)
+        if takes_grads:
+            self._behind_vae_work(recon, first, last, st)
         self.last = (recon, mu, logvar)
         return recon, mu, logvar
+
+    # ---- what HybridStepper overrides -----------------------------------------------------------------------------------------------
+    def _objective_inputs(self, images, recon, takes_grads: bool, mean_advantage: float, adv_dev, st):
+        """(mean_advantage, adv_dev) of lo_vae_loss; here the caller's."""
+        return mean_advantage, adv_dev
+
+    def _drecon_seed(self, eng, images, recon, first: bool, st) -> Optional[torch.Tensor]:
+        """An explicit, un-scaled d vae_loss / d recon for the backward, or None: the final conv's backward forms the MSE gradient."""
+        return None
+
+    def _behind_vae_work(self, recon, first: bool, last: bool, st) -> None:
+        """Behind the VAE's part of a call that takes gradients (on the last call of a window: behind its optimizer step)."""
 
     # ---- gradient accumulation (accumulate_gradients=True) ------------------------------------------------------------------------
     def _window_advance(self, batch: int, batch_idx: int):
@@ -262,13 +327,16 @@ class VAEStepper:
             return True, (batch_idx + 1) % self.accum == 0, 0
         first, last, slot = self._window.advance(batch_idx)
         if first:
-            self._apply_deferred_scale()
+            self._loss_scale.window_begins(self.opt_steps)
             self._win_batch = batch
         elif batch != self._win_batch:
             self._window.drop()
             raise ValueError(f"accumulate_gradients: every micro-batch of a window must have the same batch size (window of {self._win_batch}, "
                              f"got {batch} at batch_idx {batch_idx})")
         return first, last, slot
+
+    def _window_open(self) -> bool:
+        return self.accumulate and self._window.open
 
     def _window_factored(self, eng) -> bool:
         """The two Linear matrices of a window stay factor blocks: the factored mode is on, the batch is within its rank (128), the
@@ -283,252 +351,104 @@ class VAEStepper:
             _lib.check(_lib.lib.lo_grad_accumulate(acc.data_ptr() + 4 * begin, g.data_ptr() + 4 * begin, end - begin, 1.0, 0, st),
                        "lo_grad_accumulate")
 
-    def _backward_accumulating(self, eng, images: torch.Tensor, recon: torch.Tensor, st, drecon: Optional[torch.Tensor], first: bool,
-                               slot: int) -> None:
-        """One micro-batch's backward into the window's accumulator `self.grads`: the first writes it (every element: nothing of an
-        earlier window survives), the others write the staging buffer and are added.  Factored: the phased backward (data-parallel
-        mode 3) leaves this micro-batch's factor block, which is copied to its slot; the two matrices are in neither buffer.  No
-        backward of a window takes any part of the gradient norm (no scratch set): the norm is that of the sum, taken at the end."""
-        vae = self.vae
+    def _chain_loss_scale(self) -> float:
+        """The loss scale lo_vae_loss's seeds, the reward term and the backward are given.  Off: the model's.  On: times accum -- the
+        seeds carry 1 / accum, and with the scale raised by as much the fp16 activation gradients of every micro-batch are the ones a
+        plain step at accumulation 1 carries (no 1 / k taken out of fp16's range, the same roundings for a k that is no power of two);
+        the backward's fp32 `1 / scale` applies the 1 / accum instead.  One value for a whole window (`LossScaleObserver`)."""
+        return float(self.vae.loss_scale) * (self.accum if self.accumulate else 1)
+
+    # ---- the backward: one interface, three paths -------------------------------------------------------------------------------------
+    def _backward(self, eng, images: torch.Tensor, recon: torch.Tensor, drecon: Optional[torch.Tensor], first: bool, slot: int,
+                  last: bool, st) -> Optional[int]:
+        """Native backward of the fused loss into ``self.grads`` (micro-batches 2..k of an accumulation window: into the staging
+        buffer, then added).  drecon: the un-scaled d vae_loss / d recon as an explicit seed (``fused = 2``: the latent seeds stay
+        lo_vae_loss's) instead of the MSE gradient the final conv's backward forms itself -- the hybrid step's reward-gradient
+        objective.  Returns the presummed begin for the optimizer step: the flat index from which on the gradients' share of the norm
+        already lies in scratch[512..1024), or None when that step has to take the whole norm."""
         self._last_engine = eng
         if not first and self._stage is None:
             self._stage = torch.zeros_like(self.grads)
         G = self.grads if first else self._stage
-        bargs = (images.data_ptr(), vae._flat.data_ptr(), eng.ws.data_ptr(), recon.data_ptr(), images.data_ptr(),
+        bargs = (images.data_ptr(), self.vae._flat.data_ptr(), eng.ws.data_ptr(), recon.data_ptr(), images.data_ptr(),
                  1 if drecon is None else 2, _lib.ptr(drecon), None, None, self._chain_loss_scale(), G.data_ptr(), st)
+        # `accumulate` is fixed at construction; `grad_sync` is not (bench.py sets it to None for its rank-local leg)
+        if self.accumulate:
+            return self._backward_accumulating(eng, bargs, G, first, slot, last)
+        if hasattr(self.grad_sync, "begin"):
+            return self._exchange.backward(eng, bargs, self.grad_sync, self._dp_active(), self.dp_factored, self.dp_factored_adamw,
+                                           self.dp_three_phase)
+        return self._backward_single(eng, bargs)
+
+    def _backward_accumulating(self, eng, bargs, G: torch.Tensor, first: bool, slot: int, last: bool) -> Optional[int]:
+        """One micro-batch's backward into the window's accumulator `self.grads`: the first writes it (every element: nothing of an
+        earlier window survives), the others write the staging buffer and are added.  Factored: the phased backward (data-parallel
+        mode 3) leaves this micro-batch's factor block, which is copied to its slot; the two matrices are in neither buffer.  No
+        backward of a window takes any part of the gradient norm (no scratch set): the norm is that of the sum, taken at the end --
+        behind the window's last backward, factored, the norm's share of everything from fc_mu.weight on (the accumulated flat buffer,
+        and the Gram matrices of the filled factor blocks for the two matrices, cross terms between micro-batches included) goes to
+        scratch[512..1024) and the blocks are left to the optimizer step; materialised, that step takes the whole norm."""
+        st = bargs[-1]
         _lib.check(_lib.lib.lo_vae_set_gradnorm_scratch(eng.handle, None), "lo_vae_set_gradnorm_scratch")
         n = self.grads.numel()
-        if self._window_factored(eng):
-            _set_linear_mode(eng, 3)
+        factored = self._window_factored(eng)
+        if factored:
+            set_linear_mode(eng, 3)
             _lib.check(_lib.lib.lo_vae_set_gathered_sum(eng.handle, 1), "lo_vae_set_gathered_sum")
             _lib.check(_lib.lib.lo_vae_set_async_handover(eng.handle, 0), "lo_vae_set_async_handover")
-            _lib.check(_lib.lib.lo_vae_backward_phase(eng.handle, 1, *bargs), "lo_vae_backward_phase(1)")
-            _lib.check(_lib.lib.lo_vae_backward_phase(eng.handle, 2, *bargs), "lo_vae_backward_phase(2)")
-            fo, fb = _grad_range(eng, "lo_vae_factor_block")
-            self._factor_slots(eng, fb)[slot * fb:(slot + 1) * fb].copy_(eng.ws[fo:fo + fb])
-            h_end, d_beg, d_end = self._linear_matrix_bounds(eng)
-            ranges = ((0, _grad_range(eng, "lo_vae_linear_grad_range")[0]), (h_end, d_beg), (d_end, n))
+            backward_phase(eng, 1, bargs)
+            backward_phase(eng, 2, bargs)
+            fo, fb = grad_range(eng, "lo_vae_factor_block")
+            slots = self._exchange.factor_slots(eng, self.accum, fb)
+            slots[slot * fb:(slot + 1) * fb].copy_(eng.ws[fo:fo + fb])
+            h_end, d_beg, d_end = self._exchange.linear_matrix_bounds(eng)
+            ranges = ((0, grad_range(eng, "lo_vae_linear_grad_range")[0]), (h_end, d_beg), (d_end, n))
         else:
-            _set_linear_mode(eng, 0)
+            set_linear_mode(eng, 0)
             _lib.check(_lib.lib.lo_vae_backward(eng.handle, *bargs), "lo_vae_backward")
             ranges = ((0, n),)
         if not first:
             for b, e in ranges:
                 self._accumulate(self.grads, G, b, e, st)
+        if not (last and factored):
+            return None
+        self._exchange.norm_of_gathered(eng, slots[:(slot + 1) * fb], slot + 1)
+        return grad_range(eng, "lo_vae_phase1_grad_range")[0]
 
-    def _factor_slots(self, eng, block_bytes: int) -> torch.Tensor:
-        if eng.batch not in self._fac_slots:
-            self._fac_slots[eng.batch] = _alloc_scratch(self.accum * block_bytes, eng.ws.device)
-        return self._fac_slots[eng.batch]
-
-    def _finish_window(self, eng, filled: int, st) -> None:
-        """Behind the window's last backward: factored, the norm's share of everything from fc_mu.weight on -- the accumulated flat
-        buffer, and the Gram matrices of the `filled` factor blocks for the two matrices, cross terms between micro-batches included
-        -- goes to scratch[512..1024) and the blocks are left to the optimizer step; materialised, that step takes the whole norm."""
-        if not self._window_factored(eng):
-            return
-        fb = _grad_range(eng, "lo_vae_factor_block")[1]
-        self._norm_of_gathered(eng, self._factor_slots(eng, fb)[:filled * fb], filled)
-        self._presummed_begin = _grad_range(eng, "lo_vae_phase1_grad_range")[0]
-
-    def _chain_loss_scale(self) -> float:
-        """The loss scale lo_vae_loss's seeds, the reward term and the backward are given.  Off: the model's.  On: times accum -- the
-        seeds carry 1 / accum, and with the scale raised by as much the fp16 activation gradients of every micro-batch are the ones a
-        plain step at accumulation 1 carries (no 1 / k taken out of fp16's range, the same roundings for a k that is no power of two);
-        the backward's fp32 `1 / scale` applies the 1 / accum instead.  One value for a whole window (`_update_loss_scale`)."""
-        return float(self.vae.loss_scale) * (self.accum if self.accumulate else 1)
-
-    def _apply_deferred_scale(self) -> None:
-        pending, self._deferred_scale = self._deferred_scale, []
-        for skipped_total, at in pending:
-            self.vae.loss_scale = self._scale_policy.observe(self.vae.loss_scale, skipped_total, at, self.opt_steps)
-
-    def _observe_skipped_updates(self) -> None:
-        """Runs the loss-scale policy every optimizer step (the reference's GradScaler.update(), train_hybrid.py:917-923) with no
-        host synchronisation in the single-process case: the skipped-update counter of the step just enqueued travels to pinned
-        memory behind it; whichever earlier copy has landed by now is evaluated.  The host runs a step or two ahead of the GPU, so
-        an overflow is answered after that many skipped updates — not after `--log_every` of them, as when only metrics() looked."""
-        self._apply_deferred_scale()      # accumulate_gradients: what metrics() saw inside the window that has just ended
-        dp = self.grad_sync is not None and getattr(self.grad_sync, "world", 1) > 1
-        if dp:
-            # fixed lag: wait for the observation of `_DP_LAG` steps ago (long finished unless the host runs further ahead than that)
-            while len(self._skip_inflight) >= self._DP_LAG:
-                ev, slot, at = self._skip_inflight.pop(0)
-                ev.synchronize()
-                self._update_loss_scale(float(slot[0]), at)
-        else:
-            while self._skip_inflight and self._skip_inflight[0][0].query():
-                ev, slot, at = self._skip_inflight.pop(0)
-                self._update_loss_scale(float(slot[0]), at)
-        if len(self._skip_inflight) < len(self._skip_slots):
-            busy = {id(s_) for _, s_, _ in self._skip_inflight}
-            slot = next(s_ for s_ in self._skip_slots if id(s_) not in busy)
-            slot.copy_(self.scratch[1027:1028], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            self._skip_inflight.append((ev, slot, self.opt_steps))
-
-    def _backward_and_exchange(self, eng, images: torch.Tensor, recon: torch.Tensor, st, drecon: Optional[torch.Tensor] = None) -> None:
-        """Native backward of the fused loss into ``self.grads`` (+ the data-parallel exchange, overlapped with it).  drecon: the
-        un-scaled d vae_loss / d recon as an explicit seed (``fused = 2``: the latent seeds stay lo_vae_loss's) instead of the MSE
-        gradient the final conv's backward forms itself -- the hybrid step's reward-gradient objective."""
-        vae = self.vae
-        self._last_engine = eng
-        bargs = (images.data_ptr(), vae._flat.data_ptr(), eng.ws.data_ptr(), recon.data_ptr(), images.data_ptr(),
-                 1 if drecon is None else 2, _lib.ptr(drecon), None, None, float(vae.loss_scale), self.grads.data_ptr(), st)
-        if self.grad_sync is not None and hasattr(self.grad_sync, "begin"):
-            self._backward_data_parallel(eng, bargs)
-        else:
-            self._backward_single(eng, bargs)
-
-    def _backward_single(self, eng, bargs) -> None:
+    def _backward_single(self, eng, bargs) -> Optional[int]:
         """Single process (or a plain `grad_sync` callable): the backward takes the sum of squares of everything from fc_mu.weight on
         as soon as it is final, beside the encoder backward; _clip_adamw then reads only the encoder range for the norm."""
         fac = self.linear_factored and eng.batch <= 128
-        _set_linear_mode(eng, 1 if fac else 0)
-        early = self.grad_sync is None and (fac or os.environ.get("LO_EARLY_NORM", "1") != "0")       # LO_EARLY_NORM=0: A/B knob
+        set_linear_mode(eng, 1 if fac else 0)
+        early = self.grad_sync is None and (fac or self._early_norm)
         _lib.check(_lib.lib.lo_vae_set_gradnorm_scratch(eng.handle, self.scratch.data_ptr() if early else None),
                    "lo_vae_set_gradnorm_scratch")
         _lib.check(_lib.lib.lo_vae_backward(eng.handle, *bargs), "lo_vae_backward")
         if self.grad_sync is not None:
             self.grad_sync(self.grads)
         elif _lib.lib.lo_vae_gradnorm_presummed(eng.handle):
-            self._presummed_begin = _grad_range(eng, "lo_vae_phase1_grad_range")[0]
-
-    def _backward_data_parallel(self, eng, bargs) -> None:
-        """Everything from fc_mu.weight to the end of the flat buffer (Linear layers, decoder and final convs: 90 % of the bytes) is
-        final after phase 1 and is exchanged while the encoder backward runs; the encoder's last stage (94 % of the encoder bytes) is
-        final after phase 3 and is exchanged during stages 3..1; only the small remainder (7.7 MB) is exchanged with nothing left to
-        hide it."""
-        sync, g = self.grad_sync, self.grads
-        b, e = _grad_range(eng, "lo_vae_phase1_grad_range")
-        b4, e4 = _grad_range(eng, "lo_vae_stage4_grad_range")
-        assert e4 == b and e == g.numel()
-        # FlatGradSync runs the exchange on its own stream: the phases then hand their range over as an event for THAT stream
-        # (lo_vae_set_async_handover) instead of holding this one up until the side stream's weight gradients have finished
-        active = getattr(sync, "world", 1) > 1 or getattr(sync, "force", False)
-        hooks = getattr(sync, "supports_then", False)
-        early = os.environ.get("LO_EARLY_NORM", "1") != "0" and hooks
-        mode = self._dp_linear_mode(eng, active, early)
-        _set_linear_mode(eng, mode)
-        _lib.check(_lib.lib.lo_vae_set_async_handover(eng.handle, 1 if hooks else 0), "lo_vae_set_async_handover")
-
-        def wait_range():
-            _lib.check(_lib.lib.lo_vae_wait_handover(eng.handle, _lib.stream_ptr()), "lo_vae_wait_handover")
-        kw = {"pre": wait_range} if hooks else {}
-        _lib.check(_lib.lib.lo_vae_backward_phase(eng.handle, 1, *bargs), "lo_vae_backward_phase(1)")
-        if self._exchange_first_range(eng, mode, b, e, early, kw):
-            self._presummed_begin = b
-        if self.dp_three_phase:
-            _lib.check(_lib.lib.lo_vae_backward_phase(eng.handle, 3, *bargs), "lo_vae_backward_phase(3)")
-            sync.begin(g[b4:e4], **kw)
-            _lib.check(_lib.lib.lo_vae_backward_phase(eng.handle, 4, *bargs), "lo_vae_backward_phase(4)")
-            sync.begin(g[:b4])
-        else:                    # two-call form: the whole encoder range after phase 2
-            _lib.check(_lib.lib.lo_vae_backward_phase(eng.handle, 2, *bargs), "lo_vae_backward_phase(2)")
-            sync.begin(g[:b])
-        sync.finish()
-
-    def _exchange_first_range(self, eng, mode: int, b: int, e: int, early: bool, kw) -> bool:
-        """Hands the phase-1 range [b, e) to the exchange.  True: the range's share of the sum of squares for clip_grad_norm_ (of
-        the AVERAGED gradients) was taken right behind the exchange on the communication stream, beside the encoder backward, so the
-        tail of the step reads only the encoder range.  Three forms, by the mode of lo_vae_set_linear_factored:
-          0  the whole range is averaged like any other;
-          2  the two Linear weight gradients travel as factors: all-gather, write the averaged matrices out locally, average the rest
-             of the range (head biases; decoder.fc.bias, decoder and final convs), then the norm of the range;
-          3  the factors are kept: the callback only notes what the all-gather delivered, and the hook behind the exchange of the
-             rest takes the norm -- the rest from the averaged flat buffer, the two matrices from the Gram matrices of the gathered
-             factors -- and leaves the gathered buffer to the optimizer step."""
-        sync, g = self.grad_sync, self.grads
-        if mode == 0:
-            if early:
-                return sync.begin(g[b:e], sumsq_scratch=self.scratch.data_ptr(), **kw)
-            sync.begin(g[b:e], **kw)
-            return False
-        fo, fb = _grad_range(eng, "lo_vae_factor_block")
-        factors = eng.ws[fo:fo + fb]
-        h_end, d_beg, d_end = self._linear_matrix_bounds(eng)
-        pieces = [g[h_end:d_beg], g[d_end:e]]
-        if mode == 3:
-            seen = []
-            if not sync.begin_factored(pieces, factors, lambda gathered, world: seen.append((gathered, world)),
-                                       then=lambda: self._norm_of_gathered(eng, *seen[-1]), **kw):
-                raise RuntimeError("dp_factored_adamw: the gradient exchange did not run its hooks (begin_factored returned False)")
-            return True
-
-        def materialize(gathered, world):
-            _lib.check(_lib.lib.lo_vae_materialize_gathered_linear_grads(eng.handle, gathered.data_ptr(), world, g.data_ptr(), _lib.stream_ptr()),
-                       "lo_vae_materialize_gathered_linear_grads")
-
-        def norm_of_range():
-            _lib.check(_lib.lib.lo_gradnorm_early_range(g.data_ptr(), b, e, self.scratch.data_ptr(), _lib.stream_ptr()), "lo_gradnorm_early_range")
-
-        return sync.begin_factored(pieces, factors, materialize, then=norm_of_range if early else None, **kw) and early
-
-    def _norm_of_gathered(self, eng, gathered: torch.Tensor, world: int) -> None:
-        key = (world, eng.batch)
-        if key not in self._gram_scratch:
-            self._gram_scratch[key] = _alloc_scratch(_lib.lib.lo_vae_gathered_scratch_bytes(eng.handle, world), gathered.device)
-        _lib.check(_lib.lib.lo_vae_gathered_early_norm(eng.handle, gathered.data_ptr(), world, self._gram_scratch[key].data_ptr(),
-                                                       self.grads.data_ptr(), self.scratch.data_ptr(), _lib.stream_ptr()),
-                   "lo_vae_gathered_early_norm")
-
-    def _linear_matrix_bounds(self, eng):
-        """(end of fc_mu | fc_logvar.weight, begin of decoder.fc.weight, its end) in the flat buffer, from the module's layout table
-        by parameter name; checked once against the ranges the library reports."""
-        if self._linear_bounds is None:
-            at = {name: (o, n) for (name, _p), (o, n, _s) in zip(self.vae.named_parameters(), self.vae._layout)}
-            (mu, n_mu), (lv, n_lv), (fc, n_fc) = at["encoder.fc_mu.weight"], at["encoder.fc_logvar.weight"], at["decoder.fc.weight"]
-            lin_b, lin_e = _grad_range(eng, "lo_vae_linear_grad_range")
-            assert lv == mu + n_mu and mu == lin_b == _grad_range(eng, "lo_vae_phase1_grad_range")[0], "flat layout: head weights"
-            # decoder.fc.bias is the last tensor of the Linear range (32768 elements, aligned)
-            assert at["decoder.fc.bias"][0] == fc + n_fc == lin_e - 32768, "flat layout: decoder.fc"
-            self._linear_bounds = (lv + n_lv, fc, fc + n_fc)
-        return self._linear_bounds
-
-    def _dp_linear_mode(self, eng, active: bool, early: bool) -> int:
-        """Mode of lo_vae_set_linear_factored for a data-parallel step: 0 the Linear weight gradients are exchanged like the rest,
-        2 their factors are all-gathered and the averaged matrices materialised, 3 (opt-in) norm and AdamW read the gathered
-        factors.  Mode 3 needs the exchange's `then` hook on a GPU communication stream and world * padded batch <= 512
-        (lo_vae_gathered_scratch_bytes says so); otherwise mode 2, silently."""
-        if not (self.dp_factored and active and eng.batch <= 128):
-            return 0
-        world = int(getattr(self.grad_sync, "world", 1))
-        if (self.dp_factored_adamw and early and getattr(self.grad_sync, "backend", "nccl") != "gloo"
-                and _lib.lib.lo_vae_gathered_scratch_bytes(eng.handle, world) > 0):
-            return 3
-        return 2
+            return grad_range(eng, "lo_vae_phase1_grad_range")[0]
+        return None
 
     def synchronize_parameters(self) -> None:
         """Make the current stream wait for a pipelined optimizer step's side-stream work (no-op otherwise)."""
         if self._pipelined_engine is not None:
             _lib.check(_lib.lib.lo_vae_join(self._pipelined_engine.handle, _lib.stream_ptr()), "lo_vae_join")
 
-    def _clip_adamw(self, flat: torch.Tensor, lr: float, st, eng=None) -> None:
-        """clip_grad_norm_ + AdamW on the VAE's flat buffers (train_hybrid.py:913,921)."""
-        args = (float(self.max_grad_norm), float(lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
-                float(self.weight_decay), self.opt_steps, self.scratch.data_ptr(), st)
-        pre, self._presummed_begin = self._presummed_begin, None
-        if eng is not None:
-            # through the engine in both orders (LO_OPT_SERIAL = norm, AdamW, re-pack in order on this stream): its clip kernel reads the
-            # plan's rendezvous-failure word and skips the update on the device when a fused-GroupNorm wait of this step ran out
-            flags = (1 if pre is not None else 0) | (0 if self.pipeline_optimizer else 2)
-            _lib.check(_lib.lib.lo_vae_optimizer_step(eng.handle, flat.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(),
-                                                      self.exp_avg_sq.data_ptr(), eng.ws.data_ptr(), *args[:7], self.scratch.data_ptr(),
-                                                      flags, st), "lo_vae_optimizer_step")
-            self.vae.mark_weights_changed()
-            eng.packed_version = self.vae._current_version()     # this engine's operand copies were refreshed by the call itself
-            if self.pipeline_optimizer:
-                self._pipelined_engine = eng
-            self._ema_after_step(flat, st, eng)
-            return
-        if pre is not None:
-            _lib.check(_lib.lib.lo_clip_adamw_step_presummed(flat.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(),
-                                                             self.exp_avg_sq.data_ptr(), flat.numel(), pre, *args), "lo_clip_adamw_step_presummed")
-        else:
-            _lib.check(_lib.lib.lo_clip_adamw_step(flat.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                                                   flat.numel(), *args), "lo_clip_adamw_step")
-        self._ema_after_step(flat, st, None)
+    def _clip_adamw(self, flat: torch.Tensor, lr: float, st, eng, presummed: Optional[int]) -> None:
+        """clip_grad_norm_ + AdamW on the VAE's flat buffers (train_hybrid.py:913,921), through the engine in both orders (LO_OPT_SERIAL =
+        norm, AdamW, re-pack in order on this stream): its clip kernel reads the plan's rendezvous-failure word and skips the update on
+        the device when a fused-GroupNorm wait of this step ran out.  presummed: what the step's backward returned (`_backward`)."""
+        flags = (1 if presummed is not None else 0) | (0 if self.pipeline_optimizer else 2)
+        _lib.check(_lib.lib.lo_vae_optimizer_step(eng.handle, flat.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(),
+                                                  self.exp_avg_sq.data_ptr(), eng.ws.data_ptr(), float(self.max_grad_norm), float(lr),
+                                                  float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay),
+                                                  self.opt_steps, self.scratch.data_ptr(), flags, st), "lo_vae_optimizer_step")
+        self.vae.mark_weights_changed()
+        eng.packed_version = self.vae._current_version()     # this engine's operand copies were refreshed by the call itself
+        if self.pipeline_optimizer:
+            self._pipelined_engine = eng
+        self._ema_after_step(flat, st, eng)
 
     # ---- weight EMA (ema_decay > 0) --------------------------------------------------------------------------------------------------
     @property
@@ -550,12 +470,8 @@ class VAEStepper:
         if self.ema_steps % self.ema_every != 0:
             return
         omd = ema_one_minus_decay(decay, self.ema_every)
-        if eng is not None:
-            _lib.check(_lib.lib.lo_vae_ema_update(eng.handle, flat.data_ptr(), self.ema.data_ptr(), omd, self.scratch.data_ptr(), st),
-                       "lo_vae_ema_update")
-        else:
-            _lib.check(_lib.lib.lo_ema_update(self.ema.data_ptr(), flat.data_ptr(), flat.numel(), omd, self.scratch.data_ptr() + 4096, st),
-                       "lo_ema_update")
+        _lib.check(_lib.lib.lo_vae_ema_update(eng.handle, flat.data_ptr(), self.ema.data_ptr(), omd, self.scratch.data_ptr(), st),
+                   "lo_vae_ema_update")
         self.ema_updates += 1
 
     def _require_ema(self) -> None:
@@ -615,21 +531,11 @@ class VAEStepper:
         """uint8 [B,128,128,3] on the device -> normalised float32 [B,3,128,128] (`decode_sprites_u8`)."""
         return decode_sprites_u8(u8_hwc)
 
-    def _update_loss_scale(self, skipped_total: float, observed_after_step: Optional[int] = None) -> None:
-        """Feed one observation of the device's skipped-update counter to the loss-scale policy (`LossScalePolicy`)."""
-        at = self.opt_steps if observed_after_step is None else int(observed_after_step)
-        if self.accumulate and self._window.open:
-            # every micro-batch of a window runs at ONE loss scale (its factor blocks share one 1 / scale; the accumulator adds
-            # un-scaled gradients of one scale's fp16 range): the policy runs at optimizer steps only
-            self._deferred_scale.append((int(skipped_total), at))
-            return
-        self.vae.loss_scale = self._scale_policy.observe(self.vae.loss_scale, int(skipped_total), at, self.opt_steps)
-
     def metrics(self) -> Dict[str, float]:
         """Host copy of the last step's scalars (this synchronises the stream)."""
         v = torch.cat([self.losses, self.scratch[1024:1028], self._sync_fail_word()]).cpu().tolist()
         self._check_sync(v[8])
-        self._update_loss_scale(v[7])
+        self._loss_scale.observed(v[7], self.opt_steps, self.opt_steps, self._window_open())
         return {"recon_loss": v[0], "kl_loss": v[1], "vae_loss": v[2], "pg_loss": v[3], "grad_norm": v[4],
                 "clip_coef": v[5], "grads_finite": v[6], "lr": self.lr, "skipped_steps": v[7], "loss_scale": self.vae.loss_scale}
 
@@ -663,7 +569,7 @@ class VAEStepper:
         gradients of the last step are written out first (`lo_vae_materialize_linear_grads`: the tiles the AdamW pass formed).
         With ``accumulate_gradients`` these are the gradients accumulated over the last COMPLETE window (the matrices from its factor
         blocks); inside a window the buffers are half-filled and asking for them is an error."""
-        if self.accumulate and self._window.open:
+        if self._window_open():
             raise RuntimeError("accumulate_gradients: the gradients are complete after the last call of a window, not inside one")
         for eng in self.vae._engines.values():
             if eng is self._last_engine and _lib.lib.lo_vae_linear_factored(eng.handle):
@@ -683,6 +589,8 @@ class HybridStepper(VAEStepper):
     receive gradients in the reference (gate, quality_heads: SURVEY §3.2) + clip + AdamW on exactly those.
     Teacher dropout (the module's ``dropout_rate``, 0.1 like the reference unless constructed otherwise) is applied in both
     teacher calls, each with its own call seed; the heads' backward replays the masks of the evaluated call."""
+
+    _swallows_keywords = True       # step(images, batch_idx, eps, **_): the objective's inputs are the teacher's, whatever is passed
 
     def __init__(self, vae: LunarisCoreVAE, teacher, teacher_lr: float = 1e-4, quality_weight: float = 0.5, reward_scale: float = 0.1,
                  semantic_weight: float = 0.5, baseline_momentum: float = 0.9, run_dead_teacher_call: bool = True,
@@ -712,8 +620,32 @@ class HybridStepper(VAEStepper):
         self.seed_coef = torch.zeros(1, dtype=torch.float32, device=dev)         # un-scaled MSE coefficient of d vae_loss / d recon
         self._t_stage = None                     # accumulate_gradients: the teacher gradients of micro-batches 2..k before they are added
         self._t_ready = False                    # t_range, t_grads, t_m, t_v, t_scratch exist (_teacher_setup)
-        self._pending_teacher_opt = None         # a checkpoint's teacher optimizer state until then (hostside.restore_checkpoint)
+        self._t_checkpoint = None                # a checkpoint's teacher optimizer state until then (load_teacher_optimizer_state)
         self.last_teacher_out = None             # outputs of the last train-mode teacher(recon)
+
+    @property
+    def teacher_optimizer_ready(self) -> bool:
+        """The teacher's optimizer state (`t_range`, `t_grads`, `t_m`, `t_v`, `t_scratch`) exists: a step has run."""
+        return self._t_ready
+
+    def load_teacher_optimizer_state(self, state: dict) -> None:
+        """The teacher optimizer state of a checkpoint (hostside.restore_checkpoint): applied to `t_m` / `t_v` now if they exist,
+        else when the first step makes them."""
+        self._t_checkpoint = state
+        if self._t_ready:
+            self._apply_teacher_checkpoint()
+
+    def _apply_teacher_checkpoint(self) -> None:
+        from collections import OrderedDict
+        from .hostside import flat_offsets, load_adamw_state_dict
+        state, self._t_checkpoint = self._t_checkpoint, None
+        t, (b, e) = self.teacher, self.t_range
+        tp = OrderedDict(t.named_parameters())
+        offs = flat_offsets(tp, t._flat)
+        rel = {k: (o - b if b <= o < e else 0) for k, o in offs.items()}
+        names = list(tp.keys())
+        live = {"state": {i: st for i, st in state.get("state", {}).items() if b <= offs[names[int(i)]] < e}}
+        load_adamw_state_dict(live, tp, self.t_m, self.t_v, rel)
 
     def _teacher_setup(self, batch: int) -> None:
         """What the stepper owns of the teacher's update, made at the first step: the flat gradient, AdamW moments over `t_range`, the
@@ -727,27 +659,13 @@ class HybridStepper(VAEStepper):
         self.t_v = torch.zeros(e - b, dtype=torch.float32, device=t._flat.device)
         self.t_scratch = torch.zeros(1028, dtype=torch.float32, device=t._flat.device)
         self._t_ready = True
-        pending, self._pending_teacher_opt = self._pending_teacher_opt, None
-        if pending is not None:                       # optimizer state of a checkpoint (hostside.restore_checkpoint)
-            from collections import OrderedDict
-            from .hostside import flat_offsets, load_adamw_state_dict
-            tp = OrderedDict(t.named_parameters())
-            offs = flat_offsets(tp, t._flat)
-            rel = {k: (o - b if b <= o < e else 0) for k, o in offs.items()}
-            names = list(tp.keys())
-            live = {"state": {i: st for i, st in pending.get("state", {}).items() if b <= offs[names[int(i)]] < e}}
-            load_adamw_state_dict(live, tp, self.t_m, self.t_v, rel)
+        if self._t_checkpoint is not None:
+            self._apply_teacher_checkpoint()
 
-    def step(self, images: torch.Tensor, batch_idx: int = 0, eps: Optional[torch.Tensor] = None, **_):
-        vae, t = self.vae, self.teacher
-        self._require_live_weights()
-        images = images.detach().contiguous().float()
-        B = images.shape[0]
-        st = _lib.stream_ptr()
-        # accumulate_gradients: every micro-batch of a window takes its gradients (VAE and teacher), the window's last call steps
-        first, last, slot = self._window_advance(B, batch_idx)
-        takes_grads = last or self.accumulate
-        recon, mu, logvar, eng = vae._native_forward(images, eps, target=images)
+    # ---- the hooks of VAEStepper.step -------------------------------------------------------------------------------------------------
+    def _objective_inputs(self, images, recon, takes_grads: bool, mean_advantage, adv_dev, st):
+        """Between the VAE forward and lo_vae_loss: the teacher calls and the reward.  The advantage is the device's (`adv_dev`)."""
+        t, B = self.teacher, images.shape[0]
         if self.run_dead_teacher_call:
             t.update_statistics_only(images)            # train_hybrid.py:853-855 (side effects only)
         # train_hybrid.py:865 (no autograd node: the head gradients are taken below).  Full-backward mode: the plain forward that keeps
@@ -756,7 +674,7 @@ class HybridStepper(VAEStepper):
         self.last_teacher_out = tout
         self._teacher_setup(B)
         q_rows, s_rows, n_rows = tout["quality_scores"], tout["semantic_score"], B
-        if self.grad_sync is not None and (getattr(self.grad_sync, "world", 1) > 1 or getattr(self.grad_sync, "force", False)):
+        if self._dp_active():
             # data parallel: the baseline / advantage are functions of the batch means only (train_hybrid.py:870-883);
             # one 5-float all-reduce keeps them identical on every rank
             means = torch.cat([q_rows.mean(dim=0), s_rows.mean(dim=0)]).contiguous()
@@ -768,48 +686,25 @@ class HybridStepper(VAEStepper):
                                              float(self.semantic_weight), float(self.reward_scale), float(self.baseline_momentum),
                                              float(self.quality_weight), float(self.accum), self.reward_state.data_ptr(),
                                              self.reward_out.data_ptr(), self.adv_dev.data_ptr(), st), "lo_hybrid_reward")
-        _lib.check(_lib.lib.lo_vae_loss(eng.handle, eng.ws.data_ptr(), self.recon_weight, self.kl_weight, 0.0, self.adv_dev.data_ptr(),
-                                        float(self.accum), self._chain_loss_scale(), self.losses.data_ptr(), st), "lo_vae_loss")
-        drecon = None
-        if takes_grads:
-            if self.reward_grad_weight > 0:
-                # the eval forward below overwrites what the teacher's own backward reads (the kept train-mode tensors in bws, the
-                # pooled features and logits in ws, the call's dropout stream): its gradients are taken first, its update stays last
-                self._teacher_grads(t, recon, tout, first)
-                drecon = self._reward_grad_seed(t, eng, images, recon, st)
-            if self.accumulate:
-                self._backward_accumulating(eng, images, recon, st, drecon, first, slot)
-            if not last and drecon is None:
-                self._teacher_grads(t, recon, tout, first)
+        return 0.0, self.adv_dev
+
+    # `_teacher_grads` reads what the train-mode teacher(recon) of this call left (the kept tensors in bws, the pooled features and
+    # logits in ws, the call's dropout stream).  One rule places it: with a reward pass (`reward_grad_weight > 0`) it runs BEFORE that
+    # pass, whose eval forward overwrites all of this (`_drecon_seed`); otherwise at the end of the call's VAE work
+    # (`_behind_vae_work`).  The teacher's update stays last either way.
+    def _drecon_seed(self, eng, images, recon, first: bool, st) -> Optional[torch.Tensor]:
+        if self.reward_grad_weight <= 0:
+            return None
+        self._teacher_grads(self.teacher, recon, self.last_teacher_out, first)
+        return self._reward_grad_seed(self.teacher, eng, images, recon, st)
+
+    def _behind_vae_work(self, recon, first: bool, last: bool, st) -> None:
+        if self.reward_grad_weight <= 0:
+            self._teacher_grads(self.teacher, recon, self.last_teacher_out, first)
         if last:
-            flat = vae._flat
-            if self.accumulate:
-                self._finish_window(eng, slot + 1, st)
-            else:
-                self._backward_and_exchange(eng, images, recon, st, drecon)     # data parallel: exchange overlapped with the backward
-            lr = self.lr
-            t_lr = cosine_warm_restarts_lr(self.teacher_base_lr, self.min_lr, self.t0, 2, self.opt_steps)
-            self.opt_steps += 1
-            self._clip_adamw(flat, lr, st, eng)
-            self._observe_skipped_updates()
-            if drecon is None:
-                self._teacher_grads(t, recon, tout, first)
-            if self.teacher_full_backward:
-                self._teacher_full_update(t, recon, t_lr, st)
-                self.last = (recon, mu, logvar)
-                return recon, mu, logvar
-            # teacher: gate + quality heads only (train_hybrid.py:891-904, 914, 922)
-            b, e = self.t_range
-            if self.grad_sync is not None:
-                self.grad_sync(self.t_grads[b:e])
-            _lib.check(_lib.lib.lo_clip_adamw_step(t._flat[b:e].data_ptr(), self.t_grads[b:e].data_ptr(), self.t_m.data_ptr(),
-                                                   self.t_v.data_ptr(), e - b, float(self.max_grad_norm), float(t_lr),
-                                                   float(self.betas[0]), float(self.betas[1]), float(self.eps),
-                                                   float(self.weight_decay), self.opt_steps, self.t_scratch.data_ptr(), st),
-                       "lo_clip_adamw_step(teacher)")
-            # the gate / head weights are read in fp32 by the head kernels: no re-pack needed
-        self.last = (recon, mu, logvar)
-        return recon, mu, logvar
+            # the VAE's optimizer step of this call has counted itself already: the teacher's schedule is at the step before
+            t_lr = cosine_warm_restarts_lr(self.teacher_base_lr, self.min_lr, self.t0, 2, self.opt_steps - 1)
+            self._teacher_update(self.teacher, recon, t_lr, st)
 
     def _teacher_grads(self, t, recon, tout, first: bool = True) -> None:
         """teacher_loss.backward() into ``self.t_grads`` (train_hybrid.py:891-904): the gate and the quality heads
@@ -856,17 +751,24 @@ class HybridStepper(VAEStepper):
                            seed=(images, self.seed_coef, self.reward_grad_weight / (8.0 * B * float(self.accum))))
         return rg["seed"]
 
-    def _teacher_full_update(self, t, recon, t_lr, st):
-        """clip + AdamW with every teacher parameter live (train_hybrid.py:914, 922) on the gradients of `_teacher_grads`:
-        lo_teacher_clip_adamw_full."""
-        eng = t._engine(recon.shape[0])
+    def _teacher_update(self, t, recon, t_lr: float, st) -> None:
+        """clip + AdamW on the gradients of `_teacher_grads` over `t_range` (train_hybrid.py:914, 922).  The reference as it executes:
+        the gate and the quality heads only (train_hybrid.py:891-904), one flat range, which the head kernels read in fp32 -- no
+        re-pack needed.  ``teacher_full_backward``: every teacher parameter live (lo_teacher_clip_adamw_full); the conv / attention
+        operands are packed fp16 copies and are re-packed before the next forward."""
+        b, e = self.t_range
+        eng = t._engine(recon.shape[0]) if self.teacher_full_backward else None
         if self.grad_sync is not None:
-            self.grad_sync(self.t_grads)
-        _lib.check(_lib.lib.lo_teacher_clip_adamw_full(eng.handle, t._flat.data_ptr(), self.t_grads.data_ptr(), self.t_m.data_ptr(),
-                                                       self.t_v.data_ptr(), float(self.max_grad_norm), float(t_lr), float(self.betas[0]),
-                                                       float(self.betas[1]), float(self.eps), float(self.weight_decay), self.opt_steps,
-                                                       self.t_scratch.data_ptr(), st), "lo_teacher_clip_adamw_full")
-        t.mark_weights_changed()              # conv / attention operands are packed fp16 copies: re-packed before the next forward
+            self.grad_sync(self.t_grads[b:e])
+        args = (float(self.max_grad_norm), float(t_lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
+                float(self.weight_decay), self.opt_steps, self.t_scratch.data_ptr(), st)
+        if self.teacher_full_backward:
+            _lib.check(_lib.lib.lo_teacher_clip_adamw_full(eng.handle, t._flat.data_ptr(), self.t_grads.data_ptr(), self.t_m.data_ptr(),
+                                                           self.t_v.data_ptr(), *args), "lo_teacher_clip_adamw_full")
+            t.mark_weights_changed()
+        else:
+            _lib.check(_lib.lib.lo_clip_adamw_step(t._flat[b:e].data_ptr(), self.t_grads[b:e].data_ptr(), self.t_m.data_ptr(),
+                                                   self.t_v.data_ptr(), e - b, *args), "lo_clip_adamw_step(teacher)")
 
     def metrics(self) -> Dict[str, float]:
         """The 12 scalars of train_hybrid.py:929-942 (+ grad norm / lr); one host copy."""
@@ -875,7 +777,7 @@ class HybridStepper(VAEStepper):
         self._check_sync(v[15])
         recon, kl, vae_loss, pg = v[0:4]
         q_loss, sem_r, q_r, baseline, adv, t_loss, q_mean = v[7:14]
-        self._update_loss_scale(v[14])
+        self._loss_scale.observed(v[14], self.opt_steps, self.opt_steps, self._window_open())
         return {"recon_loss": recon, "kl_loss": kl, "quality_loss": q_loss, "pg_loss": pg, "semantic_reward": sem_r,
                 "quality_reward": q_r, "baseline": baseline, "advantage": adv, "vae_loss": vae_loss, "teacher_loss": t_loss,
                 "total_loss": vae_loss + t_loss, "quality_scores": q_mean, "grad_norm": v[4], "clip_coef": v[5],

@@ -17,6 +17,7 @@ import torch
 
 from oracle import vae_ref as R
 from tests.guarded import check_guards, gin, guarded, written
+from tests.stepper_scenarios import _OneGpuRanks
 
 pytestmark = pytest.mark.gpu
 
@@ -147,39 +148,6 @@ def _stepper(L, **kw):
     m.load_state_dict(R.closed_form_params(L))
     m = m.to("cuda")
     return m, VAEStepper(m, **kw)
-
-
-class _OneGpuRanks:
-    """Stand-in for FlatGradSync on one GPU, everything on the current stream.  Without a gathered buffer it only collects the
-    factor block a rank hands over; with one it plays the exchange of that rank: the hooks get the concatenated blocks of all ranks.
-    The other gradient ranges stay this rank's own (the test compares two runs of the same rank)."""
-    supports_then = True
-
-    def __init__(self, world, gathered=None):
-        self.world, self.gathered, self.block = world, gathered, None
-
-    def begin(self, g, then=None, pre=None, sumsq_scratch=None):
-        if pre is not None:
-            pre()
-        assert sumsq_scratch is None and then is None
-        return True
-
-    def begin_factored(self, pieces, factors, materialize, then=None, pre=None):
-        if pre is not None:
-            pre()                                   # the factor block is final behind this
-        if self.gathered is None:
-            self.block = factors.clone()
-            return False
-        materialize(self.gathered, self.world)
-        if then is not None:
-            then()
-        return True
-
-    def finish(self):
-        pass
-
-    def average_small(self, t):
-        pass
 
 
 def _shards(L, Bper, world):

@@ -70,7 +70,7 @@ def leg_op(a):
     import torch
     sys.path.insert(0, ROOT)
     from lunaris_orion_amd import _lib
-    from lunaris_orion_amd.trainer import _grad_range
+    from lunaris_orion_amd.parallel import grad_range as _grad_range
     from lunaris_orion_amd.vae import LunarisCoreVAE
     vae = LunarisCoreVAE(latent_dim=a.latent).to("cuda")
     eng = vae._engine(a.batch)

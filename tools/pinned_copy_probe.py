@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Does a non_blocking device -> pinned-host copy of one float return at once while the GPU is busy?  (The loss-scale policy of
-VAEStepper._observe_skipped_updates relies on it; a blocking copy would drain the queue once per step.)"""
+LossScaleObserver.step_enqueued (trainer.py) relies on it; a blocking copy would drain the queue once per step.)"""
 import time
 import torch
 a = torch.randn(8192, 8192, device="cuda", dtype=torch.float16)
